@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the wind-inversion hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config metric|2|3|4|5] [--scaling strong|weak] ...
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config metric|2|3|4|5] [--scaling strong|weak] [--full]
+                  [--dump-outputs DIR] ...
 
 One "step" = one pass of `xsw_invert` (default: CMOD5.N mono-VV, reference-default 0.1 m/s x 1 deg x 0.1 deg LUT)
 over a synthetic float32 raster that is already resident in HBM (sigma0 + incidence + complex64 ancillary wind in,
@@ -14,10 +15,19 @@ the ranks are torchrun's.  Default `--scaling strong`: the SAME raster (20000 x 
 output tiles are gathered on rank 0 over RCCL inside the timed step, chunk by chunk behind the kernel.
 `--scaling weak`: every rank inverts a full-size tile of an N-times taller raster.
 
-Prints ONE JSON line (rank 0): throughput, the HBM roofline of the dominant kernel (algorithmic bytes / HIP-event
-kernel time) with the VALU view of the same kernel next to it, the sigma0_detrend kernel (the HBM-bound kernel of
-the path), LUT build/upload time, the bit-parity configuration (sigma0 already in dB), and a CPU baseline (the
-oracle's C restatement of the reference kernel on this box's cores, on a bounded crop of the same raster).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and reports the throughput
+(`value`, `ms_per_step`) and the host-route LUT build/upload time.  `--full` adds everything else, at the cost of
+extra passes: the HBM roofline of the dominant kernel (algorithmic bytes / HIP-event kernel time) with the VALU view of
+the same kernel next to it (one extra pass with the device-side statistics on), the device-route LUT build time, the
+sigma0_detrend kernel (the HBM-bound kernel of the path), the bit-parity configuration (sigma0 already in dB), the
+exhaustive / hard-scene / gmf_eval / latency / nesz figures, a CPU baseline (the oracle's C restatement of the reference
+kernel on the host's cores, on a bounded crop of the same raster) and, for N > 1, the gather-only and no-gather figures.
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of the timed path receives it (rank 0: the
+gathered raster), to DIR/<name>.npy: complex64 winds as float32 [..., 2] (real, imaginary), the detrended sigma0 as
+float64, at the pixels where the outputs are finite (NaN marks a pixel without a retrieval: NaN incidence or sigma0 in).
+With more than DUMP_MAX_PIXELS such pixels, DUMP_MAX_PIXELS of them are drawn with a fixed seed (kept in raster order), so
+that two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -44,6 +54,8 @@ BYTES_READ_PX = 16       # inc f32 + sigma0 f32 + ancillary complex64   (SURVEY.
 BYTES_WRITE_PX = 8       # complex64 wind
 PROFILE_ROUND = "r05"
 PCIE_PEAK_GBS = 64.0      # PCIe Gen5 x16, one direction (MI355X_MICROARCH.md host link)
+DUMP_MAX_PIXELS = 1 << 21  # --dump-outputs: 16 MB per complex64 output, so the two outputs of dual-pol stay under 64 MB
+DUMP_SEED = 20260320
 
 CONFIGS = {  # BASELINE.json configs (1 is the CPU plumbing case: tests/test_gpu_api.py::test_sigma0_detrend)
     "metric": dict(lines=20000, samples=20000, mode="mono", lut="cmod5n", note="the metric's raster"),
@@ -344,6 +356,29 @@ def time_steps(step, steps, warmup, stream, after=None):
     return dt, float(np.mean([a.elapsed_time(b) for a, b in ev]))
 
 
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: the tensors of `outputs` (name -> tensor, all of one shape) to dirname/<name>.npy as float32 / float64
+    (complex as [..., 2]), at the pixels where every one of them is finite -- NaN marks a pixel without a retrieval (NaN
+    incidence or sigma0 in; the tests pin that mask to the inputs), so a build whose mask differs shifts the sample and
+    compares unequal.  With more than DUMP_MAX_PIXELS such pixels, DUMP_MAX_PIXELS of them drawn with DUMP_SEED (in raster
+    order)."""
+    os.makedirs(dirname, exist_ok=True)
+    flat = {name: t.reshape(-1) for name, t in outputs.items()}
+    ok = None
+    for t in flat.values():
+        f = torch.isfinite(torch.view_as_real(t)).all(dim=-1) if t.is_complex() else torch.isfinite(t)
+        ok = f if ok is None else ok & f
+    idx = torch.nonzero(ok).flatten()
+    if idx.numel() > DUMP_MAX_PIXELS:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(idx.numel(), DUMP_MAX_PIXELS, replace=False))
+        idx = idx[torch.from_numpy(pick).to(idx.device)]
+    for name, t in flat.items():
+        t = t[idx]
+        a = (torch.view_as_real(t) if t.is_complex() else t).cpu().numpy()
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), (name, a.dtype)
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
 def end_to_end_parity_figure(ctx, _lib, inc, s_vv, anc, out, lines, samples, algo):
     """The bit-parity route with NOTHING left outside the timer: the linear float32 sigma0 raster starts on the HOST (pageable
     numpy), incidence / ancillary wind / output stay resident, as in `value`.  Timed = one `xsw_invert` call with
@@ -512,7 +547,7 @@ def hard_scene_figures(ctx, _lib, stream, device, samples, algo, lines_hs=4000):
 
 def detrend_figures(args, ctx, stream, s_vv, lines, samples):
     """`sigma0 / ratio_row` (detrend.py:63-64) on the resident float32 raster -> float64: 4 B read + 8 B written per
-    pixel -- the one HBM-bound kernel of the path."""
+    pixel -- the one HBM-bound kernel of the path.  Returns (figure, the float64 raster of the last step)."""
     from xsarsea_amd import _lib
     det = torch.empty((lines, samples), dtype=torch.float64, device=s_vv.device)
     ratio = np.random.default_rng(0).uniform(0.5, 2.0, samples)
@@ -521,7 +556,6 @@ def detrend_figures(args, ctx, stream, s_vv, lines, samples):
         ctx.detrend_raw(lines, samples, _lib.XSW_F32, _lib.XSW_F64, _lib.MEM_DEVICE, s_vv.data_ptr(), ratio, det.data_ptr())
 
     dt, kernel_ms = time_steps(step, args.steps, max(args.warmup, 1), stream)
-    del det
     px = lines * samples
     achieved = 12.0 * px / (kernel_ms * 1e-3) / 1e9
     traffic = None
@@ -537,7 +571,7 @@ def detrend_figures(args, ctx, stream, s_vv, lines, samples):
             "kernel_ms": round(kernel_ms, 4), "bytes_per_pixel": 12,
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4), "frac_of_measured_copy_rate_6290": round(achieved / 6290.0, 4),
-                         "traffic": traffic, "traffic_provenance": prov}}
+                         "traffic": traffic, "traffic_provenance": prov}}, det
 
 
 def gmf_eval_figures(args, ctx, stream, device, n=400_000_000):
@@ -718,14 +752,22 @@ def main():
     ap.add_argument("--resolution", default="high", choices=["high", "low"],
                     help="LUT resolution passed to Model.to_lut: high = the reference default 501x499x181, low = 51x250x73 "
                          "(a parity-test configuration, SURVEY 8d; implies no CPU baseline / exhaustive figure)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the detrend / dB-parity / exhaustive side figures")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: roofline / VALU view (extra statistics pass), "
+                         "device-route LUT build, side figures, CPU baseline + parity; N > 1: gather-only and no-gather figures")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity figures")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the detrend / dB-parity / exhaustive side figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64; the finite pixels, "
+                         f"above {DUMP_MAX_PIXELS} of them a fixed-seed sample)")
     ap.add_argument("--verify-gather", action="store_true",
                     help="N > 1: the ranks' input tiles are gathered on rank 0, which inverts the whole raster in ONE launch and "
                          "compares it bit for bit with the gathered result (exit code 3 on a mismatch)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
@@ -774,7 +816,7 @@ def main():
     stream = torch.cuda.Stream(device=device)  # the kernels, the events and RCCL all use this stream
     torch.cuda.set_stream(stream)
     ctx.set_stream(stream.cuda_stream)
-    if cfg["lut"] == "cmod5n":
+    if cfg["lut"] == "cmod5n" and args.full:
         # time to a searchable LUT, device route (options.lut_build="device": grid fill + interpolation + dB + layout on the
         # GPU, xsw_lut_build); the timed steps below then run on the host-built table (bit parity with the CPU baseline)
         from xsarsea_amd.windspeed import _engine, get_model
@@ -797,7 +839,10 @@ def main():
     scene_sum0 = int(s_vv.view(torch.int32).to(torch.int64).sum().item())  # (--verify-gather checks that nothing wrote into the inputs since)
     if mode == "detrend":
         if rank == 0:
-            d = detrend_figures(args, ctx, stream, s_vv, lines, samples)
+            d, det = detrend_figures(args, ctx, stream, s_vv, lines, samples)
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, {"sigma0_detrended": det})
+            del det
             print(json.dumps({
                 "metric": "Mpixels/s sigma0_detrend", "value": d["value"], "unit": "Mpixels/s", "n_gpus": 1, "steps": args.steps,
                 "warmup": args.warmup, "ms_per_step": d["kernel_ms"], "higher_is_better": True, "scaling": "strong",
@@ -886,9 +931,12 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:  # before anything below runs the step again
+        res_co, res_dual = (pipe.full, pipe.full_dual) if coded else (out, out_dual)
+        dump_outputs(args.dump_outputs, dict(wind_co=res_co, **({"wind_dual": res_dual} if mode == "dual" else {})))
 
     mg = None
-    if world > 1:
+    if world > 1 and args.full:
         # what explains a scaling curve: every rank's kernel time, the bytes rank 0 ingests, the raw transfer time of those
         # bytes (a gather of the already computed codes, nothing else in flight), the part of the step the transfers and the
         # expansion are NOT hidden behind the kernels, and the same steps with the outputs left sharded (no exchange at all)
@@ -927,22 +975,22 @@ def main():
               "note": "gather_only_ms: the gather alone (codes already computed, nothing else in flight), wall clock between barriers; "
                       "exposed_gather_ms: rank 0's step from first launch to the expanded raster minus its kernels' time"}
 
-    # evaluated-work counters: one extra, untimed pass with the device-side statistics on
-    ctx.stats_enable(True)
-    step()
-    gather()
-    fence()
-    stats = ctx.stats()
-    ctx.stats_enable(False)
-    if world > 1:
-        t = torch.tensor([stats["pixels_co"], stats["cand_co"], stats["pixels_exact"]], dtype=torch.float64, device=device)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        stats["pixels_co"], stats["cand_co"], stats["pixels_exact"] = (int(x) for x in t.tolist())
-        t = torch.tensor([kernel_ms], dtype=torch.float64, device=device)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        kernel_ms_max = float(t.item())
-    else:
-        kernel_ms_max = kernel_ms
+    stats, kernel_ms_max = None, kernel_ms
+    if args.full:
+        # evaluated-work counters: one extra, untimed pass with the device-side statistics on
+        ctx.stats_enable(True)
+        step()
+        gather()
+        fence()
+        stats = ctx.stats()
+        ctx.stats_enable(False)
+        if world > 1:
+            t = torch.tensor([stats["pixels_co"], stats["cand_co"], stats["pixels_exact"]], dtype=torch.float64, device=device)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            stats["pixels_co"], stats["cand_co"], stats["pixels_exact"] = (int(x) for x in t.tolist())
+            t = torch.tensor([kernel_ms], dtype=torch.float64, device=device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            kernel_ms_max = float(t.item())
 
     gather_ok = None
     w_inc = w_s = w_anc = w_vh = w_dsig = None
@@ -999,64 +1047,65 @@ def main():
     if rank == 0:
         px_total = total_lines * samples
         value = px_total * args.steps / dt / 1e6
-        bytes_px = (BYTES_READ_PX + BYTES_WRITE_PX) if mode == "mono" else (24 + 16)  # dual: +vh, +dsig; 2 outputs
-        if coded:  # N > 1: the kernels write 4-byte codes instead of complex64
-            bytes_px = (BYTES_READ_PX + 4) if mode == "mono" else (24 + 8)
-        # the dominant kernel reads every pixel's inputs and writes the pixels it decides itself (the ones it hands to
-        # k_invert_band2 / k_invert_list are written there); the chain as a whole moves bytes_px per pixel
-        read_px = BYTES_READ_PX if mode == "mono" else 24
-        handed = (tm.get("last_band2_pixels", 0) + tm.get("last_blocks_pixels", 0) + tm.get("last_list_pixels", 0)) if second_ms is not None else 0
-        achieved = (read_px * lines * samples + (bytes_px - read_px) * (lines * samples - handed)) / (kernel_ms * 1e-3) / 1e9  # rank 0's tile / rank 0's kernel time
-        chain_ms = kernel_ms + (second_ms or 0.0)
-        chain_ms_max = kernel_ms_max + (second_ms or 0.0)
-        is_metric_shape = (mode == "mono" and args.resolution == "high" and cfg["lut"] == "cmod5n" and args.algo == "pruned"
-                           and (lines, samples) == (20000, 20000))
-        traffic, traffic_prov, chain_traffic = None, None, None
-        if is_metric_shape:
-            tj, traffic_prov = fresh_profile(f"{PROFILE_ROUND}_hbm_traffic_summary.json")
-            if tj:
-                # the dominant kernel's own traffic when the profile has it per kernel (else the whole chain's)
-                per = tj.get("per_kernel_20000x20000", {}).get("k_invert_band")
-                traffic = int((per or tj["k_invert_20000x20000"])["hbm_bytes_per_launch"])
-                chain_traffic = int(tj["k_invert_20000x20000"]["hbm_bytes_per_launch"])
         cand_full = int(lut.shape[1] * lut.shape[2])
-        evaluated = stats["cand_co"] / max(stats["pixels_co"], 1)
-        lane_ops = OPS_PER_CANDIDATE * stats["cand_co"] / world / (chain_ms_max * 1e-3) if args.algo == "pruned" else \
-            OPS_PER_CANDIDATE * cand_full * lines * samples / (kernel_ms * 1e-3)
-        valu = {"bound": "valu", "unit": "lane-ops/s", "peak": LANE_OPS_PEAK,
-                "ops_per_candidate": OPS_PER_CANDIDATE,
-                "candidates_per_pixel_full_grid": cand_full,
-                "evaluated_candidates_per_pixel": round(evaluated, 1),
-                "pixels_exact_fallback": stats["pixels_exact"],
-                "achieved": float(f"{lane_ops:.4g}"), "frac": round(lane_ops / LANE_OPS_PEAK, 5),
-                "peak_packed_fp32": LANE_OPS_PEAK, "peak_issue": LANE_OPS_PEAK_ISSUE, "frac_of_issue_peak": round(lane_ops / LANE_OPS_PEAK_ISSUE, 5),
-                "note": "useful work only: 6 lane-ops x candidates scored (statistics pass, every window swept in k_invert_band) / the chain's kernel time. "
-                        "`frac` is against `peak` = peak_packed_fp32 (256 CU x 128 lanes x 2.4 GHz, SURVEY 8d's figure: packed FP32); `frac_of_issue_peak` against "
-                        "peak_issue (64 lanes per CU per clock: one wave64 instruction per 4 cycles per SIMD), the peak the counter figures under `issue` "
-                        "(valu_issue_frac_of_simd_cycles) are measured against -- the two peaks differ by 2; "
-                        "the grid has candidates_per_pixel_full_grid points, all but the evaluated ones are excluded by an exact bound"}
-        sq, sq_prov = (fresh_profile(f"{PROFILE_ROUND}_pmc_counters_summary.json") if is_metric_shape else (None, None))
-        sq = (sq or {}).get("k_invert_band")
-        if sq_prov and "stale_profile" in sq_prov:
-            valu["issue"] = sq_prov
-        if sq and is_metric_shape:
-            try:
-                pp = sq["per_pixel"]
-                cyc = sq["GRBM_GUI_ACTIVE"] / 8.0  # summed over the 8 XCDs
-                valu["issue"] = {"kernel": "k_invert_band",
-                                 "valu_insts_per_pixel": round(pp["SQ_INSTS_VALU"], 1), "salu_insts_per_pixel": round(pp["SQ_INSTS_SALU"], 1),
-                                 "vmem_rd_insts_per_pixel": round(pp["SQ_INSTS_VMEM_RD"], 1),
-                                 "l1_line_accesses_per_pixel": round(pp["TCP_TOTAL_CACHE_ACCESSES_sum"], 1),
-                                 "valu_issue_frac_of_simd_cycles": round(sq["SQ_INSTS_VALU"] * 4.0 / (1024.0 * cyc), 3),
-                                 "texture_addresser_busy_frac": round(sq["TA_TA_BUSY_sum"] / (256.0 * cyc), 3),
-                                 "wave_time_waiting_frac": round(sq["SQ_WAIT_ANY"] / sq["SQ_WAVE_CYCLES"], 3),
-                                 "valu_int32_insts_per_pixel": round(pp.get("SQ_INSTS_VALU_INT32", float("nan")), 1),
-                                 "branch_insts_per_pixel": round(pp.get("SQ_INSTS_BRANCH", float("nan")), 1),
-                                 "measured_on": sq_prov.get("measured_on"),
-                                 "source": f"profiles/{PROFILE_ROUND}_pmc_counters_summary.json (rocprofv3 --pmc passes of profiles/collect_counters.sh, "
-                                           "same workload; 4 issue cycles per wave64 VALU instruction, 1024 SIMDs, 256 TAs, cycles = GRBM_GUI_ACTIVE / 8 XCDs)"}
-            except Exception:
-                pass
+        if args.full:
+            bytes_px = (BYTES_READ_PX + BYTES_WRITE_PX) if mode == "mono" else (24 + 16)  # dual: +vh, +dsig; 2 outputs
+            if coded:  # N > 1: the kernels write 4-byte codes instead of complex64
+                bytes_px = (BYTES_READ_PX + 4) if mode == "mono" else (24 + 8)
+            # the dominant kernel reads every pixel's inputs and writes the pixels it decides itself (the ones it hands to
+            # k_invert_band2 / k_invert_list are written there); the chain as a whole moves bytes_px per pixel
+            read_px = BYTES_READ_PX if mode == "mono" else 24
+            handed = (tm.get("last_band2_pixels", 0) + tm.get("last_blocks_pixels", 0) + tm.get("last_list_pixels", 0)) if second_ms is not None else 0
+            achieved = (read_px * lines * samples + (bytes_px - read_px) * (lines * samples - handed)) / (kernel_ms * 1e-3) / 1e9  # rank 0's tile / rank 0's kernel time
+            chain_ms = kernel_ms + (second_ms or 0.0)
+            chain_ms_max = kernel_ms_max + (second_ms or 0.0)
+            is_metric_shape = (mode == "mono" and args.resolution == "high" and cfg["lut"] == "cmod5n" and args.algo == "pruned"
+                               and (lines, samples) == (20000, 20000))
+            traffic, traffic_prov, chain_traffic = None, None, None
+            if is_metric_shape:
+                tj, traffic_prov = fresh_profile(f"{PROFILE_ROUND}_hbm_traffic_summary.json")
+                if tj:
+                    # the dominant kernel's own traffic when the profile has it per kernel (else the whole chain's)
+                    per = tj.get("per_kernel_20000x20000", {}).get("k_invert_band")
+                    traffic = int((per or tj["k_invert_20000x20000"])["hbm_bytes_per_launch"])
+                    chain_traffic = int(tj["k_invert_20000x20000"]["hbm_bytes_per_launch"])
+            evaluated = stats["cand_co"] / max(stats["pixels_co"], 1)
+            lane_ops = OPS_PER_CANDIDATE * stats["cand_co"] / world / (chain_ms_max * 1e-3) if args.algo == "pruned" else \
+                OPS_PER_CANDIDATE * cand_full * lines * samples / (kernel_ms * 1e-3)
+            valu = {"bound": "valu", "unit": "lane-ops/s", "peak": LANE_OPS_PEAK,
+                    "ops_per_candidate": OPS_PER_CANDIDATE,
+                    "candidates_per_pixel_full_grid": cand_full,
+                    "evaluated_candidates_per_pixel": round(evaluated, 1),
+                    "pixels_exact_fallback": stats["pixels_exact"],
+                    "achieved": float(f"{lane_ops:.4g}"), "frac": round(lane_ops / LANE_OPS_PEAK, 5),
+                    "peak_packed_fp32": LANE_OPS_PEAK, "peak_issue": LANE_OPS_PEAK_ISSUE, "frac_of_issue_peak": round(lane_ops / LANE_OPS_PEAK_ISSUE, 5),
+                    "note": "useful work only: 6 lane-ops x candidates scored (statistics pass, every window swept in k_invert_band) / the chain's kernel time. "
+                            "`frac` is against `peak` = peak_packed_fp32 (256 CU x 128 lanes x 2.4 GHz, SURVEY 8d's figure: packed FP32); `frac_of_issue_peak` against "
+                            "peak_issue (64 lanes per CU per clock: one wave64 instruction per 4 cycles per SIMD), the peak the counter figures under `issue` "
+                            "(valu_issue_frac_of_simd_cycles) are measured against -- the two peaks differ by 2; "
+                            "the grid has candidates_per_pixel_full_grid points, all but the evaluated ones are excluded by an exact bound"}
+            sq, sq_prov = (fresh_profile(f"{PROFILE_ROUND}_pmc_counters_summary.json") if is_metric_shape else (None, None))
+            sq = (sq or {}).get("k_invert_band")
+            if sq_prov and "stale_profile" in sq_prov:
+                valu["issue"] = sq_prov
+            if sq and is_metric_shape:
+                try:
+                    pp = sq["per_pixel"]
+                    cyc = sq["GRBM_GUI_ACTIVE"] / 8.0  # summed over the 8 XCDs
+                    valu["issue"] = {"kernel": "k_invert_band",
+                                     "valu_insts_per_pixel": round(pp["SQ_INSTS_VALU"], 1), "salu_insts_per_pixel": round(pp["SQ_INSTS_SALU"], 1),
+                                     "vmem_rd_insts_per_pixel": round(pp["SQ_INSTS_VMEM_RD"], 1),
+                                     "l1_line_accesses_per_pixel": round(pp["TCP_TOTAL_CACHE_ACCESSES_sum"], 1),
+                                     "valu_issue_frac_of_simd_cycles": round(sq["SQ_INSTS_VALU"] * 4.0 / (1024.0 * cyc), 3),
+                                     "texture_addresser_busy_frac": round(sq["TA_TA_BUSY_sum"] / (256.0 * cyc), 3),
+                                     "wave_time_waiting_frac": round(sq["SQ_WAIT_ANY"] / sq["SQ_WAVE_CYCLES"], 3),
+                                     "valu_int32_insts_per_pixel": round(pp.get("SQ_INSTS_VALU_INT32", float("nan")), 1),
+                                     "branch_insts_per_pixel": round(pp.get("SQ_INSTS_BRANCH", float("nan")), 1),
+                                     "measured_on": sq_prov.get("measured_on"),
+                                     "source": f"profiles/{PROFILE_ROUND}_pmc_counters_summary.json (rocprofv3 --pmc passes of profiles/collect_counters.sh, "
+                                               "same workload; 4 issue cycles per wave64 VALU instruction, 1024 SIMDs, 256 TAs, cycles = GRBM_GUI_ACTIVE / 8 XCDs)"}
+                except Exception:
+                    pass
         mode_txt = "mono-VV" if mode == "mono" else "dual-pol (VV + S1 VH GMF)"
         par = f"row tiles x{n_gpus}" + (f" ({args.scaling} scaling: {'the same raster split' if args.scaling == 'strong' else 'one full tile per rank'}), "
                                         f"RCCL gather of 4-byte grid codes to rank 0 in the step ({n_chunks} chunks behind the kernel), expanded to complex64 there"
@@ -1073,38 +1122,39 @@ def main():
                                    f"complex64 out, algo={args.algo}, sigma0 -> dB fused on the device",
                        "baseline_config": args.config, "lines": total_lines, "samples": samples,
                        "lines_rank0": lines, "lut": [int(x) for x in lut.shape], "parallelism": par},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_provenance": traffic_prov,
-                         "kernel": {"exhaustive": "k_invert_exhaustive32", "exhaustive_f64": "k_invert_exhaustive"}.get(
-                             args.algo, "k_invert_band" if second_ms is not None else "k_invert"),
-                         "kernel_ms": round(kernel_ms, 3), "bytes_per_pixel": bytes_px,
-                         "second_kernel": None if second_ms is None else dict(
-                             {"kernel": "k_invert_list", "kernel_ms": round(second_ms, 3), "pixels_last_launch": tm.get("last_list_pixels")},
-                             **({"kernel": "k_invert_band2 + k_invert_blocks + k_invert_list", "k_invert_band2_ms": round(tm.get("band2_kernel_ms", 0.0) / args.steps, 3),
-                                 "k_invert_blocks_ms": round(tm.get("blocks_kernel_ms", 0.0) / args.steps, 3),
-                                 "k_invert_list_ms": round(tm["second_kernel_ms"] / args.steps, 3),
-                                 "pixels_to_band2_last_launch": tm.get("last_band2_pixels"),
-                                 "pixels_to_blocks_last_launch": tm.get("last_blocks_pixels")} if tm.get("band2_kernel_ms", 0.0) > 0.0 else {})),
-                         "chain": {"kernels": "k_invert_band + k_invert_band2 + k_invert_blocks + k_invert_list" if second_ms is not None else "k_invert",
-                                   "ms": round(chain_ms, 3), "achieved": round(bytes_px * lines * samples / (chain_ms * 1e-3) / 1e9, 3),
-                                   "frac": round(bytes_px * lines * samples / (chain_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6),
-                                   "traffic": chain_traffic},
-                         "step_kernels_ms": round(step_kernels_ms, 3),
-                         "note": f"algorithmic raster bytes ({read_px} B read per pixel x rank 0's {lines * samples} px + {bytes_px - read_px} B written per "
-                                 "pixel the kernel decides itself, i.e. not handed to k_invert_band2 / k_invert_blocks / k_invert_list) / mean "
-                                 "duration of the dominant kernel per step (HIP events on the launch stream, recorded by the library around each kernel); "
-                                 "chain: all bytes of the step / the four kernels' time; "
-                                 "the search itself is bound by VALU issue and the texture-address path, not by HBM: see valu.  "
-                                 "north_star's '>= 40 % of the HBM-read roofline' is OUT OF REACH for an exact search: at 40 % of 8 TB/s a pixel's 16 B of "
-                                 "input may cost 5 ps, i.e. ~5 wave-instructions (300 lane-instructions) end to end, while the exact branch-and-bound "
-                                 "spends 44 VALU + 18 SALU wave-instructions per pixel (~2 800 lane-instructions: 16 for stage 1 -- dB, incidence bin, three "
-                                 "rays, window --, 25 for the band passes, 3 for the store) at 86 % VALU issue: the binding roofline is VALU issue, "
-                                 "and the kernel sits at 3.5 % of HBM (2.3 % counting reads only) because it is 12x over that instruction budget, not because it wastes bytes "
-                                 "(counter traffic 1.1x the algorithmic bytes)",
-                         "valu": valu},
-            "lut": timings,
         }
-        extras = n_gpus == 1 and not args.no_extras
+        if args.full:
+            res["roofline"] = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_provenance": traffic_prov,
+                               "kernel": {"exhaustive": "k_invert_exhaustive32", "exhaustive_f64": "k_invert_exhaustive"}.get(
+                                   args.algo, "k_invert_band" if second_ms is not None else "k_invert"),
+                               "kernel_ms": round(kernel_ms, 3), "bytes_per_pixel": bytes_px,
+                               "second_kernel": None if second_ms is None else dict(
+                                   {"kernel": "k_invert_list", "kernel_ms": round(second_ms, 3), "pixels_last_launch": tm.get("last_list_pixels")},
+                                   **({"kernel": "k_invert_band2 + k_invert_blocks + k_invert_list", "k_invert_band2_ms": round(tm.get("band2_kernel_ms", 0.0) / args.steps, 3),
+                                       "k_invert_blocks_ms": round(tm.get("blocks_kernel_ms", 0.0) / args.steps, 3),
+                                       "k_invert_list_ms": round(tm["second_kernel_ms"] / args.steps, 3),
+                                       "pixels_to_band2_last_launch": tm.get("last_band2_pixels"),
+                                       "pixels_to_blocks_last_launch": tm.get("last_blocks_pixels")} if tm.get("band2_kernel_ms", 0.0) > 0.0 else {})),
+                               "chain": {"kernels": "k_invert_band + k_invert_band2 + k_invert_blocks + k_invert_list" if second_ms is not None else "k_invert",
+                                         "ms": round(chain_ms, 3), "achieved": round(bytes_px * lines * samples / (chain_ms * 1e-3) / 1e9, 3),
+                                         "frac": round(bytes_px * lines * samples / (chain_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6),
+                                         "traffic": chain_traffic},
+                               "step_kernels_ms": round(step_kernels_ms, 3),
+                               "note": f"algorithmic raster bytes ({read_px} B read per pixel x rank 0's {lines * samples} px + {bytes_px - read_px} B written per "
+                                       "pixel the kernel decides itself, i.e. not handed to k_invert_band2 / k_invert_blocks / k_invert_list) / mean "
+                                       "duration of the dominant kernel per step (HIP events on the launch stream, recorded by the library around each kernel); "
+                                       "chain: all bytes of the step / the four kernels' time; "
+                                       "the search itself is bound by VALU issue and the texture-address path, not by HBM: see valu.  "
+                                       "a target of '>= 40 % of the HBM-read roofline' is OUT OF REACH for an exact search: at 40 % of 8 TB/s a pixel's 16 B of "
+                                       "input may cost 5 ps, i.e. ~5 wave-instructions (300 lane-instructions) end to end, while the exact branch-and-bound "
+                                       "spends 44 VALU + 18 SALU wave-instructions per pixel (~2 800 lane-instructions: 16 for stage 1 -- dB, incidence bin, three "
+                                       "rays, window --, 25 for the band passes, 3 for the store) at 86 % VALU issue: the binding roofline is VALU issue, "
+                                       "and the kernel sits at 3.5 % of HBM (2.3 % counting reads only) because it is 12x over that instruction budget, not because it wastes bytes "
+                                       "(counter traffic 1.1x the algorithmic bytes)",
+                               "valu": valu}
+        res["lut"] = timings
+        extras = args.full and n_gpus == 1 and not args.no_extras
         if extras and mode == "mono":
             # the bit-parity configuration for float32 rasters: sigma0 converted to dB by numpy on the host (as the
             # drop-in API does by default, options.db_on_device="auto") and resident in HBM before the timed region
@@ -1141,9 +1191,9 @@ def main():
         if extras:
             res["gmf_eval"] = gmf_eval_figures(args, ctx, stream, device)
             res["latency"] = latency_figures(local_rank)
-            res["detrend"] = detrend_figures(args, ctx, stream, s_vv, lines, samples)
+            res["detrend"] = detrend_figures(args, ctx, stream, s_vv, lines, samples)[0]
             res["nesz_flatten"] = nesz_figures(args, ctx, stream, s_vv, inc, lines, samples)
-        if n_gpus == 1 and not args.no_cpu_baseline and mode == "mono":
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline and mode == "mono":
             cpu, parity = cpu_baseline_and_parity(ctx, inc, s_vv, anc, args.algo)
             res["cpu_baseline"] = cpu
             parity["db_mode"] = ("timed value: sigma0 -> dB fused on the device (float32 log10 correctly rounded; index_match_device_db "

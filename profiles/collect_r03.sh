@@ -19,7 +19,7 @@ cat $O/measured_on.json
 python3 -m xsarsea_amd._build --resources $O/kernel_resources.tsv > /dev/null 2>&1
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/kt
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extras > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 cp $O/kt/*/*kernel_stats.csv $O/kernel_stats.csv
 python3 - <<PY
 import csv, glob, collections
@@ -30,7 +30,7 @@ for r in rows:
     if "k_invert" in k or "k_expand" in k:
         by[k.split("(")[0]].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6)
 with open("$O/kernel_trace_durations.txt", "w") as f:
-    f.write("# per-dispatch durations (ms, launch order) of the inversion kernels, rocprofv3 --kernel-trace of bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras\n")
+    f.write("# per-dispatch durations (ms, launch order) of the inversion kernels, rocprofv3 --kernel-trace of bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extras\n")
     for k, v in by.items():
         f.write(f"{k}: n={len(v)} avg={sum(v)/len(v):.3f} ms  [{', '.join(f'{x:.2f}' for x in v)}]\n")
 print(open("$O/kernel_trace_durations.txt").read())

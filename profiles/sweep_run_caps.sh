@@ -11,7 +11,7 @@ for cfg in "64 24 64" "128 64 128" "256 256 256"; do
   lib=$(pwd)/build/libxsw_caps_$1_$2_$3.so
   XSW_LIB=$lib XSW_EXTRA_FLAGS="-DXSW_LONG_RUN_MAX=$1 -DXSW_LONG_RUN_MAX_CUT=$2 -DXSW_SWEEP_MAX=$3" python3 -m xsarsea_amd._build > /dev/null 2>&1 || exit 1
   XSW_LIB=$lib timeout -k 10 200 python3 profiles/hard_scenes.py --verify --only "$S" 2>/dev/null || exit 1
-  XSW_LIB=$lib timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
+  XSW_LIB=$lib timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('bench', d['value'], 'Mpx/s', d['ms_per_step'], 'ms  band', r['kernel_ms'], r['second_kernel'])"

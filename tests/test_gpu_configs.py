@@ -164,23 +164,33 @@ def _run_bench(extra_args, tmp_path):
     return json.loads(lines[0])
 
 
-def test_bench_line_contract(tmp_path):
-    """The default bench command (at a reduced raster so that it runs in seconds) prints ONE JSON line carrying the driver's
-    contract: metric/value/unit/n_gpus/..., `roofline` (hbm, dominant kernel, its own HIP-event time, the valu view),
-    `cpu_baseline` (oracle C port on a bounded crop) and the parity block; the two-kernel path reports both kernels."""
+def _bench_line(args, timeout):
     import json
     import subprocess
     import sys
     bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, bench, "--lines", "768", "--samples", "2048", "--steps", "2", "--warmup", "1"], env=env,
-                       capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, bench] + args, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
     j = json.loads(lines[0])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
         assert k in j, k
+    return j
+
+
+def _same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.int32), b.view(np.int32))
+
+
+def test_bench_line_contract(tmp_path):
+    """The default bench command with --full (at a reduced raster so that it runs in seconds) prints ONE JSON line carrying the
+    driver's contract: metric/value/unit/n_gpus/..., `roofline` (hbm, dominant kernel, its own HIP-event time, the valu view),
+    `cpu_baseline` (oracle C port on a bounded crop) and the parity block; the two-kernel path reports both kernels.  The plain
+    command reports the headline alone and, with --dump-outputs, writes the same last-step raster as the --full run."""
+    size = ["--lines", "768", "--samples", "2048", "--warmup", "1"]
+    j = _bench_line(size + ["--steps", "2", "--full", "--dump-outputs", str(tmp_path / "full")], 600)
     assert j["n_gpus"] == 1 and j["steps"] == 2 and j["unit"] == "Mpixels/s" and j["vs_baseline"] is None and j["value"] > 0
     rf = j["roofline"]
     assert rf["bound"] == "hbm" and rf["unit"] == "GB/s" and rf["peak"] == 8000.0 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-5
@@ -208,6 +218,38 @@ def test_bench_line_contract(tmp_path):
     assert "numpy_restatement" in cb and cb["numpy_restatement"]["equals_c_port"] is True
     # counter-derived fields are either fresh (stamped with the loaded library's device-code hash) or null with a reason
     assert rf["traffic"] is None or "measured_on" in rf["traffic_provenance"]
+    # the plain command: headline only, exactly --steps timed steps, `value` and `ms_per_step` describe the same steps
+    p = _bench_line(size + ["--steps", "3", "--dump-outputs", str(tmp_path / "plain")], 300)
+    assert p["n_gpus"] == 1 and p["steps"] == 3 and p["higher_is_better"] is True and p["dtype"] == j["dtype"] and p["metric"] == j["metric"]
+    assert p["ms_per_step"] > 0 and abs(p["value"] * p["ms_per_step"] * 1e3 / (768 * 2048) - 1) < 0.01
+    for k in ("roofline", "cpu_baseline", "parity", "detrend", "hard_scene", "latency"):
+        assert k not in p, k
+    assert "lut_device_build_ms" not in p["lut"]
+    # what the timed path computed: every retrieved pixel of the 768 x 2048 complex64 raster (below the sampling threshold),
+    # as float32 pairs; the scene's NaN incidence (8 samples per line) and sigma0 holes (0.5 %) have no wind and are left out
+    assert sorted(os.listdir(tmp_path / "plain")) == sorted(os.listdir(tmp_path / "full")) == ["wind_co.npy"]
+    a, b = np.load(tmp_path / "plain" / "wind_co.npy"), np.load(tmp_path / "full" / "wind_co.npy")
+    assert a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == 2 and 0.98 * 768 * 2040 < a.shape[0] <= 768 * 2040
+    assert np.isfinite(a).all()
+    assert _same_bits(a, b), "plain and --full runs computed different winds"
+
+
+def test_bench_dump_outputs_dual_pol_sampled(tmp_path):
+    """--dump-outputs on a raster above the sampling threshold, dual-pol (both outputs): DUMP_MAX_PIXELS sampled pixels per
+    output as float32 pairs, under 64 MB in all, and bit-identical in a second process run with the same arguments."""
+    import bench
+    args = ["--config", "3", "--lines", "1100", "--samples", "2048", "--steps", "2", "--warmup", "1"]
+    for tag in ("a", "b"):
+        _bench_line(args + ["--dump-outputs", str(tmp_path / tag)], 300)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["wind_co.npy", "wind_dual.npy"]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_PIXELS, 2)
+        assert np.isfinite(a).all() and _same_bits(a, b), f"{n}: two runs with the same arguments differ"
+        total += os.path.getsize(tmp_path / "a" / n)
+    assert total <= 64 << 20
 
 
 @pytest.mark.parametrize("cfg,shape", [("4", (2503, 1700)), ("3", (1001, 1030))])
@@ -216,7 +258,7 @@ def test_two_rank_rehearsal_gathers_the_single_launch_raster(cfg, shape, tmp_pat
     uneven tiles, chunked gather inside the step; rank 0 then inverts the whole raster in ONE launch and the gathered raster
     must equal it bit for bit (mono config-4 aspect ratio, and dual-pol with both outputs)."""
     j = _run_bench(["--gpus", "2", "--config", cfg, "--lines", str(shape[0]), "--samples", str(shape[1]), "--steps", "2",
-                    "--warmup", "1", "--verify-gather", "--no-extras", "--no-cpu-baseline"], tmp_path)
+                    "--warmup", "1", "--verify-gather", "--full", "--no-extras", "--no-cpu-baseline"], tmp_path)
     assert j["n_gpus"] == 2 and j["scaling"] == "strong" and j["gather_verified"] is True
     assert j["config"]["lines"] == shape[0] and j["config"]["lines_rank0"] == shape[0] // 2
     # the gather ships 4-byte grid codes (two for dual-pol) and explains itself
