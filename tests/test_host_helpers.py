@@ -132,3 +132,18 @@ def test_a_one_entry_devices_list_is_honoured():
             _engine._device_list()
     finally:
         xsarsea_amd.options.devices = prev
+
+
+def test_cuda_array_interface_stream_field():
+    """`__cuda_array_interface__` v3 `stream` (xsarsea_amd._device.producer_stream): absent / None = nothing to wait for, 1 and 2
+    the legacy / per-thread default streams, any other int a stream handle; 0 is disallowed by the interface."""
+    from xsarsea_amd import _device
+    assert _device.producer_stream({"version": 2}) is None
+    assert _device.producer_stream({"version": 3, "stream": None}) is None
+    assert _device.producer_stream({"version": 3, "stream": 1}) == 1
+    assert _device.producer_stream({"version": 3, "stream": 2}) == 2
+    assert _device.producer_stream({"version": 3, "stream": 0x7f0012345600}) == 0x7f0012345600
+    with pytest.raises(ValueError, match="disallowed"):
+        _device.producer_stream({"version": 3, "stream": 0})
+    with pytest.raises(TypeError):
+        _device.producer_stream({"version": 3, "stream": "0x1"})

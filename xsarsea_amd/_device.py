@@ -2,7 +2,8 @@
 
 `invert_from_model`, `sigma0_detrend` and `nesz_flattening` accept rasters that already live in HBM -- torch CUDA(=HIP)
 tensors, or any object exposing `__cuda_array_interface__` -- and then return torch tensors on the same device: nothing
-crosses PCIe, the kernels run on torch's current stream (asynchronously, ordered with the caller's other work on it).
+crosses PCIe, the kernels run on torch's current stream (asynchronously, ordered with the caller's other work on it).  An
+interface object that names the stream its data is produced on (version 3 `stream`) is waited for on that stream first.
 PyTorch is plumbing here: it owns the device memory and the stream, the work is libxsw's.
 """
 import numpy as np
@@ -34,10 +35,39 @@ def as_tensor(a, device, dtype=None):
     if isinstance(a, torch.Tensor):
         t = a if a.device == device else a.to(device)
     elif hasattr(a, "__cuda_array_interface__"):
+        wait_for_producer(a.__cuda_array_interface__, device)
         t = torch.as_tensor(a, device=device)
     else:
         t = torch.as_tensor(np.asarray(a)).to(device)
     return t if dtype is None or t.dtype == dtype else t.to(dtype)
+
+
+def producer_stream(cai):
+    """The stream a `__cuda_array_interface__` (v3) says its data is being produced on, as a HIP stream handle, or None when
+    nothing needs to be waited for.  Per the interface: absent / None = no synchronisation, 1 = the legacy default stream,
+    2 = the per-thread default stream, 0 = disallowed (ambiguous), anything else = a stream handle."""
+    s = cai.get("stream")
+    if s is None:
+        return None
+    if isinstance(s, bool) or not isinstance(s, int):
+        raise TypeError(f"__cuda_array_interface__ stream must be an int or None, not {type(s).__name__}")
+    if s == 0:
+        raise ValueError("__cuda_array_interface__ stream 0 is disallowed (ambiguous between the legacy and the per-thread "
+                         "default stream)")
+    return s
+
+
+def wait_for_producer(cai, device):
+    """Orders torch's current stream of `device` (the one the kernels will run on) after the work queued so far on the stream
+    the array's producer advertises (device-side event wait; the host does not block)."""
+    s = producer_stream(cai)
+    if s is None:
+        return
+    import torch
+    src = torch.cuda.default_stream(device) if s == 1 else torch.cuda.ExternalStream(s, device=device)
+    cur = torch.cuda.current_stream(device)
+    if src.cuda_stream != cur.cuda_stream:
+        cur.wait_stream(src)
 
 
 def device_of(*arrays):

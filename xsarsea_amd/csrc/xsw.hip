@@ -351,6 +351,10 @@ static int install_co(xsw_ctx *c, const xsw_lut *l, const double *d_dense)
         !strictly_ascending(l->phi, l->n_phi))
         return fail(c, XSW_EINVAL, "co-pol LUT: axes must be strictly ascending");
     if ((int64_t)l->n_wspd * l->n_phi >= (int64_t)1 << 30) return fail(c, XSW_EINVAL, "co-pol LUT too large");
+    // a search queued on the context's stream (an asynchronous device-raster call, possibly on the caller's stream, or on the
+    // previous stream that this one waits for since xsw_set_stream) may still read the old tables: it must be through with
+    // them before they are freed -- stated here rather than left to whatever hipFree happens to wait for
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     free_all(c->co_allocs);
     c->have_co = false;
     DevTables &T = c->T;
@@ -384,11 +388,12 @@ static int install_co(xsw_ctx *c, const xsw_lut *l, const double *d_dense)
             e = hipGetLastError();
         }
         int *d_mono = nullptr;
+        std::vector<int> init((size_t)nI, nW);  // read by the copy below until the stream is synchronised at the end of this block
         if (e == hipSuccess) e = hipMalloc((void **)&d_mono, (size_t)nI * sizeof(int) + 64);
         if (e == hipSuccess) {
             c->co_allocs.push_back(d_mono);
-            std::vector<int> init((size_t)nI, nW);
-            e = hipMemcpy(d_mono, init.data(), (size_t)nI * sizeof(int), hipMemcpyHostToDevice);
+            // on the launch stream, in order with k_mono_rows (not a null-stream copy whose completion the kernel would rely on)
+            e = hipMemcpyAsync(d_mono, init.data(), (size_t)nI * sizeof(int), hipMemcpyHostToDevice, c->stream);
         }
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_mono_rows, dim3((unsigned)(((long long)nI * nP + 255) / 256)), dim3(256), 0, c->stream, d_dense, nI, nW, nP, d_mono);
@@ -591,6 +596,7 @@ static int upload_cr(xsw_ctx *c, const xsw_lut *l)
         return fail(c, XSW_EINVAL, "cross-pol LUT: null pointer or empty axis");
     if (!strictly_ascending(l->inc, l->n_inc) || !strictly_ascending(l->wspd, l->n_wspd))
         return fail(c, XSW_EINVAL, "cross-pol LUT: axes must be strictly ascending");
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // a queued search may still read the old tables (install_co)
     free_all(c->cr_allocs);
     c->have_cr = false;
     DevTables &T = c->T;
@@ -1184,7 +1190,7 @@ static int interp_device(xsw_ctx *c, const double *d_raw, const double *inc_raw,
         if (rc) return;
         if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess) { rc = fail(c, XSW_ENOMEM, "lut_interp: hipMalloc failed"); return; }
         tmp.push_back(p);
-        if (bytes && hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, XSW_EHIP, "lut_interp: H2D failed");
+        if (bytes && hipMemcpyAsync(p, h, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(c, XSW_EHIP, "lut_interp: H2D failed");
         *d = p;
     };
     a.raw = d_raw;
@@ -1209,6 +1215,9 @@ static int interp_device(xsw_ctx *c, const double *d_raw, const double *inc_raw,
         hipLaunchKernelGGL(k_lut_interp, dim3((unsigned)blocks), dim3(256), 0, c->stream, a);
         if (hipGetLastError() != hipSuccess) rc = fail(c, XSW_EHIP, "lut_interp: launch failed");
     }
+    // the copies above are queued on the launch stream, in order with k_lut_interp; loi / low / lop are locals of this function
+    hipError_t se = hipStreamSynchronize(c->stream);
+    if (!rc && se != hipSuccess) rc = fail(c, XSW_EHIP, "lut_interp: %s", hipGetErrorString(se));
     return rc;
 }
 
@@ -1271,7 +1280,8 @@ extern "C" int xsw_lut_build(xsw_ctx *c, int32_t gmf_id, const double *inc_raw, 
         if (rc) return nullptr;
         if (hipMalloc(&p, bytes + 8) != hipSuccess) { rc = fail(c, XSW_ENOMEM, "lut_build: hipMalloc(%zu) failed", bytes); return nullptr; }
         tmp.push_back(p);
-        if (h && hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, XSW_EHIP, "lut_build: H2D failed");
+        // on the launch stream, in order with the kernels that read it (the stream is synchronised before this function returns)
+        if (h && hipMemcpyAsync(p, h, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(c, XSW_EHIP, "lut_build: H2D failed");
         return p;
     };
     const double *d_i = (const double *)dev(inc_raw, (size_t)n_inc_raw * 8), *d_w = (const double *)dev(wspd_raw, (size_t)n_wspd_raw * 8);

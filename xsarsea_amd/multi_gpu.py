@@ -373,8 +373,9 @@ def invert_from_model_tiled(inc, sigma0, sigma0_dual=None, /, *, dst=0, group=No
             return False
         if torch.is_tensor(a):  # device-resident ancillary wind: decided where it lives (NaN if either part is, as numpy's isnan)
             return bool(a.numel()) and bool((~torch.isnan(a)).any().item())
-        if hasattr(a, "__cuda_array_interface__"):
-            return has_valid(torch.as_tensor(a, device="cuda"))
+        if hasattr(a, "__cuda_array_interface__"):  # (after the stream it says it is produced on, if it names one)
+            from . import _device
+            return has_valid(_device.as_tensor(a, _device.device_of(a)))
         return bool(np.size(a)) and bool(np.any(~np.isnan(np.asarray(a))))
 
     # step 1: cut the tile, look at its ancillary wind
