@@ -311,6 +311,48 @@ int xsw_detrend(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int
 int xsw_nesz_flatten(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, const void *noise,
                      const void *inc, double *out);
 
+/* ---- wind-streak direction histograms (Koch 2004; reference: gradients.py).  Additive to XSW_VERSION 4.  Raster pointers are
+ * host or device per `mem` (XSW_MEM_HOST / XSW_MEM_DEVICE); device calls are asynchronous on the context's stream, host calls
+ * return with the outputs filled.  Sums are float64 in a fixed order: results are bit-identical from run to run. */
+
+/* Replaces Gradients._sigma0_resample (gradients.py:343-367, cv2.resize INTER_AREA at an integer factor):
+ * out[Y][X] = (sum of in[f*Y + i][f*X + j], i, j < f) * (1 / f^2), float64 sums rounded to `dtype` (the output has the input's
+ * dtype, as cv2's); NaN propagates.  out is (lines / f) x (samples / f) (floor: the remainder is trimmed). */
+int xsw_grad_area(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t factor, int32_t dtype, int32_t mem, const void *in,
+                  void *out);
+
+/* Replaces R2 (gradients.py:689-722) and, with take_sqrt != 0, Gradients2D.ampl = sqrt(R2(sigma0)) (:126-134):
+ * scipy convolve2d(B4 = B2*B2, 5x5, boundary="symm"), xarray coarsen(2 x 2, boundary="trim").mean() (NaN-skipping: a block
+ * with some NaN is the mean of the others, an all-NaN block is NaN), convolve2d(B2, 3x3, "symm") -- each reflection at that
+ * stage's own array edge.  The divisions by convolve2d(ones) are divisions by 1.0 and are not performed.  `in` is a float32 or
+ * float64 raster (converted to float64 as scipy does), out is float64 (lines / 2) x (samples / 2). */
+int xsw_grad_r2(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, int32_t take_sqrt, const void *in,
+                double *out);
+
+/* Replaces local_gradients (gradients.py:588-634) on the float64 amplitude raster `ampl` (lines x samples):
+ * grad = Scharr_x + 1j * Scharr_y (cv2.Scharr, CV_64F, BORDER_REFLECT_101; dx along sample, dy along line), squared;
+ * g2 (complex128) = sqrt(R2(grad**2)) (principal root), g3 = R2(|grad**2|), quality = |R2(grad**2)| / (g3 + 1e-5), set to 0
+ * where above 1 or NaN.  Outputs are (lines / 2) x (samples / 2). */
+int xsw_grad_local(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, const double *ampl, double *g2, double *g3,
+                   double *quality);
+
+/* Replaces Gradients2D.histogram over its windows (gradients.py:87-121 with gradient_histogram :828-879): for every window
+ * centre (rows[a], cols[b]) on the g2 / quality grid (lines x samples), the window of xarray's rolling(center=True) -- rows
+ * rows[a] - window_lines/2 .. rows[a] - window_lines/2 + window_lines - 1, columns likewise with window_samples, pixels outside
+ * the raster are NaN -- is reduced to
+ *   kept      = pixels whose |g2| is not NaN and > 0,  m = median(|g2| over kept) (numpy: mean of the middle two for an even count)
+ *   weight[a][b][k] = sum over kept of |g2| / (|g2| + m) * quality, k = rint((angle(g2) - angle_start) / angle_step) (round half
+ *                     to even), divided by window_lines * window_samples when normalise != 0 (:118-120);  k = n_angles
+ *                     (angle = +pi/2) is folded onto bin 0 (the reference raises IndexError there), k = -n_angles .. -1
+ *                     are numpy's negative indices; a pixel with any other k (possible only for a g2 that is not a principal
+ *                     square root; the reference raises IndexError) is skipped: nothing outside weight[a][b] is written
+ *   used_ratio[a][b] = count(kept) / (window_lines * window_samples).
+ * One workgroup per window; the median is exact (radix select on the float64 bit patterns, integer counters only).
+ * rows (n_rows) and cols (n_cols) are int32 indices; weight is [n_rows][n_cols][n_angles], used_ratio [n_rows][n_cols] (float64). */
+int xsw_grad_hist(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, const double *g2, const double *quality,
+                  int32_t window_lines, int32_t window_samples, int32_t n_rows, const int32_t *rows, int32_t n_cols, const int32_t *cols, int32_t n_angles, double angle_start,
+                  double angle_step, int32_t normalise, double *weight, double *used_ratio);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,7 @@ EXPORTS = (
     "xsw_version", "xsw_device_count", "xsw_ctx_create", "xsw_ctx_destroy", "xsw_last_error", "xsw_set_stream", "xsw_use_own_stream",
     "xsw_synchronize", "xsw_lut_upload", "xsw_invert", "xsw_stats_enable", "xsw_stats_read", "xsw_stats_read_chain", "xsw_detrend", "xsw_lut_interp", "xsw_gmf_eval",
     "xsw_nesz_flatten", "xsw_lut_build", "xsw_lut_read", "xsw_timing_enable", "xsw_timing_read", "xsw_expand_codes", "xsw_expand_codes_on_stream",
-    "xsw_host_alloc", "xsw_host_free", "xsw_set_host_threads",
+    "xsw_host_alloc", "xsw_host_free", "xsw_set_host_threads", "xsw_grad_area", "xsw_grad_r2", "xsw_grad_local", "xsw_grad_hist",
 )
 
 
@@ -141,6 +141,12 @@ def load():
         lib.xsw_host_alloc.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
         lib.xsw_host_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         lib.xsw_set_host_threads.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        lib.xsw_grad_area.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 2
+        lib.xsw_grad_r2.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 2
+        lib.xsw_grad_local.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 4
+        lib.xsw_grad_hist.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                      ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
         if lib.xsw_version() != ABI_VERSION:
             raise XswError(f"{_build.LIB} is version {lib.xsw_version()}, this package binds version {ABI_VERSION}: rebuild it")
         _cdll = lib
@@ -507,6 +513,35 @@ class Context:
             self.nesz_flatten_raw(noise.shape[0], noise.shape[1], XSW_F32 if noise.dtype == np.float32 else XSW_F64, MEM_HOST,
                                   noise.ctypes.data, inc.ctypes.data, out.ctypes.data)
         return out
+
+    # ---- wind-streak direction histograms (xsarsea_amd.gradients).  Pointers are ints (device or host addresses per `mem`).
+    @_locked
+    def grad_area_raw(self, lines, samples, factor, dtype, mem, in_ptr, out_ptr):
+        """Thin call of xsw_grad_area: f x f box mean, output of the input's dtype."""
+        self._check(self._lib.xsw_grad_area(self._h, int(lines), int(samples), int(factor), dtype, mem, ctypes.c_void_p(in_ptr),
+                                            ctypes.c_void_p(out_ptr)), "xsw_grad_area")
+
+    @_locked
+    def grad_r2_raw(self, lines, samples, dtype, mem, take_sqrt, in_ptr, out_ptr):
+        """Thin call of xsw_grad_r2: R2 (or sqrt(R2) with take_sqrt) -> float64 (lines // 2, samples // 2)."""
+        self._check(self._lib.xsw_grad_r2(self._h, int(lines), int(samples), dtype, mem, int(bool(take_sqrt)), ctypes.c_void_p(in_ptr),
+                                          ctypes.c_void_p(out_ptr)), "xsw_grad_r2")
+
+    @_locked
+    def grad_local_raw(self, lines, samples, mem, ampl_ptr, g2_ptr, g3_ptr, c_ptr):
+        """Thin call of xsw_grad_local: float64 ampl -> G2 (complex128), G3, c on the (lines // 2, samples // 2) grid."""
+        self._check(self._lib.xsw_grad_local(self._h, int(lines), int(samples), mem, ctypes.c_void_p(ampl_ptr), ctypes.c_void_p(g2_ptr),
+                                             ctypes.c_void_p(g3_ptr), ctypes.c_void_p(c_ptr)), "xsw_grad_local")
+
+    @_locked
+    def grad_hist_raw(self, lines, samples, mem, g2_ptr, c_ptr, window_lines, window_samples, n_rows, rows_ptr, n_cols, cols_ptr,
+                      n_angles, angle_start, angle_step, normalise, weight_ptr, ratio_ptr):
+        """Thin call of xsw_grad_hist: per-window bin sums (divided by the window's pixel count with `normalise`) and used ratios
+        (rows / cols: int32 window-centre indices)."""
+        self._check(self._lib.xsw_grad_hist(self._h, int(lines), int(samples), mem, ctypes.c_void_p(g2_ptr), ctypes.c_void_p(c_ptr),
+                                            int(window_lines), int(window_samples), int(n_rows), ctypes.c_void_p(rows_ptr), int(n_cols), ctypes.c_void_p(cols_ptr),
+                                            int(n_angles), float(angle_start), float(angle_step), int(bool(normalise)), ctypes.c_void_p(weight_ptr),
+                                            ctypes.c_void_p(ratio_ptr)), "xsw_grad_hist")
 
     @_locked
     def detrend_raw(self, lines, samples, dtype, out_dtype, mem, sigma0_ptr, ratio_row, out_ptr):

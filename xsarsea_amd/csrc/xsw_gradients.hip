@@ -1,0 +1,532 @@
+// Wind-streak direction histograms (Koch 2004; reference: src/xsarsea/gradients.py): the kernels behind
+// xsarsea_amd.gradients and their C ABI (xsw_grad_area / xsw_grad_r2 / xsw_grad_local / xsw_grad_hist, include/xsw.h).
+//
+//   k_grad_area   f x f box mean (cv2.resize INTER_AREA at an integer factor, Gradients._sigma0_resample :343-367)
+//   k_grad_r2     R2 (:689-722): 5x5 B4 "symm" convolution, 2x2 NaN-skipping mean, 3x3 B2 "symm" convolution, optional sqrt;
+//                 one 16 x 16 tile of the coarse output per workgroup, the fine input with its halo in LDS
+//   k_grad_local  local_gradients (:588-634): Scharr (BORDER_REFLECT_101), grad**2, then R2 of (re, im, |grad**2|) in the
+//                 same tiling; writes G2 = sqrt(R2(grad**2)), G3 = R2(|grad**2|) and the quality c
+//   k_grad_hist   gradient_histogram (:828-879) of one window per workgroup: exact median of |G2| by radix select on the
+//                 float64 bit patterns (integer LDS atomics on counters), then the bin sums in a fixed order (deterministic)
+//
+// Every stage reflects at its OWN array's edge, as the reference's chain of separate scipy / xarray calls does.  Sums are
+// float64 in a fixed order; -ffp-contract=off (xsarsea_amd/_build.py) keeps them free of contractions.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+
+#include "xsw_host.hpp"
+
+namespace {
+
+constexpr int TILE = 16;               // coarse outputs per tile side (k_grad_r2, k_grad_local)
+constexpr int FR = 2 * TILE + 8;       // fine rows / columns of a tile: coarse halo +-1, then the 5x5 reach +-2
+constexpr int FRP = FR + 1;
+constexpr int CH = TILE + 2;           // coarse halo side
+constexpr int CHP = CH + 1;
+constexpr int AR = FR + 2;             // ampl rows / columns of a k_grad_local tile (the Scharr reach +-1)
+constexpr int ARP = AR + 1;
+constexpr int HIST_THREADS = 512;
+constexpr int HIST_WAVES = HIST_THREADS / 64;
+constexpr int HIST_CHUNK = 72;         // bins accumulated per sweep (registers per thread)
+constexpr int RADIX_BITS = 11;
+constexpr int RADIX = 1 << RADIX_BITS;
+
+// scipy.signal.convolve2d(boundary="symm"): d c b a | a b c d | d c b a  (any overshoot: period 2n)
+__host__ __device__ inline long long refl_symm(long long i, long long n)
+{
+    if (i >= 0 && i < n) return i;  // the common case: no 64-bit remainder
+    const long long p = 2 * n;
+    i %= p;
+    if (i < 0) i += p;
+    return i < n ? i : p - 1 - i;
+}
+
+// cv2 BORDER_REFLECT_101: d c b | a b c d | c b a  (period 2n - 2)
+__host__ __device__ inline long long refl_101(long long i, long long n)
+{
+    if (i >= 0 && i < n) return i;
+    if (n == 1) return 0;
+    const long long p = 2 * n - 2;
+    i %= p;
+    if (i < 0) i += p;
+    return i < n ? i : p - i;
+}
+
+__device__ inline int clampi(long long v, int lo, int hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
+
+// B4 = B2 * B2 = outer([1,4,6,4,1], [1,4,6,4,1]) / 256 and B2 = outer([1,2,1], [1,2,1]) / 16: dyadic, exact in float64
+__device__ inline double b4(int i, int j)
+{
+    const double w[5] = {1.0, 4.0, 6.0, 4.0, 1.0};
+    return w[i] * w[j] * (1.0 / 256.0);
+}
+__device__ inline double b2(int i, int j)
+{
+    const double w[3] = {1.0, 2.0, 1.0};
+    return w[i] * w[j] * (1.0 / 16.0);
+}
+
+// 5x5 B4 at the fine pixel whose window starts at F[y][x]
+__device__ inline double conv5(const double (*F)[FRP], int y, int x)
+{
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+#pragma unroll
+        for (int j = 0; j < 5; ++j) s += b4(i, j) * F[y + i][x + j];
+    return s;
+}
+
+__device__ inline double conv3(const double (*C)[CHP], int y, int x)
+{
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) s += b2(i, j) * C[y + i][x + j];
+    return s;
+}
+
+// coarse halo cell (cy, cx) of the tile at (Y0, X0) holds the coarse pixel symm(Y0 - 1 + cy, L2): its local row in the tile
+// (clamped for the cells past a partial tile, whose values are never used)
+__device__ inline int halo_src(int c, long long org, long long n) { return clampi(refl_symm(org - 1 + c, n) - (org - 1), 0, CH - 1); }
+
+// ---------------------------------------------------------------------------------------------------------- k_grad_area
+template <typename T>
+__global__ void k_grad_area(const T *__restrict__ in, T *__restrict__ out, long long S, int f, long long Lo, long long So)
+{
+    const long long n = Lo * So;
+    const double scale = 1.0 / ((double)f * f);
+    for (long long o = blockIdx.x * (long long)blockDim.x + threadIdx.x; o < n; o += (long long)gridDim.x * blockDim.x) {
+        const long long Y = o / So, X = o - Y * So;
+        const T *p = in + Y * f * S + X * f;
+        double s = 0.0;
+        for (int i = 0; i < f; ++i)
+            for (int j = 0; j < f; ++j) s += (double)p[i * S + j];
+        out[o] = (T)(s * scale);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ k_grad_r2
+template <typename T>
+__global__ __launch_bounds__(256) void k_grad_r2(const T *__restrict__ in, double *__restrict__ out, int L1, int S1, int L2, int S2,
+                                                 int take_sqrt)
+{
+    __shared__ double F[FR][FRP];
+    __shared__ double C[CH][CHP];
+    const int Y0 = blockIdx.y * TILE, X0 = blockIdx.x * TILE, tid = threadIdx.x;
+    const long long fy0 = 2LL * Y0 - 4, fx0 = 2LL * X0 - 4;
+    for (int k = tid; k < FR * FR; k += 256) {
+        const int ly = k / FR, lx = k - ly * FR;
+        F[ly][lx] = (double)in[refl_symm(fy0 + ly, L1) * S1 + refl_symm(fx0 + lx, S1)];
+    }
+    __syncthreads();
+    for (int k = tid; k < CH * CH; k += 256) {
+        const int cy = k / CH, cx = k - cy * CH;
+        const int sy = 2 * halo_src(cy, Y0, L2), sx = 2 * halo_src(cx, X0, S2);
+        const double v00 = conv5(F, sy, sx), v01 = conv5(F, sy, sx + 1), v10 = conv5(F, sy + 1, sx), v11 = conv5(F, sy + 1, sx + 1);
+        // xarray coarsen(...).mean() skips NaN (nanmean): sum of the finite ones / their count; all NaN -> NaN
+        int cnt = 0;
+        double s = 0.0;
+        if (!isnan(v00)) { s += v00; ++cnt; }
+        if (!isnan(v01)) { s += v01; ++cnt; }
+        if (!isnan(v10)) { s += v10; ++cnt; }
+        if (!isnan(v11)) { s += v11; ++cnt; }
+        C[cy][cx] = cnt ? s / (double)cnt : __builtin_nan("");
+    }
+    __syncthreads();
+    const int ty = tid / TILE, tx = tid - ty * TILE, Y = Y0 + ty, X = X0 + tx;
+    if (Y < L2 && X < S2) {
+        const double v = conv3(C, ty, tx);
+        out[(long long)Y * S2 + X] = take_sqrt ? sqrt(v) : v;
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------- k_grad_local
+// principal square root, the formula of C99 csqrt (numpy's np.sqrt on complex128)
+__device__ inline double2 csqrt_principal(double x, double y)
+{
+    if (isnan(x) || isnan(y)) return make_double2(__builtin_nan(""), __builtin_nan(""));
+    if (x == 0.0 && y == 0.0) return make_double2(0.0, y);
+    const double d = hypot(x, y);
+    if (x >= 0.0) {
+        const double r = sqrt(0.5 * (d + x));
+        return make_double2(r, 0.5 * (y / r));
+    }
+    const double s = sqrt(0.5 * (d - x));
+    return make_double2(fabs(0.5 * (y / s)), copysign(s, y));
+}
+
+__global__ __launch_bounds__(256) void k_grad_local(const double *__restrict__ ampl, double2 *__restrict__ g2, double *__restrict__ g3,
+                                                    double *__restrict__ cq, int L1, int S1, int L2, int S2)
+{
+    // A (ampl with its Scharr halo) is dead once grad**2 is formed: the coarse halo planes reuse its storage
+    constexpr int A_DOUBLES = AR * ARP, C_DOUBLES = 3 * CH * CHP;
+    static_assert(C_DOUBLES <= A_DOUBLES, "coarse planes must fit in the ampl tile");
+    __shared__ double U[A_DOUBLES];
+    __shared__ double G[3][FR][FRP];
+    double (*A)[ARP] = (double (*)[ARP])U;
+    double (*Cr)[CHP] = (double (*)[CHP])U;
+    double (*Ci)[CHP] = (double (*)[CHP])(U + CH * CHP);
+    double (*Ca)[CHP] = (double (*)[CHP])(U + 2 * CH * CHP);
+    const int Y0 = blockIdx.y * TILE, X0 = blockIdx.x * TILE, tid = threadIdx.x;
+    const long long ay0 = 2LL * Y0 - 5, ax0 = 2LL * X0 - 5;
+    for (int k = tid; k < AR * AR; k += 256) {
+        const int ly = k / AR, lx = k - ly * AR;
+        A[ly][lx] = ampl[refl_101(ay0 + ly, L1) * S1 + refl_101(ax0 + lx, S1)];
+    }
+    __syncthreads();
+    // grad**2 at the fine pixel symm(2*Y0 - 4 + ly, L1): A holds ampl at reflect101(q) for the raw rows q = r - 1 .. r + 1
+    for (int k = tid; k < FR * FR; k += 256) {
+        const int ly = k / FR, lx = k - ly * FR;
+        const int r = clampi(refl_symm(2LL * Y0 - 4 + ly, L1) - ay0, 1, AR - 2);
+        const int q = clampi(refl_symm(2LL * X0 - 4 + lx, S1) - ax0, 1, AR - 2);
+        // cv2.Scharr(CV_64F) as the separable row-then-column filter; every tap multiplies (NaN covers the 3x3 footprint)
+        double hx[3], hy[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const double *row = &A[r - 1 + d][q - 1];
+            hx[d] = -1.0 * row[0] + 0.0 * row[1] + 1.0 * row[2];
+            hy[d] = 3.0 * row[0] + 10.0 * row[1] + 3.0 * row[2];
+        }
+        double dx = 3.0 * hx[0] + 10.0 * hx[1] + 3.0 * hx[2];
+        double dy = -1.0 * hy[0] + 0.0 * hy[1] + 1.0 * hy[2];
+        if (isnan(dx) || isnan(dy)) dx = dy = __builtin_nan("");  // grad = dx + 1j*dy: one NaN part makes both NaN
+        const double re = dx * dx - dy * dy, im = dx * dy + dy * dx;
+        G[0][ly][lx] = re;
+        G[1][ly][lx] = im;
+        G[2][ly][lx] = hypot(re, im);
+    }
+    __syncthreads();
+    for (int k = tid; k < CH * CH; k += 256) {
+        const int cy = k / CH, cx = k - cy * CH;
+        const int sy = 2 * halo_src(cy, Y0, L2), sx = 2 * halo_src(cx, X0, S2);
+        double vr[4], vi[4], va[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            vr[a] = conv5(G[0], sy + (a >> 1), sx + (a & 1));
+            vi[a] = conv5(G[1], sy + (a >> 1), sx + (a & 1));
+            va[a] = conv5(G[2], sy + (a >> 1), sx + (a & 1));
+        }
+        // nanmean: complex values are skipped when either part is NaN
+        int nc = 0, na = 0;
+        double sr = 0.0, si = 0.0, sa = 0.0;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            if (!isnan(vr[a]) && !isnan(vi[a])) { sr += vr[a]; si += vi[a]; ++nc; }
+            if (!isnan(va[a])) { sa += va[a]; ++na; }
+        }
+        Cr[cy][cx] = nc ? sr / (double)nc : __builtin_nan("");
+        Ci[cy][cx] = nc ? si / (double)nc : __builtin_nan("");
+        Ca[cy][cx] = na ? sa / (double)na : __builtin_nan("");
+    }
+    __syncthreads();
+    const int ty = tid / TILE, tx = tid - ty * TILE, Y = Y0 + ty, X = X0 + tx;
+    if (Y < L2 && X < S2) {
+        const double zr = conv3(Cr, ty, tx), zi = conv3(Ci, ty, tx), za = conv3(Ca, ty, tx);
+        const long long o = (long long)Y * S2 + X;
+        g2[o] = csqrt_principal(zr, zi);
+        g3[o] = za;
+        const double c = hypot(zr, zi) / (za + 0.00001);
+        cq[o] = c <= 1.0 ? c : 0.0;  // c.where(c <= 1).fillna(0): above 1 or NaN -> 0
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------- k_grad_hist
+struct HistWin {
+    long long r0, c0;  // first raster row / column of the window inside the raster
+    int nr, nc;        // window rows / columns inside the raster (the rest is NaN padding: never kept)
+};
+
+__device__ inline bool kept(const double2 *g2, const HistWin &h, long long S, int p, double &a)
+{
+    const int i = p / h.nc, j = p - i * h.nc;
+    const double2 z = g2[(h.r0 + i) * S + h.c0 + j];
+    a = hypot(z.x, z.y);
+    return !isnan(a) && a > 0.0;
+}
+
+__device__ inline unsigned long long bits_of(double a)
+{
+    return (unsigned long long)__double_as_longlong(a);
+}
+
+// One window per workgroup.  Rows / columns outside the raster are the NaN padding of xarray's rolling(center=True): they
+// count in the window's size (wl*ws) and are never kept, so only the clipped rectangle is read.  weight receives the bin sums
+// (gradient_histogram's `grads`), divided by the window's pixel count when `normalise` (Gradients2D.histogram :118-120).
+__global__ __launch_bounds__(HIST_THREADS) void k_grad_hist(const double2 *__restrict__ g2, const double *__restrict__ cq, int L, int S,
+                                                            int wl, int ws, const int *__restrict__ rows, int n_rows, const int *__restrict__ cols,
+                                                            int n_cols, int n_angles, double start, double step, int normalise,
+                                                            double *__restrict__ weight, double *__restrict__ used_ratio)
+{
+    __shared__ unsigned hist[2][RADIX];
+    __shared__ unsigned long long s_prefix[2];
+    __shared__ long long s_rank[2];
+    __shared__ long long s_n;
+    __shared__ double s_wave[HIST_WAVES][HIST_CHUNK];
+    const int win = blockIdx.x, wr = win / n_cols, wc = win - wr * n_cols, tid = threadIdx.x;
+    HistWin h;
+    {
+        const long long r0 = (long long)rows[wr] - wl / 2, c0 = (long long)cols[wc] - ws / 2;
+        const long long ra = r0 < 0 ? 0 : r0, rb = r0 + wl > L ? L : r0 + wl;
+        const long long ca = c0 < 0 ? 0 : c0, cb = c0 + ws > S ? S : c0 + ws;
+        h.r0 = ra;
+        h.c0 = ca;
+        h.nr = rb > ra ? (int)(rb - ra) : 0;
+        h.nc = cb > ca ? (int)(cb - ca) : 0;
+    }
+    const int np = h.nr * h.nc;  // < 2^31: the window side is bounded by the raster's (checked on the host)
+    const double wpix = (double)wl * (double)ws;
+
+    // ---- exact median of the kept |G2|: radix select of ranks (n-1)/2 and n/2 over the bit patterns (non-negative doubles
+    // order as their bits), 11-bit digits from the top
+    if (tid == 0) { s_prefix[0] = s_prefix[1] = 0; s_rank[0] = s_rank[1] = -1; s_n = 0; }
+    for (int shift = 64 - RADIX_BITS, pass = 0; shift > -RADIX_BITS; shift -= RADIX_BITS, ++pass) {
+        const int sh = shift < 0 ? 0 : shift;
+        const int width = shift < 0 ? RADIX_BITS + shift : RADIX_BITS;
+        const unsigned dmask = (1u << width) - 1;
+        for (int k = tid; k < 2 * RADIX; k += HIST_THREADS) (&hist[0][0])[k] = 0;
+        __syncthreads();
+        const unsigned long long pmask = (shift + RADIX_BITS >= 64) ? 0ull : ~0ull << (sh + width);
+        const unsigned long long p0 = s_prefix[0], p1 = s_prefix[1];
+        const bool same = p0 == p1;
+        for (int p = tid; p < np; p += HIST_THREADS) {
+            double a;
+            if (!kept(g2, h, S, p, a)) continue;
+            const unsigned long long key = bits_of(a);
+            const unsigned d = (unsigned)(key >> sh) & dmask;
+            if ((key & pmask) == p0) atomicAdd(&hist[0][d], 1u);
+            if (!same && (key & pmask) == p1) atomicAdd(&hist[1][d], 1u);
+        }
+        __syncthreads();
+        if (tid < 128) {  // wave 0 resolves rank (n-1)/2, wave 1 rank n/2: a wave-wide scan of 32 counters per lane
+            const int sel = tid >> 6, lane = tid & 63;
+            const unsigned *hh = hist[same ? 0 : sel];
+            long long mine = 0;
+            for (int k = 0; k < RADIX / 64; ++k) mine += hh[lane * (RADIX / 64) + k];
+            long long incl = mine;
+            for (int off = 1; off < 64; off <<= 1) {
+                const long long o = __shfl_up(incl, off, 64);
+                if (lane >= off) incl += o;
+            }
+            long long rank;
+            if (pass == 0) {
+                const long long n = __shfl(incl, 63, 64);
+                rank = sel == 0 ? (n - 1) / 2 : n / 2;
+                if (lane == 0 && sel == 0) s_n = n;
+            } else {
+                rank = s_rank[sel];
+            }
+            const long long excl = incl - mine;
+            const bool here = rank >= excl && rank < incl;
+            const unsigned long long ball = __ballot(here);
+            if (ball && lane == __ffsll((long long)ball) - 1) {
+                long long r = rank - excl;
+                int d = lane * (RADIX / 64);
+                while (r >= (long long)hh[d]) r -= hh[d++];
+                s_rank[sel] = r;
+                s_prefix[sel] |= (unsigned long long)d << sh;
+            }
+        }
+        __syncthreads();
+        if (s_n == 0) break;  // nothing kept: the bin sums are all zero
+    }
+    const long long n = s_n;
+    double m = 0.0;
+    if (n > 0) {
+        const double lo = __longlong_as_double((long long)s_prefix[0]), hi = __longlong_as_double((long long)s_prefix[1]);
+        m = (n & 1) ? lo : (lo + hi) / 2.0;  // numpy's median of an even count: the mean of the two middle values
+    }
+
+    // ---- bin sums: every kept pixel adds |g2| / (|g2| + m) * c into bin rint((angle - start) / step) (round half to even,
+    // numpy's round); bin n_angles (angle = +pi/2) folds onto bin 0, bins -n_angles .. -1 are numpy's negative indices, and a
+    // pixel whose bin lies outside -n_angles .. n_angles (a non-principal g2 only) is skipped, never written.  Each
+    // thread sums its own pixels in order, the waves reduce by a fixed butterfly, then the 8 wave sums add in wave order:
+    // the result does not depend on scheduling.
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int b0 = 0; b0 < n_angles; b0 += HIST_CHUNK) {
+        double acc[HIST_CHUNK];
+#pragma unroll
+        for (int b = 0; b < HIST_CHUNK; ++b) acc[b] = 0.0;
+        if (n > 0) {
+            for (int p = tid; p < np; p += HIST_THREADS) {
+                double a;
+                if (!kept(g2, h, S, p, a)) continue;
+                const int i = p / h.nc, j = p - i * h.nc;
+                const long long o = (h.r0 + i) * S + h.c0 + j;
+                const double2 z = g2[o];
+                const double v = a / (a + m) * cq[o];
+                if (isnan(v)) continue;
+                long long k = (long long)rint((atan2(z.y, z.x) - start) / step);
+                if (k == n_angles) k = 0;        // angle +pi/2 == -pi/2 (mod pi): the one deliberate deviation
+                else if (k < 0) k += n_angles;   // numpy's negative index, -n_angles .. -1
+                if (k < 0 || k >= n_angles) continue;  // outside numpy's range: the reference raises IndexError (only a
+                                                       // non-principal g2 gets here; gradient_histogram checks on the host)
+                const int kb = (int)k - b0;
+#pragma unroll
+                for (int b = 0; b < HIST_CHUNK; ++b) acc[b] += kb == b ? v : 0.0;
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < HIST_CHUNK; ++b) {
+            double s = acc[b];
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+            if (lane == 0) s_wave[wave][b] = s;
+        }
+        __syncthreads();
+        if (tid < HIST_CHUNK && b0 + tid < n_angles) {
+            double s = 0.0;
+            for (int v = 0; v < HIST_WAVES; ++v) s += s_wave[v][tid];
+            weight[(long long)win * n_angles + b0 + tid] = normalise ? s / wpix : s;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) used_ratio[win] = (double)n / wpix;
+}
+
+// ------------------------------------------------------------------------------------------------------------ host side
+static int gfail(xsw_ctx *c, int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    c->err = buf;
+    return code;
+}
+
+// Host buffers of one call: uploaded to temporaries, the launch runs on the context's stream, outputs come back, all before
+// the call returns.  Device buffers: the launch alone, asynchronous on the context's stream.
+struct Buf {
+    const void *host_in;  // input: host pointer to upload (nullptr for outputs)
+    void *host_out;       // output: host pointer to fill (nullptr for inputs)
+    size_t bytes;
+    void *dev = nullptr;
+};
+
+template <size_t N, typename Launch>
+static int run(xsw_ctx *c, int32_t mem, Buf (&b)[N], Launch &&launch, const char *what)
+{
+    if (hipSetDevice(c->device) != hipSuccess) return gfail(c, XSW_EHIP, "%s: hipSetDevice failed", what);
+    if (mem == XSW_MEM_DEVICE) {
+        for (auto &x : b) x.dev = x.host_out ? x.host_out : (void *)x.host_in;
+        launch(b);
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? XSW_OK : gfail(c, XSW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
+    }
+    int rc = XSW_OK;
+    hipError_t e = hipSuccess;
+    for (auto &x : b)
+        if (e == hipSuccess && x.bytes) e = hipMalloc(&x.dev, x.bytes);
+    if (e != hipSuccess) rc = gfail(c, XSW_ENOMEM, "%s: hipMalloc failed (%s)", what, hipGetErrorString(e));
+    for (auto &x : b)
+        if (!rc && x.host_in && x.bytes && (e = hipMemcpyAsync(x.dev, x.host_in, x.bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
+            rc = gfail(c, XSW_EHIP, "%s: upload failed (%s)", what, hipGetErrorString(e));
+    if (!rc) {
+        launch(b);
+        if ((e = hipGetLastError()) != hipSuccess) rc = gfail(c, XSW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
+    }
+    for (auto &x : b)
+        if (!rc && x.host_out && x.bytes && (e = hipMemcpyAsync(x.host_out, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
+            rc = gfail(c, XSW_EHIP, "%s: download failed (%s)", what, hipGetErrorString(e));
+    e = hipStreamSynchronize(c->stream);  // also before freeing after a failure: queued work may still use the temporaries
+    if (!rc && e != hipSuccess) rc = gfail(c, XSW_EHIP, "%s: %s", what, hipGetErrorString(e));
+    for (auto &x : b)
+        if (x.dev) (void)hipFree(x.dev);
+    return rc;
+}
+
+static bool bad_mem(int32_t mem) { return mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE; }
+
+}  // namespace
+
+extern "C" int xsw_grad_area(xsw_ctx *c, int64_t lines, int64_t samples, int32_t factor, int32_t dtype, int32_t mem, const void *in,
+                             void *out)
+{
+    if (!c) return XSW_EINVAL;
+    if (!in || !out || factor < 1 || lines < factor || samples < factor) return gfail(c, XSW_EINVAL, "grad_area: bad argument");
+    if (dtype != XSW_F32 && dtype != XSW_F64) return gfail(c, XSW_EINVAL, "dtype must be XSW_F32 or XSW_F64");
+    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    const long long Lo = lines / factor, So = samples / factor, es = dtype == XSW_F32 ? 4 : 8;
+    Buf b[2] = {{in, nullptr, (size_t)(lines * samples * es)}, {nullptr, out, (size_t)(Lo * So * es)}};
+    const long long nblk = std::min<long long>((Lo * So + 255) / 256, 65536);
+    return run(c, mem, b, [&](Buf (&x)[2]) {
+        if (dtype == XSW_F32)
+            hipLaunchKernelGGL(k_grad_area<float>, dim3((unsigned)nblk), dim3(256), 0, c->stream, (const float *)x[0].dev, (float *)x[1].dev,
+                               (long long)samples, (int)factor, Lo, So);
+        else
+            hipLaunchKernelGGL(k_grad_area<double>, dim3((unsigned)nblk), dim3(256), 0, c->stream, (const double *)x[0].dev, (double *)x[1].dev,
+                               (long long)samples, (int)factor, Lo, So);
+    }, "grad_area");
+}
+
+extern "C" int xsw_grad_r2(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, int32_t take_sqrt, const void *in,
+                           double *out)
+{
+    if (!c) return XSW_EINVAL;
+    if (!in || !out || lines < 2 || samples < 2) return gfail(c, XSW_EINVAL, "grad_r2: bad argument (the raster needs 2 x 2 pixels)");
+    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_r2: raster too large");
+    if (dtype != XSW_F32 && dtype != XSW_F64) return gfail(c, XSW_EINVAL, "dtype must be XSW_F32 or XSW_F64");
+    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    const int L1 = (int)lines, S1 = (int)samples, L2 = L1 / 2, S2 = S1 / 2;
+    const long long es = dtype == XSW_F32 ? 4 : 8;
+    Buf b[2] = {{in, nullptr, (size_t)(lines * samples * es)}, {nullptr, out, (size_t)L2 * S2 * 8}};
+    const dim3 grid((S2 + TILE - 1) / TILE, (L2 + TILE - 1) / TILE);
+    if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_r2: raster too large for one launch");
+    return run(c, mem, b, [&](Buf (&x)[2]) {
+        if (dtype == XSW_F32)
+            hipLaunchKernelGGL(k_grad_r2<float>, grid, dim3(256), 0, c->stream, (const float *)x[0].dev, (double *)x[1].dev, L1, S1, L2, S2,
+                               (int)(take_sqrt != 0));
+        else
+            hipLaunchKernelGGL(k_grad_r2<double>, grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double *)x[1].dev, L1, S1, L2,
+                               S2, (int)(take_sqrt != 0));
+    }, "grad_r2");
+}
+
+extern "C" int xsw_grad_local(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, const double *ampl, double *g2, double *g3,
+                              double *quality)
+{
+    if (!c) return XSW_EINVAL;
+    if (!ampl || !g2 || !g3 || !quality || lines < 2 || samples < 2)
+        return gfail(c, XSW_EINVAL, "grad_local: bad argument (the raster needs 2 x 2 pixels)");
+    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_local: raster too large");
+    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    const int L1 = (int)lines, S1 = (int)samples, L2 = L1 / 2, S2 = S1 / 2;
+    const size_t no = (size_t)L2 * S2;
+    Buf b[4] = {{ampl, nullptr, (size_t)(lines * samples * 8)}, {nullptr, g2, no * 16}, {nullptr, g3, no * 8}, {nullptr, quality, no * 8}};
+    const dim3 grid((S2 + TILE - 1) / TILE, (L2 + TILE - 1) / TILE);
+    if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_local: raster too large for one launch");
+    return run(c, mem, b, [&](Buf (&x)[4]) {
+        hipLaunchKernelGGL(k_grad_local, grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double2 *)x[1].dev, (double *)x[2].dev,
+                           (double *)x[3].dev, L1, S1, L2, S2);
+    }, "grad_local");
+}
+
+extern "C" int xsw_grad_hist(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, const double *g2, const double *quality,
+                             int32_t window_lines, int32_t window_samples, int32_t n_rows, const int32_t *rows, int32_t n_cols,
+                             const int32_t *cols, int32_t n_angles, double angle_start, double angle_step, int32_t normalise,
+                             double *weight, double *used_ratio)
+{
+    if (!c) return XSW_EINVAL;
+    if (!g2 || !quality || !rows || !cols || !weight || !used_ratio || lines < 1 || samples < 1 || window_lines < 1 || window_samples < 1 || n_rows < 1 ||
+        n_cols < 1 || n_angles < 1)
+        return gfail(c, XSW_EINVAL, "grad_hist: bad argument");
+    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL || std::min<long long>(window_lines, lines) * std::min<long long>(window_samples, samples) > 0x7fffffffLL)
+        return gfail(c, XSW_EINVAL, "grad_hist: raster or window too large");
+    if ((long long)n_rows * n_cols > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_hist: too many windows");
+    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    const size_t npx = (size_t)lines * samples, nw = (size_t)n_rows * n_cols;
+    Buf b[6] = {{g2, nullptr, npx * 16}, {quality, nullptr, npx * 8}, {rows, nullptr, (size_t)n_rows * 4}, {cols, nullptr, (size_t)n_cols * 4},
+                {nullptr, weight, nw * n_angles * 8}, {nullptr, used_ratio, nw * 8}};
+    return run(c, mem, b, [&](Buf (&x)[6]) {
+        hipLaunchKernelGGL(k_grad_hist, dim3((unsigned)nw), dim3(HIST_THREADS), 0, c->stream, (const double2 *)x[0].dev, (const double *)x[1].dev,
+                           (int)lines, (int)samples, (int)window_lines, (int)window_samples, (const int *)x[2].dev, (int)n_rows, (const int *)x[3].dev, (int)n_cols,
+                           (int)n_angles, angle_start, angle_step, (int)(normalise != 0), (double *)x[4].dev, (double *)x[5].dev);
+    }, "grad_hist");
+}

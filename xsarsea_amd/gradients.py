@@ -1,0 +1,475 @@
+"""Wind-streak direction histograms (Koch 2004) on the GPU: port of `xsarsea.gradients` (reference: src/xsarsea/gradients.py).
+
+    sigma0 -> [f x f box mean] -> ampl = sqrt(R2(sigma0)) -> local_gradients(ampl) -> per-window gradient_histogram
+
+`Gradients(sigma0, windows_sizes, downscales_factors, window_step).histogram` is the notebook's entry point; `Gradients2D` is the
+mono-pol, single-window-size class it stacks.  The raster passes and the per-window histograms run in HIP kernels
+(csrc/xsw_gradients.hip, include/xsw.h: xsw_grad_*); window geometry is host arithmetic that copies the reference's expressions.
+
+Containers (neither xarray nor cv2 is needed): `sigma0` is a 2-D (line, sample) -- or 3-D (pol, line, sample) for `Gradients` --
+numpy array, a device tensor, or any object with `.values` and `.line` / `.sample` coordinates (an xarray.DataArray).  Coordinates
+come from the object, else from the `line=` / `sample=` keywords, else np.arange.  Numpy in gives numpy out; a device tensor in gives
+device tensors out, computed asynchronously on the caller's current stream.
+
+One deliberate deviation: a pixel whose G2 is a negative real with +0 imaginary part has angle +pi/2, bin index n_angles; the
+reference's np.add.at raises IndexError there, this port folds it onto bin 0 (pi/2 == -pi/2 modulo pi).  See DESIGN.md.
+"""
+import numpy as np
+
+from . import _device, _lib, options
+
+__all__ = ["Gradients", "Gradients2D", "GradientsHistogram", "local_gradients", "R2", "gradient_histogram", "circ_smooth",
+           "angles_bins"]
+
+
+def angles_bins(n_angles=72):
+    """Bin centres: the midpoints of linspace(-pi/2, pi/2, n_angles + 1) (gradients.py:93-97)."""
+    b = np.linspace(-np.pi / 2, np.pi / 2, n_angles + 1)
+    return (b[1:] + b[:-1]) / 2
+
+
+# ------------------------------------------------------------------------------------------------------ host geometry
+def coarsen_coords(coords, factor):
+    """Coordinates of a factor-f reduction with the remainder trimmed: the means of the groups (xarray coarsen(...).mean(),
+    Gradients._sigma0_resample.compute_coords)."""
+    coords = np.asarray(coords)
+    n = (len(coords) // factor) * factor
+    return coords[:n].reshape(-1, factor).mean(axis=1)
+
+
+def window_pixels(window_size, line, sample):
+    """Window size in pixels of a grid: int(mean(window_size / smallest coordinate step)) over both axes (gradients.py:146-150,
+    :169-177)."""
+    return int(np.mean(tuple(window_size / np.unique(np.diff(np.asarray(ax)))[0] for ax in (line, sample))))
+
+
+def nearest_indexer(index, target):
+    """pandas.Index(index).get_indexer(target, method="nearest") for an ascending index: the nearest position, a tie going to the
+    larger coordinate (gradients.py:198, `.sel(..., method="nearest")`)."""
+    index, target = np.asarray(index), np.asarray(target)
+    right = np.searchsorted(index, target, side="left")        # first index >= target ('backfill'), len: none
+    left = np.searchsorted(index, target, side="right") - 1    # last index <= target ('pad'), -1: none
+    right_m = np.where(right == len(index), -1, right)
+    left_dist = np.abs(index[left] - target)
+    right_dist = np.abs(index[right_m] - target)
+    return np.where((left_dist < right_dist) | (right_m == -1), left, right_m)
+
+
+def _coord_values(v):
+    return np.asarray(getattr(v, "values", v))
+
+
+class _Raster:
+    """A 2-D or 3-D raster (numpy or device tensor) with its coordinates."""
+
+    def __init__(self, sigma0, line=None, sample=None, pol=None, allow_pol=False):
+        self.device = _device.is_device_array(sigma0)
+        dims = tuple(getattr(sigma0, "dims", ()) or ())
+        if self.device:
+            values = _device.as_tensor(sigma0, _device.device_of(sigma0))
+        elif hasattr(sigma0, "values") and not isinstance(sigma0, np.ndarray):
+            values = np.asarray(sigma0.values)
+            if dims:
+                order = [d for d in ("pol", "line", "sample") if d in dims]
+                if sorted(order) != sorted(dims) or "line" not in order or "sample" not in order:
+                    raise ValueError(f"sigma0 dims must be (line, sample) with an optional pol, not {dims}")
+                values = np.transpose(values, [dims.index(d) for d in order])
+            line = _coord_values(sigma0.line) if line is None and hasattr(sigma0, "line") else line
+            sample = _coord_values(sigma0.sample) if sample is None and hasattr(sigma0, "sample") else sample
+            if pol is None and "pol" in dims:
+                pol = _coord_values(sigma0.pol)
+        else:
+            values = np.asarray(sigma0)
+        if values.ndim not in ((2, 3) if allow_pol else (2,)):
+            raise ValueError(f"sigma0 must be {'2-D or 3-D' if allow_pol else '2-D'}, not {values.ndim}-D")
+        self.values = values
+        self.has_pol = values.ndim == 3
+        shape = tuple(values.shape[-2:])
+        self.line = np.arange(shape[0]) if line is None else _coord_values(line)
+        self.sample = np.arange(shape[1]) if sample is None else _coord_values(sample)
+        if self.line.shape != (shape[0],) or self.sample.shape != (shape[1],):
+            raise ValueError("line / sample coordinates do not match the raster's shape")
+        self.pol = (np.arange(values.shape[0]) if pol is None else _coord_values(pol)) if self.has_pol else None
+
+
+# ------------------------------------------------------------------------------------------------------ device calls
+def _is_tensor(a):
+    return _device.is_device_array(a)
+
+
+class _Call:
+    """Where one kernel call runs: the default context of the array's device on torch's current stream (device arrays), or of
+    options.device with host buffers."""
+
+    def __init__(self, *arrays):
+        self.device = any(_is_tensor(a) for a in arrays)
+        if self.device:
+            import torch
+            self.torch = torch
+            self.dev = _device.device_of(*[a for a in arrays if _is_tensor(a)])
+            self.ctx = _lib.default_context(self.dev.index if self.dev.index is not None else torch.cuda.current_device())
+        else:
+            self.ctx = _lib.default_context(options.device)
+
+    def empty(self, shape, dtype):
+        if self.device:
+            tdt = {np.float32: self.torch.float32, np.float64: self.torch.float64, np.complex128: self.torch.complex128,
+                   np.int32: self.torch.int32}[np.dtype(dtype).type]
+            return self.torch.empty(tuple(shape), dtype=tdt, device=self.dev)
+        return np.empty(shape, dtype)
+
+    def prep(self, a, dtype=None):
+        """Contiguous array of a kernel's input dtype (float32 / float64 rasters pass as they are, anything else -> float64)."""
+        if self.device:
+            t = _device.as_tensor(a, self.dev)
+            if dtype is not None:
+                t = t.to({np.float64: self.torch.float64, np.complex128: self.torch.complex128, np.int32: self.torch.int32}[np.dtype(dtype).type])
+            elif t.dtype not in (self.torch.float32, self.torch.float64):
+                t = t.double()
+            return t.contiguous()
+        a = np.asarray(a)
+        if dtype is not None:
+            return np.ascontiguousarray(a, dtype=dtype)
+        return np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+
+    @staticmethod
+    def ptr(a):
+        return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+    def xsw_dtype(self, a):
+        if self.device:
+            return _device.xsw_dtype(a)
+        return _lib.XSW_F32 if a.dtype == np.float32 else _lib.XSW_F64
+
+    def run(self, fn, inputs):
+        """fn(ctx, mem) on the context; device inputs are recorded on the launch stream (the caching allocator keeps them)."""
+        if not self.device:
+            return fn(self.ctx, _lib.MEM_HOST)
+        with _device.on_current_stream(self.ctx, self.dev):
+            fn(self.ctx, _lib.MEM_DEVICE)
+            cur = self.torch.cuda.current_stream(self.dev)
+            for t in inputs:
+                t.record_stream(cur)
+
+
+def _area(values, factor):
+    """f x f box mean of a 2-D raster, the input's dtype (float32 / float64) kept (xsw_grad_area)."""
+    call = _Call(values)
+    x = call.prep(values)
+    L, S = x.shape
+    out = call.empty((L // factor, S // factor), np.float32 if call.xsw_dtype(x) == _lib.XSW_F32 else np.float64)
+    call.run(lambda ctx, mem: ctx.grad_area_raw(L, S, factor, call.xsw_dtype(x), mem, call.ptr(x), call.ptr(out)), [x])
+    return out
+
+
+def _r2(values, take_sqrt):
+    call = _Call(values)
+    x = call.prep(values)
+    if x.ndim != 2:
+        raise ValueError("R2 needs a 2-D raster")
+    L, S = x.shape
+    if L < 2 or S < 2:
+        raise ValueError("R2 needs at least 2 x 2 pixels")
+    out = call.empty((L // 2, S // 2), np.float64)
+    call.run(lambda ctx, mem: ctx.grad_r2_raw(L, S, call.xsw_dtype(x), mem, take_sqrt, call.ptr(x), call.ptr(out)), [x])
+    return out
+
+
+def _local(ampl):
+    call = _Call(ampl)
+    x = call.prep(ampl, np.float64)
+    if x.ndim != 2:
+        raise ValueError("local_gradients needs a 2-D raster")
+    L, S = x.shape
+    if L < 2 or S < 2:
+        raise ValueError("local_gradients needs at least 2 x 2 pixels")
+    shape = (L // 2, S // 2)
+    g2, g3, c = call.empty(shape, np.complex128), call.empty(shape, np.float64), call.empty(shape, np.float64)
+    call.run(lambda ctx, mem: ctx.grad_local_raw(L, S, mem, call.ptr(x), call.ptr(g2), call.ptr(g3), call.ptr(c)), [x])
+    return g2, g3, c
+
+
+def _hist(g2, c, window, rows, cols, n_angles, bins=None, normalise=True):
+    """Bin sums [rows, cols, n_angles] (divided by the window's pixel count with `normalise`, as an IEEE division on the device
+    whatever the route) and used ratios [rows, cols] of the windows centred at (rows[a], cols[b])."""
+    call = _Call(g2, c)
+    g2, c = call.prep(g2, np.complex128), call.prep(c, np.float64)
+    L, S = g2.shape
+    if c.shape != g2.shape:
+        raise ValueError("g2 and c must have one shape")
+    wl, ws = (window, window) if np.isscalar(window) else window
+    bins = angles_bins(n_angles) if bins is None else np.asarray(bins, dtype=np.float64)
+    rows = call.prep(np.asarray(rows, dtype=np.int32), np.int32)
+    cols = call.prep(np.asarray(cols, dtype=np.int32), np.int32)
+    nr, nc = rows.shape[0], cols.shape[0]
+    weight, ratio = call.empty((nr, nc, len(bins)), np.float64), call.empty((nr, nc), np.float64)
+    if nr and nc:
+        call.run(lambda ctx, mem: ctx.grad_hist_raw(L, S, mem, call.ptr(g2), call.ptr(c), int(wl), int(ws), nr, call.ptr(rows), nc,
+                                                    call.ptr(cols), len(bins), bins[0], bins[1] - bins[0], normalise, call.ptr(weight),
+                                                    call.ptr(ratio)), [g2, c, rows, cols])
+    return weight, ratio
+
+
+# --------------------------------------------------------------------------------------------------- public functions
+def R2(image):
+    """Reduce a 2-D real raster by a factor 2 with no moire effect (gradients.py:689-722): B4 smoothing ("symm" border),
+    NaN-skipping 2 x 2 mean (the remainder trimmed), B2 smoothing.  float64 (lines // 2, samples // 2), same container kind as
+    `image` (numpy or device tensor); the coarse coordinates are `coarsen_coords(coords, 2)`."""
+    values = _Raster(image).values
+    return _r2(values, False)
+
+
+class LocalGradients:
+    """local_gradients' result (the reference's Dataset of G2, G3, c): attribute or item access."""
+
+    def __init__(self, G2, G3, c, line=None, sample=None):
+        self.G2, self.G3, self.c, self.line, self.sample = G2, G3, c, line, sample
+
+    def __getitem__(self, name):
+        return getattr(self, name)
+
+
+def local_gradients(image, line=None, sample=None):
+    """Local gradients of a 2-D amplitude raster (gradients.py:588-634): G2 = sqrt(R2(grad**2)) (complex128; its angle is the
+    gradient direction in [-pi/2, pi/2]), G3 = R2(|grad**2|), c = |R2(grad**2)| / (G3 + 1e-5) set to 0 above 1 or where NaN,
+    grad = Scharr_x + 1j * Scharr_y.  All on the (lines // 2, samples // 2) grid, whose coordinates are the means of pairs."""
+    r = _Raster(image, line, sample)
+    g2, g3, c = _local(r.values)
+    return LocalGradients(g2, g3, c, coarsen_coords(r.line, 2), coarsen_coords(r.sample, 2))
+
+
+def _check_bins(call, g2, c, bins):
+    """IndexError, as the reference's np.add.at raises it, when a pixel that would be summed falls outside numpy's index range
+    -n .. n - 1 (bin n is the documented fold onto bin 0).  Only a g2 that is not a principal square root can do that (G2 from
+    local_gradients never does).  Device input: one synchronising check."""
+    n, start, step = len(bins), float(bins[0]), float(bins[1] - bins[0])
+    if call.device:
+        t = call.torch
+        a, cc = g2.abs(), call.prep(c, np.float64)
+        k = t.round((t.angle(g2) - start) / step)  # round half to even, as numpy's
+        bad = t.isfinite(a) & (a > 0) & ~t.isnan(cc) & ((k > n) | (k < -n))
+        first = int(k[bad][0].item()) if bool(bad.any()) else None
+    else:
+        a, cc = np.abs(g2), np.asarray(c, dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            k = np.round((np.angle(g2) - start) / step)
+            bad = np.isfinite(a) & (a > 0) & ~np.isnan(cc) & ((k > n) | (k < -n))
+        first = int(k[bad][0]) if bad.any() else None
+    if first is not None:
+        raise IndexError(f"index {first} is out of bounds for axis 0 with size {n}")
+
+
+def gradient_histogram(g2, c, angles_bins):
+    """Direction histogram of ONE box (gradients.py:828-879): (bin sums [len(angles_bins)], used ratio).  Each pixel whose |g2|
+    is not NaN and > 0 adds |g2| / (|g2| + median|g2|) * c into bin rint((angle(g2) - angles_bins[0]) / step).  Bin
+    len(angles_bins) (angle +pi/2) is folded onto bin 0 where the reference raises IndexError; any other index outside
+    numpy's range raises IndexError as the reference does."""
+    call = _Call(g2, c)
+    g2 = call.prep(g2, np.complex128)
+    if g2.ndim != 2:
+        raise ValueError("g2 must be 2-D")
+    if np.shape(c) != tuple(g2.shape):
+        raise ValueError("g2 and c must have one shape")
+    _check_bins(call, g2, c, np.asarray(angles_bins, dtype=np.float64))
+    L, S = g2.shape
+    weight, ratio = _hist(g2, c, (L, S), [L // 2], [S // 2], len(angles_bins), angles_bins, normalise=False)
+    return weight[0, 0], ratio[0, 0]
+
+
+_SMOOTHERS = [np.array(k, float) / 4 for k in ([1, 2, 1], [1, 0, 2, 0, 1], [1, 0, 0, 0, 2, 0, 0, 0, 1],
+                                              [1, 0, 0, 0, 0, 0, 0, 0, 2, 0, 0, 0, 0, 0, 0, 0, 1])]
+
+
+def circ_smooth(hist, axis=-1):
+    """Smooth histograms along their angles axis with Bx, Bx2, Bx4, Bx8 in that order, circularly (gradients.py:882-923: the
+    reference pads 17 bins by wrapping, more than the cumulative reach of 15, so its result is exactly circular).  numpy in
+    gives numpy out, a device tensor gives a device tensor (torch ops, the caller's stream)."""
+    if _is_tensor(hist):
+        import torch
+        x = _device.as_tensor(hist, _device.device_of(hist)).double()
+        roll, zeros = torch.roll, torch.zeros_like
+    else:
+        x = np.asarray(hist, dtype=np.float64)
+        roll, zeros = np.roll, np.zeros_like
+    for B in _SMOOTHERS:
+        h = len(B) // 2
+        out = zeros(x)
+        for j, b in enumerate(B):  # out[i] = sum_j B[j] * x[i + j - h]
+            out = out + float(b) * roll(x, h - j, axis)
+        x = out
+    return x
+
+
+# ------------------------------------------------------------------------------------------------------------ classes
+class GradientsHistogram:
+    """Result of `.histogram` (the reference's xarray.Dataset, field and axis names kept):
+    weight [pol?, downscale_factor, window_size, line, sample, angles] (Gradients) or [line, sample, angles] (Gradients2D),
+    used_ratio without the angles axis, and the coordinate vectors.  `pol` is present only when the input had it."""
+
+    def __init__(self, weight, used_ratio, angles, line, sample, dims, **coords):
+        self.weight, self.used_ratio, self.angles, self.line, self.sample, self.dims = weight, used_ratio, angles, line, sample, dims
+        self.window_size = coords.get("window_size")
+        self.downscale_factor = coords.get("downscale_factor")
+        self.pol = coords.get("pol")
+
+    def __getitem__(self, name):
+        return getattr(self, name)
+
+
+class _Field:
+    """One (pol, downscale factor) raster and its lazily computed local gradients, shared by the window sizes.
+
+    Device intermediates are computed on the stream current at their first use; an event recorded there after the launches
+    makes the stream current at any later use wait for them (on the device: the host does not block), so the cached
+    tensors stay ordered when `.histogram` is called again from another stream."""
+
+    def __init__(self, values, line, sample, factor=1):
+        self._src, self.factor = values, factor
+        self.line = coarsen_coords(line, factor) if factor > 1 else np.asarray(line)
+        self.sample = coarsen_coords(sample, factor) if factor > 1 else np.asarray(sample)
+        self._values = values if factor == 1 else None
+        self._values_ev = None
+        self._lg = None
+        self._lg_ev = None
+
+    @staticmethod
+    def _produced(t):
+        """Event on the current stream of t's device, after what has been queued there (None for host arrays)."""
+        if not _is_tensor(t):
+            return None
+        import torch
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(t.device))
+        return ev
+
+    @staticmethod
+    def _consume(ev, t):
+        if ev is not None:
+            import torch
+            torch.cuda.current_stream(t.device).wait_event(ev)
+
+    @property
+    def values(self):
+        if self._values is None:
+            self._values = _area(self._src, self.factor)
+            self._values_ev = self._produced(self._values)
+        else:
+            self._consume(self._values_ev, self._values)
+        return self._values
+
+    @property
+    def lg(self):
+        """(G2, c, line, sample) of local_gradients(sqrt(R2(sigma0)))."""
+        if self._lg is None:
+            g2, _g3, c = _local(_r2(self.values, True))
+            self._lg = (g2, c, coarsen_coords(coarsen_coords(self.line, 2), 2), coarsen_coords(coarsen_coords(self.sample, 2), 2))
+            self._lg_ev = self._produced(g2)
+        else:
+            self._consume(self._lg_ev, self._lg[0])
+        return self._lg
+
+
+class Gradients2D:
+    """Direction histograms of a mono-pol (line, sample) sigma0 for one window size (gradients.py:45-205).
+
+    window_size: in units of the coordinates (1600 = 16 km windows for 10 m coordinates, whatever sigma0's resolution);
+    window_step: window stepping as a fraction of the window (1: no overlap); windows_at: dict(line=, sample=) of window centre
+    coordinates.  window_step and windows_at are mutually exclusive."""
+
+    def __init__(self, sigma0, window_size=1600, window_step=None, windows_at=None, line=None, sample=None):
+        if window_step is not None and windows_at is not None:
+            raise ValueError("window_step and window_at are mutually exclusive")
+        if window_step is None and windows_at is None:
+            window_step = 1
+        if isinstance(sigma0, _Field):
+            self._field = sigma0
+        else:
+            r = _Raster(sigma0, line, sample)
+            self._field = _Field(r.values, r.line, r.sample)
+        self.window_size = window_size
+        self.n_angles = 72
+        """Bin angles count, in the range [-pi/2, pi/2] (can be changed)"""
+        self.window_step = window_step
+        self._windows_at = windows_at
+
+    @property
+    def sigma0(self):
+        return self._field.values
+
+    @property
+    def windows_at(self):
+        """dict(line=, sample=) of window centre coordinates; by default sigma0's coordinates stepped by
+        int(window pixels of sigma0 * window_step) (gradients.py:153-190).  Settable."""
+        if self._windows_at is None and self.window_step is not None:
+            step = int(window_pixels(self.window_size, self._field.line, self._field.sample) * self.window_step)
+            self._windows_at = {"line": self._field.line[::step], "sample": self._field.sample[::step]}
+        return self._windows_at
+
+    @windows_at.setter
+    def windows_at(self, windows_at):
+        self._windows_at = windows_at
+
+    def _weights(self):
+        """(weight [line, sample, angles] divided by the window's pixel count, used_ratio [line, sample], centre coordinates)."""
+        at = self.windows_at
+        at_line, at_sample = _coord_values(at["line"]), _coord_values(at["sample"])
+        g2, c, lg_line, lg_sample = self._field.lg
+        w = window_pixels(self.window_size, lg_line, lg_sample)
+        if w < 1:
+            raise ValueError(f"window_size {self.window_size} is smaller than one pixel of the local-gradients grid")
+        rows, cols = nearest_indexer(lg_line, at_line), nearest_indexer(lg_sample, at_sample)
+        weight, ratio = _hist(g2, c, w, rows, cols, self.n_angles)
+        return weight, ratio, at_line, at_sample
+
+    @property
+    def histogram(self):
+        """Direction histograms of every window: weight [line, sample, angles] (divided by the window's pixel count), used_ratio
+        [line, sample]; line / sample are the window centres (`windows_at`)."""
+        weight, ratio, at_line, at_sample = self._weights()
+        return GradientsHistogram(weight, ratio, angles_bins(self.n_angles), at_line, at_sample, ("line", "sample", "angles"))
+
+
+class Gradients:
+    """Direction histograms at several window sizes and resolutions (gradients.py:248-367).
+
+    sigma0: (line, sample) or (pol, line, sample); windows_sizes: window sizes in coordinate units; downscales_factors: integer
+    box-mean reductions of sigma0 (cv2 INTER_AREA); window_step: stepping of the FIRST (pol, factor, size) combination, whose
+    window centres every other combination uses."""
+
+    def __init__(self, sigma0, windows_sizes=[1600], downscales_factors=[1], window_step=1, line=None, sample=None, pol=None):
+        r = _Raster(sigma0, line, sample, pol, allow_pol=True)
+        self._drop_pol = not r.has_pol
+        self.windows_sizes, self.downscales_factors = list(windows_sizes), list(downscales_factors)
+        self.pol = r.pol
+        planes = [r.values] if self._drop_pol else [r.values[p] for p in range(r.values.shape[0])]
+        self.gradients_list = []
+        for plane in planes:
+            for df in self.downscales_factors:
+                field = _Field(plane, r.line, r.sample, int(df))
+                for ws in self.windows_sizes:
+                    self.gradients_list.append(Gradients2D(field, window_size=ws))
+        # the 1st gradient defines windows_at from window_step for all the others (StackedGradients, :208-245)
+        self.gradients_list[0].window_step = window_step
+        for g in self.gradients_list[1:]:
+            g.windows_at = self.gradients_list[0].windows_at
+
+    @property
+    def histogram(self):
+        """weight [pol?, downscale_factor, window_size, line, sample, angles], used_ratio without angles, and the coordinates."""
+        parts = [g._weights() for g in self.gradients_list]
+        weight, ratio = [p[0] for p in parts], [p[1] for p in parts]
+        lead = ([] if self._drop_pol else [len(self.pol)]) + [len(self.downscales_factors), len(self.windows_sizes)]
+        if _is_tensor(weight[0]):
+            import torch
+            W, R = torch.stack(weight), torch.stack(ratio)
+        else:
+            W, R = np.stack(weight), np.stack(ratio)
+        W = W.reshape(tuple(lead) + tuple(weight[0].shape))
+        R = R.reshape(tuple(lead) + tuple(ratio[0].shape))
+        dims = ("downscale_factor", "window_size", "line", "sample", "angles")
+        coords = dict(window_size=np.asarray(self.windows_sizes), downscale_factor=np.asarray(self.downscales_factors))
+        if not self._drop_pol:
+            dims = ("pol",) + dims
+            coords["pol"] = self.pol
+        g0 = self.gradients_list[0]
+        return GradientsHistogram(W, R, angles_bins(g0.n_angles), parts[0][2], parts[0][3], dims, **coords)
