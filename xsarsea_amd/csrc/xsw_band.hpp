@@ -31,6 +31,8 @@
 // incidence bin, the upper bound along the a-priori direction and two neighbours (co_window_lanes), the window and the two
 // threshold bins, and parks the pixel's search parameters in an LDS slot -- slots SORTED by window class, so that a pass takes
 // the next 64/S slots of its class (no per-pass ranking) and every lane picks its result up once, after the last pass.  The
+// classes of the workgroup's four waves are pooled (XSW_BAND_POOL: one queue per class, passes dealt to the waves round-robin --
+// 6.8 instead of 7.9 passes per wave on the benchmark scene).  A
 // wave then takes 64/S pixels per pass, one per S-lane segment; a lane owns K = 2 or 3 directions of one pixel, blocked (sl,
 // sl + S, ...: every load of a segment reads contiguous words); classes S*K = 4, 6, 8, 12, ..., 96, 128 directions, wider
 // windows loop over chunks in the S = 64 class; on each trip a direction group whose lanes have no rows left is skipped:
@@ -86,7 +88,12 @@ namespace xsw {
 #endif
 #ifndef XSW_BAND_WG_WAVES
 #define XSW_BAND_WG_WAVES 4  // waves (= raster lines) per workgroup; measured 1 / 2 / 4 / 8 / 16: 81.0 / 79.4 / 77.3 / 82.6 / 91.2 ms
+                             // (round 2); with pooled queues 4 / 8: 36.5 / 39.3 ms per bench step (8 spills 12 B per lane)
 #endif
+#ifndef XSW_BAND_POOL
+#define XSW_BAND_POOL 1  // k_invert_band: the window-class queues of the workgroup's waves pooled (band_wave); 0: one queue per wave
+#endif
+static_assert(XSW_BAND_WG_WAVES % 4 == 0 || !XSW_BAND_POOL, "pooled class counts are read as four bytes per word");
 #ifndef XSW_BAND_WAVES
 #define XSW_BAND_WAVES 8
 #endif
@@ -108,6 +115,17 @@ struct BandSlot {  // 64 bytes per pixel, read by every lane of its segment (sam
     int inc_bin /* i_inc | threshold bin of s - d << 16 */, rows /* w_lo | w_hi << 16 */, ipn /* ip_lo | ncols << 16 */;
     int bin_hi /* threshold bin above s + d, or -1 */;
 };
+
+constexpr int kBandClasses = 11;  // window classes S x K = 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128 (band_wave)
+struct BandPool {  // a workgroup's pooled class queues (k_invert_band, XSW_BAND_POOL)
+    alignas(4) unsigned char cnt[kBandClasses][XSW_BAND_WG_WAVES];  // pixels of each class in each wave's slots
+    unsigned short map[64 * XSW_BAND_WG_WAVES];          // pooled queue position -> slot (wave * 64 + slot of the wave)
+};
+__device__ __forceinline__ int byte_sum4(unsigned x)  // the four bytes of x added (each <= 64)
+{
+    x = (x & 0x00ff00ffu) + ((x >> 8) & 0x00ff00ffu);
+    return (int)((x & 0xffffu) + (x >> 16));
+}
 
 struct BandRec {  // what k_invert_band hands to k_invert_band2 per pixel (KArgs::rec_b): 48 bytes, written and read coalesced
     double s, ah, bh;  // sigma0 in dB; the ancillary wind / 2 (b: |b| for a 0..180 deg LUT)
@@ -198,14 +216,16 @@ __device__ __forceinline__ double ld_co(const char *__restrict__ base, unsigned 
 #endif
 template <int S, int K, bool COUNT>
 __device__ __forceinline__ void co_band_pass(const DevTables &L, double inv_dsig, int lane,
-                                             const BandSlot *slots /* this wave's [64], sorted by class */, int *res /* [64], by slot */,
-                                             int first, int count /* slots [first, first + count) -> segments 0 .. count-1 */, unsigned &cand)
+                                             const BandSlot *slots /* this wave's [64], sorted by class; pooled: the workgroup's */, int *res /* by slot */,
+                                             int first, int count /* slots [first, first + count) -> segments 0 .. count-1 */, unsigned &cand,
+                                             const unsigned short *map = nullptr /* pooled: queue position -> slot (BandPool) */)
 {
     constexpr int sweep_max = XSW_BAND_MAX;  // rows a direction may hold
     const double inf = __builtin_inf();
     const int q = lane / S, sl = lane & (S - 1);
     const bool valid = q < count;
-    const int owner = valid ? first + q : lane;  // slot index (idle segment: any slot, its contents are overridden below)
+    // slot index (idle segment: any slot, its contents are overridden below)
+    const int owner = valid ? (map ? (int)map[first + q] : first + q) : lane;
     BandSlot B = slots[owner];
     if (!valid) { B.inc_bin = 0; B.rows = 0; B.ipn = 0; B.bin_hi = -1; }  // idle segment: harmless addresses, nothing scored
     const int B_ip_lo = B.ipn & 0xffff, B_ncols = (int)((unsigned)B.ipn >> 16);
@@ -413,13 +433,37 @@ __device__ __forceinline__ void wave_tail(const DevTables &L, const KArgs &A, lo
 template <typename T, typename TO, bool CR, bool COUNT, int ROLE = 0>
 __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, long long i, bool in, int lane, BandSlot *__restrict__ slots,
                                           int *__restrict__ res_, bool strip_walk = false /* ROLE 2 walking every strip: the short-run pixels are k_invert_band's */,
-                                          long long strip = -1 /* the wave's pixels are strip `strip` of the raster (lane = sample); -1: listed pixels */)
+                                          long long strip = -1 /* the wave's pixels are strip `strip` of the raster (lane = sample); -1: listed pixels */,
+                                          BandPool *__restrict__ pool = nullptr /* k_invert_band: the workgroup's pooled queues (XSW_BAND_POOL) */)
 {
     const double nan = __builtin_nan("");
     int flags, my_flat = -1, my_icr = -1;
     unsigned cand = 0;
-    constexpr int NC = 11;  // window classes: S lanes x K directions = 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128 (and wider: chunks)
-    int pos = -1, first[NC] = {}, ncls[NC] = {};  // slot of this lane's pixel; slot range of each class
+    constexpr int NC = kBandClasses;  // window classes: S lanes x K directions = 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128 (and wider: chunks)
+    // POOLED (k_invert_band, XSW_BAND_POOL): the classes of the workgroup's waves form ONE queue each, and its passes are dealt to the
+    // waves round-robin -- a class present in several waves leaves one part-filled last pass instead of one per wave.  Every wave
+    // still parks its pixels in its own 64 slots, sorted by class; BandPool::map says which slot a queue position is.  The res_
+    // block then holds the workgroup's results by slot (wave * 64 + slot), then the waves' lane -> slot blocks (PK).
+    constexpr bool POOLED = XSW_BAND_POOL && ROLE != 2;
+    constexpr int WG = XSW_BAND_WG_WAVES, PK = POOLED ? 64 * WG : 64;
+    int pos = -1, myc = NC, first[NC] = {}, ncls[NC] = {};  // slot of this lane's pixel, its class; slot range of each class
+    // the pixels a class would leave for a part-filled last pass move up into the next wider class when they fit into
+    // ITS part-filled last pass (their slots lie right before that class's: only the boundary moves; a narrow window in
+    // a wide segment merely leaves lanes idle): one pass less each time
+    auto settle_queues = [&]() {
+#pragma unroll
+        for (int c = 0; c + 1 < NC; ++c) {
+            const int np = 64 / (2 << (c >> 1)), npn = 64 / (2 << ((c + 1) >> 1));  // pixels per pass of this class / of the next
+            const int rem = ncls[c] % np;
+            const int added = (ncls[c + 1] + rem + npn - 1) / npn - (ncls[c + 1] + npn - 1) / npn;
+            if (rem > 0 && added == 0) { ncls[c] -= rem; ncls[c + 1] += rem; first[c + 1] -= rem; }
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {  // wave-uniform by construction: say so (they live in SGPRs through the passes, not in VGPRs)
+            first[c] = __builtin_amdgcn_readfirstlane(first[c]);
+            ncls[c] = __builtin_amdgcn_readfirstlane(ncls[c]);
+        }
+    };
     bool skip = false;        // ROLE 2 walking every strip (list B overflowed): not one of the long-run pixels this kernel is for
     // (F_TO_B in `flags`: ROLE 1, left to the second band kernel -- its band holds a long run of rows; F_TO_C: left to
     // k_invert_blocks -- a finite pixel the band rule is not for: its window leaves the monotone rows, or its band holds more rows /
@@ -518,7 +562,7 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
                 }
             }
             bool hard = false;  // ROLE 1: the handed pixel is worth k_invert_band2's refinement (long run x wide window, or a tail)
-            int myc = NC;
+            myc = NC;
             if (eligb) {
                 const int nv = ncols_p;
                 const int p2 = 31 - __clz(max(nv, 2) - 1);  // 2^p2 < n <= 2^(p2 + 1)
@@ -586,21 +630,7 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
                 ncls[c] = __popcll(m);
                 base += ncls[c];
             }
-            // the pixels a class would leave for a part-filled last pass move up into the next wider class when they fit into
-            // ITS part-filled last pass (their slots lie right before that class's: only the boundary moves; a narrow window in
-            // a wide segment merely leaves lanes idle): one pass less each time
-#pragma unroll
-            for (int c = 0; c + 1 < NC; ++c) {
-                const int np = 64 / (2 << (c >> 1)), npn = 64 / (2 << ((c + 1) >> 1));  // pixels per pass of this class / of the next
-                const int rem = ncls[c] % np;
-                const int added = (ncls[c + 1] + rem + npn - 1) / npn - (ncls[c + 1] + npn - 1) / npn;
-                if (rem > 0 && added == 0) { ncls[c] -= rem; ncls[c + 1] += rem; first[c + 1] -= rem; }
-            }
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {  // wave-uniform by construction: say so (they live in SGPRs through the passes, not in VGPRs)
-                first[c] = __builtin_amdgcn_readfirstlane(first[c]);
-                ncls[c] = __builtin_amdgcn_readfirstlane(ncls[c]);
-            }
+            if constexpr (!POOLED) settle_queues();
             const bool to_rec = ROLE == 1 && A.rec_b != nullptr && (flags & F_TO_B) != 0;
             if constexpr (ROLE == 2) {
                 // k_invert_band2 on a pixel WITHOUT a record (list B as indices, or a pixel marked in the strip mask because its
@@ -657,17 +687,73 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
             }
         }
     }
-    res_[64 + lane] = pos;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    res_[PK + lane] = pos;
+    // (every wave of the workgroup reaches the barriers below: k_invert_band runs a wave past the raster's last line through
+    // with no pixel)
+    const int wv = POOLED ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+    if constexpr (POOLED) {
+        // pooled queues: each wave's class counts (one byte per wave and class) -> the workgroup's queue of every class, in the
+        // order (class, wave, slot); the lane's pixel sits at queue position pos + e.  The promotion rule then acts on the
+        // pooled queues, and each lane enters its pixel into the map.
+        static_assert((WG & (WG - 1)) == 0, "passes are dealt to the waves modulo XSW_BAND_WG_WAVES");
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) pool->cnt[c][wv] = (unsigned char)ncls[c];
+        }
+        __syncthreads();
+        int e = 0, base = 0;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            int n = 0, before = 0;  // the class's pixels in the workgroup / in the waves before this one
+#pragma unroll
+            for (int k = 0; k < WG / 4; ++k) {
+                const unsigned x = (unsigned)__builtin_amdgcn_readfirstlane((int)((const unsigned *)pool->cnt[c])[k]);
+                const int lo = wv - 4 * k;  // bytes of this word that belong to waves before this one
+                n += byte_sum4(x);
+                before += byte_sum4(lo >= 4 ? x : lo <= 0 ? 0u : x & ((1u << (8 * lo)) - 1u));
+            }
+            e = myc == c ? base + before - first[c] : e;
+            first[c] = base;
+            ncls[c] = n;
+            base += n;
+        }
+        settle_queues();
+        if (pos >= 0) pool->map[pos + e] = (unsigned short)(wv * 64 + pos);
+        __syncthreads();
+    } else {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+#ifdef XSW_BAND_PASS_STATS
+    // counter build (profiles: passes per wave): per class group min(c, 7), the passes this wave ran << 32 + the segments they
+    // filled, into A.stats[0..7] (xsw_invert_tu.hip keeps the other kernels' counters out of it)
+    unsigned long long pst[8] = {};
+#endif
     // ---- stage 2: band passes, narrowest windows first (most pixels per pass)
 #ifndef XSW_TIMING_STAGE1_ONLY  // (timing / counter builds only: results are invalid without the passes)
     {
+        int dealt = 0;  // pooled: passes of the narrower classes (the class's first pass goes to wave dealt % WG)
         auto run = [&](auto seg, auto kk, int c) {
-            constexpr int S = decltype(seg)::value, K = decltype(kk)::value;
-            for (int p = 0; p < ncls[c]; p += 64 / S)
-                co_band_pass<S, K, COUNT>(L, A.inv_dsig_co, lane, slots, res_, first[c] + p, min(64 / S, ncls[c] - p), cand);
+            constexpr int S = decltype(seg)::value, K = decltype(kk)::value, np = 64 / S;
+            if constexpr (POOLED) {
+                const int npass = (ncls[c] + np - 1) / np;
+                for (int p = (wv - dealt) & (WG - 1); p < npass; p += WG) {
+                    co_band_pass<S, K, COUNT>(L, A.inv_dsig_co, lane, slots - 64 * wv, res_ - 64 * wv, first[c] + p * np, min(np, ncls[c] - p * np), cand,
+                                              pool->map);
+#ifdef XSW_BAND_PASS_STATS
+                    pst[c < 7 ? c : 7] += (1ULL << 32) + (unsigned long long)min(np, ncls[c] - p * np);
+#endif
+                }
+                dealt += npass;
+            } else {
+                for (int p = 0; p < ncls[c]; p += np) {
+                    co_band_pass<S, K, COUNT>(L, A.inv_dsig_co, lane, slots, res_, first[c] + p, min(np, ncls[c] - p), cand);
+#ifdef XSW_BAND_PASS_STATS
+                    pst[c < 7 ? c : 7] += (1ULL << 32) + (unsigned long long)min(np, ncls[c] - p);
+#endif
+                }
+            }
         };
         using two = std::integral_constant<int, 2>;
         using three = std::integral_constant<int, 3>;
@@ -687,10 +773,21 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
         run(std::integral_constant<int, 64>{}, XSW_BAND_WIDE_K{}, 10);
     }
 #endif
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    pos = res_[64 + lane];
+    if constexpr (POOLED) {
+        __syncthreads();  // the workgroup's passes have settled every slot
+    } else {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+#ifdef XSW_BAND_PASS_STATS
+    if (A.stats && lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (pst[k]) atomicAdd(&A.stats[k], pst[k]);
+    }
+#endif
+    pos = res_[PK + lane];
     if (pos >= 0) my_flat = res_[pos];  // -1: undecided by its pass
     if (ROLE == 1 && (flags & F_REC_DONE) != 0) in = false;  // its record is k_invert_band2's: no cross-pol search, no list, no store here
     if (ROLE == 2 && strip_walk) {  // strip walk: lanes without a co-pol search, and the pixels k_invert_band kept, are not this kernel's
@@ -706,7 +803,11 @@ __global__ __launch_bounds__(64 * XSW_BAND_WG_WAVES, CR ? XSW_BAND_WAVES_CR : XS
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     __shared__ BandSlot slots[XSW_BAND_WG_WAVES][64];  // search parameters of the wave's eligible pixels, sorted by window class
     __shared__ int res_[XSW_BAND_WG_WAVES][128];       // [0, 64): slot -> winning flat index (or -1); [64, 128): lane -> its pixel's slot
-                                                       // (parked here through the passes: one VGPR less where the pressure peaks)
+                                                       // (parked here through the passes: one VGPR less where the pressure peaks);
+                                                       // pooled: the same words as results by slot of the workgroup, then lane -> slot
+#if XSW_BAND_POOL
+    __shared__ BandPool pool;
+#endif
     // same tile walk as k_invert (XCD x owns a contiguous range of tile columns, line groups fastest), as a 2-D grid so that
     // no division is needed: blockIdx.x = xcd + 8 * line group, blockIdx.y = tile column inside the XCD's range (workgroups
     // are dealt to the XCDs round-robin in linear order, x fastest: the XCD of a workgroup is still blockIdx.x & 7)
@@ -715,11 +816,21 @@ __global__ __launch_bounds__(64 * XSW_BAND_WG_WAVES, CR ? XSW_BAND_WAVES_CR : XS
     const long long xcd = blockIdx.x & 7;
     const long long col = xcd * cols_per_xcd + blockIdx.y;
     const long long line = (long long)(blockIdx.x >> 3) * XSW_BAND_WG_WAVES + wv;
-    if (col >= strips_per_line || line >= A.lines) return;  // wave-uniform
     const long long smp = col * 64 + lane;
+#if XSW_BAND_POOL
+    if (col >= strips_per_line) return;  // workgroup-uniform
+    // a wave past the raster's last line (raster heights that are not a multiple of XSW_BAND_WG_WAVES) runs through without a
+    // pixel, on the last line's addresses: it publishes empty classes and takes its share of the workgroup's passes
+    const bool live = line < A.lines;
+    const bool in = live && smp < A.samples;
+    const long long i = (live ? line : A.lines - 1) * A.samples + (smp < A.samples ? smp : A.samples - 1);
+    band_wave<T, TO, CR, COUNT, ROLE>(L, A, i, in, lane, slots[wv], &res_[0][0] + 64 * wv, false, line * strips_per_line + col, &pool);
+#else
+    if (col >= strips_per_line || line >= A.lines) return;  // wave-uniform
     const bool in = smp < A.samples;
     const long long i = line * A.samples + (in ? smp : A.samples - 1);
     band_wave<T, TO, CR, COUNT, ROLE>(L, A, i, in, lane, slots[wv], res_[wv], false, line * strips_per_line + col);
+#endif
 }
 
 }  // namespace xsw

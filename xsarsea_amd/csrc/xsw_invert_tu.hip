@@ -127,6 +127,9 @@ static int launch_invert(xsw_ctx *c, const KArgs &A_in, int algo, const LaunchCt
             hipLaunchKernelGGL((k_invert_band<T, TO, true, false>), band_grid, band_block, 0, lc.stream, c->T, B);
         }
         if (lc.timing) timing_mark(c);
+#ifdef XSW_BAND_PASS_STATS
+        B.stats = nullptr;  // counter build: the statistics buffer holds k_invert_band's passes per class (band_wave), nothing else
+#endif
         if (band2) {
             const dim3 b2_grid((unsigned)std::min<long long>(nblocks, 256 * XSW_BAND2_WAVES));  // XSW_BAND2_WAVES waves per SIMD, 4-wave workgroups
             if (mono) hipLaunchKernelGGL((k_invert_band2<T, TO, false>), b2_grid, band_block, 0, lc.stream, c->T, B);
