@@ -353,6 +353,44 @@ int xsw_grad_hist(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, con
                   int32_t window_lines, int32_t window_samples, int32_t n_rows, const int32_t *rows, int32_t n_cols, const int32_t *cols, int32_t n_angles, double angle_start,
                   double angle_step, int32_t normalise, double *weight, double *used_ratio);
 
+/* ---- rain / heterogeneity mask (filtering_parameters, gradients.py:758-825).  Additive to XSW_VERSION 4; conventions as above. */
+
+/* R2(sqrt(sigma0)) (gradients.py:773 and :776 with R2 :689-722): xsw_grad_r2 with the square root taken on load, in the input's
+ * dtype (float32: the correctly rounded float32 root, widened to float64 afterwards, as np.sqrt on a float32 array; negative
+ * input gives NaN).  No full-resolution amplitude raster is written.  out is float64 (lines / 2) x (samples / 2). */
+int xsw_grad_r2_sqrt(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, const void *sigma0, double *out);
+
+/* local_gradients(sqrt(sigma0)) (gradients.py:773 and :777 with local_gradients :588-634): xsw_grad_local with the square
+ * root taken on load from a float32 or float64 sigma0 raster.  g2 may be NULL (filtering_parameters uses G3 and c only). */
+int xsw_grad_local_sqrt(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, const void *sigma0, double *g2,
+                        double *g3, double *quality);
+
+/* smoothing (gradients.py:675-686): out = scipy convolve2d(x, B2, 3x3, boundary="symm"); the division by convolve2d(ones) is
+ * by 1.0 and is not performed.  coarsen == 0: x = in, out is lines x samples.  coarsen != 0: x = the NaN-skipping 2 x 2 mean of
+ * `in` with the remainder trimmed (xarray coarsen(trim).mean(), :791), out is (lines / 2) x (samples / 2): the quarter-resolution
+ * raster smoothing(resampl) of :794. */
+int xsw_grad_smooth(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, int32_t coarsen, const double *in, double *out);
+
+/* Mean (gradients.py:724-755): convolve2d(in, B4, "symm") then convolve2d(., B42, "symm"), B42 = convolve(B22, B22) = B4
+ * dilated by 2 (9 x 9, 25 non-zero taps k/256), each stage reflecting at the raster's own edge, the divisions by
+ * convolve2d(ones, B4) == 1.0 not performed.  Evaluated separably; the zero taps multiply as in scipy's direct sum, so one
+ * NaN or Inf makes its whole 9 x 9 footprint NaN.  out is lines x samples. */
+int xsw_grad_mean(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, const double *in, double *out);
+
+/* The rest of filtering_parameters (gradients.py:780-819) in one pass over the half-resolution grid (lines x samples here):
+ * r2 = R2(ampl), g3 and quality = G3 and c of local_gradients(ampl), smooth4 = smoothing(coarsen(r2)) ((lines / 2) x (samples / 2)).
+ *   J = Mean(r2), J1 = Mean(r2**2), P1 = sqrt(J1 - J**2) / (J + 1e-5)     (a negative difference gives NaN)
+ *   K = r2 - zoom(smooth4), P2 = K**2 / (J**2 + 1e-5): scipy.ndimage.zoom(order=1, mode="constant", grid_mode=False) to
+ *       lines x samples: output o of an axis reads the coordinate o * (n_in - 1) / (n_out - 1), two taps per axis; a tap of
+ *       weight 0 still multiplies, and the second tap of the last output is the mirrored element n_in - 2
+ *   P3 = g3 / (Mean(g3) + 1e-5), P4 = sqrt(quality)
+ *   f_i = clip(a_i P_i + b_i, 0, 1), (a, b) = (-50, 2.75), (-5000, 3), (-2.5, 4), (-10, 6.3); NaN passes through clip
+ *   F = sqrt(1/4 (f1**2 + f2**2 + f3**2 + f4**2))
+ * out is [5][lines][samples] = f1, f2, f3, f4, F.  Lines :822-823 of the reference cannot run (F has half the shape of
+ * image_ori) and are not ported. */
+int xsw_grad_filter(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, const double *r2, const double *g3, const double *quality,
+                    const double *smooth4, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ EXPORTS = (
     "xsw_synchronize", "xsw_lut_upload", "xsw_invert", "xsw_stats_enable", "xsw_stats_read", "xsw_stats_read_chain", "xsw_detrend", "xsw_lut_interp", "xsw_gmf_eval",
     "xsw_nesz_flatten", "xsw_lut_build", "xsw_lut_read", "xsw_timing_enable", "xsw_timing_read", "xsw_expand_codes", "xsw_expand_codes_on_stream",
     "xsw_host_alloc", "xsw_host_free", "xsw_set_host_threads", "xsw_grad_area", "xsw_grad_r2", "xsw_grad_local", "xsw_grad_hist",
+    "xsw_grad_r2_sqrt", "xsw_grad_local_sqrt", "xsw_grad_smooth", "xsw_grad_mean", "xsw_grad_filter",
 )
 
 
@@ -147,6 +148,11 @@ def load():
         lib.xsw_grad_hist.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                       ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+        lib.xsw_grad_r2_sqrt.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 2
+        lib.xsw_grad_local_sqrt.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 4
+        lib.xsw_grad_smooth.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 2
+        lib.xsw_grad_mean.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 2
+        lib.xsw_grad_filter.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 5
         if lib.xsw_version() != ABI_VERSION:
             raise XswError(f"{_build.LIB} is version {lib.xsw_version()}, this package binds version {ABI_VERSION}: rebuild it")
         _cdll = lib
@@ -542,6 +548,37 @@ class Context:
                                             int(window_lines), int(window_samples), int(n_rows), ctypes.c_void_p(rows_ptr), int(n_cols), ctypes.c_void_p(cols_ptr),
                                             int(n_angles), float(angle_start), float(angle_step), int(bool(normalise)), ctypes.c_void_p(weight_ptr),
                                             ctypes.c_void_p(ratio_ptr)), "xsw_grad_hist")
+
+    @_locked
+    def grad_r2_sqrt_raw(self, lines, samples, dtype, mem, in_ptr, out_ptr):
+        """Thin call of xsw_grad_r2_sqrt: R2(sqrt(sigma0)) -> float64 (lines // 2, samples // 2)."""
+        self._check(self._lib.xsw_grad_r2_sqrt(self._h, int(lines), int(samples), dtype, mem, ctypes.c_void_p(in_ptr),
+                                               ctypes.c_void_p(out_ptr)), "xsw_grad_r2_sqrt")
+
+    @_locked
+    def grad_local_sqrt_raw(self, lines, samples, dtype, mem, in_ptr, g2_ptr, g3_ptr, c_ptr):
+        """Thin call of xsw_grad_local_sqrt: local_gradients(sqrt(sigma0)); g2_ptr None skips G2."""
+        self._check(self._lib.xsw_grad_local_sqrt(self._h, int(lines), int(samples), dtype, mem, ctypes.c_void_p(in_ptr),
+                                                  ctypes.c_void_p(g2_ptr), ctypes.c_void_p(g3_ptr), ctypes.c_void_p(c_ptr)),
+                    "xsw_grad_local_sqrt")
+
+    @_locked
+    def grad_smooth_raw(self, lines, samples, mem, coarsen, in_ptr, out_ptr):
+        """Thin call of xsw_grad_smooth: 3x3 B2 "symm" smoothing of `in` or, with coarsen, of its NaN-skipping 2 x 2 mean."""
+        self._check(self._lib.xsw_grad_smooth(self._h, int(lines), int(samples), mem, int(bool(coarsen)), ctypes.c_void_p(in_ptr),
+                                              ctypes.c_void_p(out_ptr)), "xsw_grad_smooth")
+
+    @_locked
+    def grad_mean_raw(self, lines, samples, mem, in_ptr, out_ptr):
+        """Thin call of xsw_grad_mean: Mean (B4 then B42, "symm") of a float64 raster."""
+        self._check(self._lib.xsw_grad_mean(self._h, int(lines), int(samples), mem, ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr)),
+                    "xsw_grad_mean")
+
+    @_locked
+    def grad_filter_raw(self, lines, samples, mem, r2_ptr, g3_ptr, c_ptr, smooth4_ptr, out_ptr):
+        """Thin call of xsw_grad_filter: (f1, f2, f3, f4, F) as [5, lines, samples] on the half-resolution grid."""
+        self._check(self._lib.xsw_grad_filter(self._h, int(lines), int(samples), mem, ctypes.c_void_p(r2_ptr), ctypes.c_void_p(g3_ptr),
+                                              ctypes.c_void_p(c_ptr), ctypes.c_void_p(smooth4_ptr), ctypes.c_void_p(out_ptr)), "xsw_grad_filter")
 
     @_locked
     def detrend_raw(self, lines, samples, dtype, out_dtype, mem, sigma0_ptr, ratio_row, out_ptr):

@@ -9,6 +9,16 @@
 //   k_grad_hist   gradient_histogram (:828-879) of one window per workgroup: exact median of |G2| by radix select on the
 //                 float64 bit patterns (integer LDS atomics on counters), then the bin sums in a fixed order (deterministic)
 //
+// and the rain / heterogeneity mask filtering_parameters (:758-825; xsw_grad_r2_sqrt / xsw_grad_local_sqrt / xsw_grad_smooth /
+// xsw_grad_mean / xsw_grad_filter):
+//   k_grad_r2 / k_grad_local with SQ   the same kernels taking sqrt(sigma0) on load (float32: the float32 root, then widened)
+//   k_grad_smooth   smoothing (:675-686, 3x3 B2 "symm"), optionally of the NaN-skipping 2x2 mean of its input (the quarter-
+//                   resolution raster smoothing(coarsen(r2)) that filtering_parameters zooms back)
+//   k_grad_mean     Mean (:724-755): B4 then B42 (9x9, B4 dilated by 2, its zero taps multiplying), separable, one 32 x 32 tile
+//                   with a halo of 6 in LDS per workgroup
+//   k_grad_filter   the same Mean on r2, r2**2 and G3 in turn, the bilinear ndimage.zoom(order=1) sample of the quarter
+//                   raster, P1..P4 and f1..f4, F; no half-resolution temporary
+//
 // Every stage reflects at its OWN array's edge, as the reference's chain of separate scipy / xarray calls does.  Sums are
 // float64 in a fixed order; -ffp-contract=off (xsarsea_amd/_build.py) keeps them free of contractions.
 #include <hip/hip_runtime.h>
@@ -112,8 +122,15 @@ __global__ void k_grad_area(const T *__restrict__ in, T *__restrict__ out, long 
     }
 }
 
+// square root on load (filtering_parameters: image = np.sqrt(image_ori) in the input's dtype, widened afterwards).  sqrtf is the
+// correctly rounded IEEE root here (hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt); negative input gives NaN
+template <bool SQ>
+__device__ inline double load_px(float v) { return SQ ? (double)sqrtf(v) : (double)v; }
+template <bool SQ>
+__device__ inline double load_px(double v) { return SQ ? sqrt(v) : v; }
+
 // ------------------------------------------------------------------------------------------------------------ k_grad_r2
-template <typename T>
+template <typename T, bool SQ = false>
 __global__ __launch_bounds__(256) void k_grad_r2(const T *__restrict__ in, double *__restrict__ out, int L1, int S1, int L2, int S2,
                                                  int take_sqrt)
 {
@@ -123,7 +140,7 @@ __global__ __launch_bounds__(256) void k_grad_r2(const T *__restrict__ in, doubl
     const long long fy0 = 2LL * Y0 - 4, fx0 = 2LL * X0 - 4;
     for (int k = tid; k < FR * FR; k += 256) {
         const int ly = k / FR, lx = k - ly * FR;
-        F[ly][lx] = (double)in[refl_symm(fy0 + ly, L1) * S1 + refl_symm(fx0 + lx, S1)];
+        F[ly][lx] = load_px<SQ>(in[refl_symm(fy0 + ly, L1) * S1 + refl_symm(fx0 + lx, S1)]);
     }
     __syncthreads();
     for (int k = tid; k < CH * CH; k += 256) {
@@ -162,7 +179,8 @@ __device__ inline double2 csqrt_principal(double x, double y)
     return make_double2(fabs(0.5 * (y / s)), copysign(s, y));
 }
 
-__global__ __launch_bounds__(256) void k_grad_local(const double *__restrict__ ampl, double2 *__restrict__ g2, double *__restrict__ g3,
+template <typename T = double, bool SQ = false>
+__global__ __launch_bounds__(256) void k_grad_local(const T *__restrict__ ampl, double2 *__restrict__ g2, double *__restrict__ g3,
                                                     double *__restrict__ cq, int L1, int S1, int L2, int S2)
 {
     // A (ampl with its Scharr halo) is dead once grad**2 is formed: the coarse halo planes reuse its storage
@@ -178,7 +196,7 @@ __global__ __launch_bounds__(256) void k_grad_local(const double *__restrict__ a
     const long long ay0 = 2LL * Y0 - 5, ax0 = 2LL * X0 - 5;
     for (int k = tid; k < AR * AR; k += 256) {
         const int ly = k / AR, lx = k - ly * AR;
-        A[ly][lx] = ampl[refl_101(ay0 + ly, L1) * S1 + refl_101(ax0 + lx, S1)];
+        A[ly][lx] = load_px<SQ>(ampl[refl_101(ay0 + ly, L1) * S1 + refl_101(ax0 + lx, S1)]);
     }
     __syncthreads();
     // grad**2 at the fine pixel symm(2*Y0 - 4 + ly, L1): A holds ampl at reflect101(q) for the raw rows q = r - 1 .. r + 1
@@ -230,7 +248,7 @@ __global__ __launch_bounds__(256) void k_grad_local(const double *__restrict__ a
     if (Y < L2 && X < S2) {
         const double zr = conv3(Cr, ty, tx), zi = conv3(Ci, ty, tx), za = conv3(Ca, ty, tx);
         const long long o = (long long)Y * S2 + X;
-        g2[o] = csqrt_principal(zr, zi);
+        if (g2) g2[o] = csqrt_principal(zr, zi);
         g3[o] = za;
         const double c = hypot(zr, zi) / (za + 0.00001);
         cq[o] = c <= 1.0 ? c : 0.0;  // c.where(c <= 1).fillna(0): above 1 or NaN -> 0
@@ -389,6 +407,222 @@ __global__ __launch_bounds__(HIST_THREADS) void k_grad_hist(const double2 *__res
     if (tid == 0) used_ratio[win] = (double)n / wpix;
 }
 
+// ------------------------------------------------------------------------------------- k_grad_smooth / mean / filter
+// NaN-skipping 2x2 mean of `in` (row length S) at the coarse pixel (y, x): xarray coarsen(trim).mean()
+__device__ inline double coarsen_at(const double *__restrict__ in, long long S, long long y, long long x)
+{
+    const double *p = in + 2 * y * S + 2 * x;
+    const double v[4] = {p[0], p[1], p[S], p[S + 1]};
+    int cnt = 0;
+    double s = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+        if (!isnan(v[a])) { s += v[a]; ++cnt; }
+    return cnt ? s / (double)cnt : __builtin_nan("");
+}
+
+// smoothing (:675-686): out = convolve2d(x, B2, "symm") on the Lo x So raster x, which is `in` itself or, with COARSEN, the
+// NaN-skipping 2x2 mean of `in` (rows of S pixels, remainder trimmed).  One output per thread, the 3x3 taps from the cache.
+template <bool COARSEN>
+__global__ __launch_bounds__(256) void k_grad_smooth(const double *__restrict__ in, double *__restrict__ out, int S, int Lo, int So)
+{
+    const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (Y >= Lo || X >= So) return;
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const long long y = refl_symm((long long)Y - 1 + i, Lo);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const long long x = refl_symm((long long)X - 1 + j, So);
+            s += b2(i, j) * (COARSEN ? coarsen_at(in, S, y, x) : in[y * S + x]);
+        }
+    }
+    out[(long long)Y * So + X] = s;
+}
+
+// Mean (:724-755) of one channel on a 32 x 32 tile: convolve2d(B4, "symm") then convolve2d(B42, "symm"), each reflecting at
+// the raster's own edge, both separable (B4 = w5 x w5, B42 = w9 x w9 with w9 = w5 dilated by 2).  The zero taps of w9 multiply,
+// as scipy's direct sum does: a NaN or Inf anywhere in the 9 x 9 footprint gives NaN.
+constexpr int MT = 32;            // outputs per tile side
+constexpr int MX = MT + 12;       // staged side: halo 2 (B4) + 4 (B42)
+constexpr int MM = MT + 8;        // side after B4: halo 4
+constexpr int MXP = MX + 1, MMP = MM + 1;
+
+struct MeanLds {
+    double A[MX * MXP];  // the staged channel, then (stride MMP) the B4 result
+    double B[MX * MMP];  // row pass of B4, then row pass of B42
+    int sy[MM], sx[MM];  // first staged row / column of the B4 taps of each cell of the B4 result
+};
+
+__device__ inline double w5(int i)
+{
+    const double w[5] = {1.0 / 16, 4.0 / 16, 6.0 / 16, 4.0 / 16, 1.0 / 16};
+    return w[i];
+}
+__device__ inline double w9(int i)
+{
+    const double w[9] = {1.0 / 16, 0.0, 4.0 / 16, 0.0, 6.0 / 16, 0.0, 4.0 / 16, 0.0, 1.0 / 16};
+    return w[i];
+}
+
+// Cell m of the B4 result holds Mean-stage-1 at the raster index symm(org - 4 + m, n): the taps of that index start at its
+// staged cell - 2 (the staged cell l holds the input at symm(org - 6 + l, n), so the taps reflect at the input's edge).  Cells
+// past a partial tile are clamped; their values are never used.
+__device__ inline void mean_setup(MeanLds &t, int Y0, int X0, int L, int S)
+{
+    for (int m = threadIdx.x; m < 2 * MM; m += 256) {
+        const int k = m < MM ? m : m - MM;
+        const long long org = m < MM ? Y0 : X0, n = m < MM ? L : S;
+        const int v = clampi(refl_symm(org - 4 + k, n) - (org - 6), 2, MX - 3) - 2;
+        if (m < MM) t.sy[k] = v; else t.sx[k] = v;
+    }
+}
+
+// Mean of the channel load(y, x) at the thread's four outputs (rows threadIdx.x / 32 + 8 * o, column threadIdx.x % 32)
+template <typename Load>
+__device__ inline void mean_tile(MeanLds &t, Load load, int Y0, int X0, int L, int S, double (&out)[4])
+{
+    const int tid = threadIdx.x;
+    for (int k = tid; k < MX * MX; k += 256) {
+        const int ly = k / MX, lx = k - ly * MX;
+        t.A[ly * MXP + lx] = load(refl_symm((long long)Y0 - 6 + ly, L), refl_symm((long long)X0 - 6 + lx, S));
+    }
+    __syncthreads();  // also orders mean_setup's writes and the previous channel's reads of B
+    for (int k = tid; k < MX * MM; k += 256) {
+        const int r = k / MM, mx = k - r * MM;
+        const double *a = &t.A[r * MXP + t.sx[mx]];
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) s += w5(j) * a[j];
+        t.B[r * MMP + mx] = s;
+    }
+    __syncthreads();
+    for (int k = tid; k < MM * MM; k += 256) {
+        const int my = k / MM, mx = k - my * MM;
+        const double *b = &t.B[t.sy[my] * MMP + mx];
+        double s = 0.0;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) s += w5(i) * b[i * MMP];
+        t.A[my * MMP + mx] = s;
+    }
+    __syncthreads();
+    for (int k = tid; k < MM * MT; k += 256) {
+        const int my = k / MT, tx = k - my * MT;
+        const double *a = &t.A[my * MMP + tx];
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) s += w9(j) * a[j];
+        t.B[my * MMP + tx] = s;
+    }
+    __syncthreads();
+    const int ty = tid >> 5, tx = tid & 31;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        const double *b = &t.B[(ty + 8 * o) * MMP + tx];
+        double s = 0.0;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) s += w9(i) * b[i * MMP];
+        out[o] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_grad_mean(const double *__restrict__ in, double *__restrict__ out, int L, int S)
+{
+    __shared__ MeanLds t;
+    const int Y0 = blockIdx.y * MT, X0 = blockIdx.x * MT;
+    double m[4];
+    mean_setup(t, Y0, X0, L, S);
+    mean_tile(t, [&](long long y, long long x) { return in[y * S + x]; }, Y0, X0, L, S, m);
+    const int X = X0 + (threadIdx.x & 31);
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        const int Y = Y0 + (threadIdx.x >> 5) + 8 * o;
+        if (Y < L && X < S) out[(long long)Y * S + X] = m[o];
+    }
+}
+
+// One axis of scipy.ndimage.zoom(order=1, mode="constant", grid_mode=False): output index o reads the input coordinate
+// o * z, z = (n_in - 1) / (n_out - 1); taps floor and floor + 1 with weights 1 - t and 1 - (1 - t).  A tap past the last
+// element (the last output, where its weight is 0) is mirrored to n - 2 (index 0 for a one-element axis) and still
+// multiplies.  A coordinate beyond n - 1 would be outside (cval 0): it does not occur for n_out in {2 n, 2 n + 1}, n <= 20000.
+struct ZoomTap {
+    int i0, i1;
+    double w0, w1;
+    bool inside;
+};
+__device__ inline ZoomTap zoom_tap(int o, double z, int n)
+{
+    ZoomTap t;
+    const double cc = (double)o * z, fl = floor(cc);
+    t.inside = cc <= (double)(n - 1);
+    t.i0 = t.inside ? (int)fl : 0;
+    t.i1 = t.i0 + 1 < n ? t.i0 + 1 : (n > 1 ? n - 2 : 0);
+    t.w0 = 1.0 - (cc - fl);
+    t.w1 = 1.0 - t.w0;
+    return t;
+}
+
+__device__ inline double clip01(double v) { return v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v); }  // np.clip: NaN passes
+
+// filtering_parameters (:780-819) from r2 = R2(ampl), G3 and c of local_gradients(ampl) (L x S) and the quarter-resolution
+// q4 = smoothing(coarsen(r2)) (L4 x S4): out is [5][L][S] = f1, f2, f3, f4, F.
+__global__ __launch_bounds__(256) void k_grad_filter(const double *__restrict__ r2, const double *__restrict__ g3, const double *__restrict__ cq,
+                                                     const double *__restrict__ q4, double *__restrict__ out, int L, int S, int L4, int S4,
+                                                     double zy, double zx)
+{
+    __shared__ MeanLds t;
+    const int Y0 = blockIdx.y * MT, X0 = blockIdx.x * MT;
+    double J[4], J1[4], G4[4];
+    mean_setup(t, Y0, X0, L, S);
+    // the three channels r2, r2**2, G3 in turn through one copy of the tile code (unrolled, it costs 230 VGPRs)
+#pragma unroll 1
+    for (int ch = 0; ch < 3; ++ch) {
+        const double *src = ch == 2 ? g3 : r2;
+        double m[4];
+        mean_tile(t, [&](long long y, long long x) { const double v = src[y * S + x]; return ch == 1 ? v * v : v; }, Y0, X0, L, S, m);
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            if (ch == 0) J[o] = m[o];
+            else if (ch == 1) J1[o] = m[o];
+            else G4[o] = m[o];
+        }
+    }
+    const int X = X0 + (threadIdx.x & 31);
+    const long long plane = (long long)L * S;
+    const ZoomTap tx = zoom_tap(X, zx, S4);
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        const int Y = Y0 + (threadIdx.x >> 5) + 8 * o;
+        if (Y >= L || X >= S) continue;
+        const long long p = (long long)Y * S + X;
+        const double r = r2[p];
+        // P1 = sqrt(Mean(r2**2) - Mean(r2)**2) / (Mean(r2) + 1e-5): a negative difference is NaN, as numpy's
+        const double P1 = sqrt(J1[o] - J[o] * J[o]) / (J[o] + 0.00001);
+        // P2 = (r2 - zoom(q4))**2 / (J**2 + 1e-5); scipy's tap order: ((a00 wy0) wx0 + (a01 wy0) wx1) + (a10 wy1) wx0 + (a11 wy1) wx1
+        const ZoomTap ty = zoom_tap(Y, zy, L4);
+        double z = 0.0;
+        if (ty.inside && tx.inside) {
+            const double *q0 = q4 + (long long)ty.i0 * S4, *q1 = q4 + (long long)ty.i1 * S4;
+            z += q0[tx.i0] * ty.w0 * tx.w0;
+            z += q0[tx.i1] * ty.w0 * tx.w1;
+            z += q1[tx.i0] * ty.w1 * tx.w0;
+            z += q1[tx.i1] * ty.w1 * tx.w1;
+        }
+        const double K = r - z;
+        const double P2 = K * K / (J[o] * J[o] + 0.00001);
+        const double P3 = g3[p] / (G4[o] + 0.00001);
+        const double P4 = sqrt(cq[p]);
+        const double f1 = clip01(-50.0 * P1 + 2.75), f2 = clip01(-5000.0 * P2 + 3.0);
+        const double f3 = clip01(-2.5 * P3 + 4.0), f4 = clip01(-10.0 * P4 + 6.3);
+        out[p] = f1;
+        out[plane + p] = f2;
+        out[2 * plane + p] = f3;
+        out[3 * plane + p] = f4;
+        out[4 * plane + p] = sqrt(1.0 / 4.0 * (f1 * f1 + f2 * f2 + f3 * f3 + f4 * f4));
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------ host side
 static int gfail(xsw_ctx *c, int code, const char *fmt, ...)
 {
@@ -481,10 +715,10 @@ extern "C" int xsw_grad_r2(xsw_ctx *c, int64_t lines, int64_t samples, int32_t d
     if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_r2: raster too large for one launch");
     return run(c, mem, b, [&](Buf (&x)[2]) {
         if (dtype == XSW_F32)
-            hipLaunchKernelGGL(k_grad_r2<float>, grid, dim3(256), 0, c->stream, (const float *)x[0].dev, (double *)x[1].dev, L1, S1, L2, S2,
+            hipLaunchKernelGGL((k_grad_r2<float, false>), grid, dim3(256), 0, c->stream, (const float *)x[0].dev, (double *)x[1].dev, L1, S1, L2, S2,
                                (int)(take_sqrt != 0));
         else
-            hipLaunchKernelGGL(k_grad_r2<double>, grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double *)x[1].dev, L1, S1, L2,
+            hipLaunchKernelGGL((k_grad_r2<double, false>), grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double *)x[1].dev, L1, S1, L2,
                                S2, (int)(take_sqrt != 0));
     }, "grad_r2");
 }
@@ -503,7 +737,7 @@ extern "C" int xsw_grad_local(xsw_ctx *c, int64_t lines, int64_t samples, int32_
     const dim3 grid((S2 + TILE - 1) / TILE, (L2 + TILE - 1) / TILE);
     if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_local: raster too large for one launch");
     return run(c, mem, b, [&](Buf (&x)[4]) {
-        hipLaunchKernelGGL(k_grad_local, grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double2 *)x[1].dev, (double *)x[2].dev,
+        hipLaunchKernelGGL((k_grad_local<double, false>), grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double2 *)x[1].dev, (double *)x[2].dev,
                            (double *)x[3].dev, L1, S1, L2, S2);
     }, "grad_local");
 }
@@ -529,4 +763,105 @@ extern "C" int xsw_grad_hist(xsw_ctx *c, int64_t lines, int64_t samples, int32_t
                            (int)lines, (int)samples, (int)window_lines, (int)window_samples, (const int *)x[2].dev, (int)n_rows, (const int *)x[3].dev, (int)n_cols,
                            (int)n_angles, angle_start, angle_step, (int)(normalise != 0), (double *)x[4].dev, (double *)x[5].dev);
     }, "grad_hist");
+}
+
+extern "C" int xsw_grad_r2_sqrt(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, const void *sigma0, double *out)
+{
+    if (!c) return XSW_EINVAL;
+    if (!sigma0 || !out || lines < 2 || samples < 2) return gfail(c, XSW_EINVAL, "grad_r2_sqrt: bad argument (the raster needs 2 x 2 pixels)");
+    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_r2_sqrt: raster too large");
+    if (dtype != XSW_F32 && dtype != XSW_F64) return gfail(c, XSW_EINVAL, "dtype must be XSW_F32 or XSW_F64");
+    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    const int L1 = (int)lines, S1 = (int)samples, L2 = L1 / 2, S2 = S1 / 2;
+    const long long es = dtype == XSW_F32 ? 4 : 8;
+    Buf b[2] = {{sigma0, nullptr, (size_t)(lines * samples * es)}, {nullptr, out, (size_t)L2 * S2 * 8}};
+    const dim3 grid((S2 + TILE - 1) / TILE, (L2 + TILE - 1) / TILE);
+    if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_r2_sqrt: raster too large for one launch");
+    return run(c, mem, b, [&](Buf (&x)[2]) {
+        if (dtype == XSW_F32)
+            hipLaunchKernelGGL((k_grad_r2<float, true>), grid, dim3(256), 0, c->stream, (const float *)x[0].dev, (double *)x[1].dev, L1, S1, L2, S2, 0);
+        else
+            hipLaunchKernelGGL((k_grad_r2<double, true>), grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double *)x[1].dev, L1, S1, L2, S2, 0);
+    }, "grad_r2_sqrt");
+}
+
+extern "C" int xsw_grad_local_sqrt(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, const void *sigma0, double *g2,
+                                   double *g3, double *quality)
+{
+    if (!c) return XSW_EINVAL;
+    if (!sigma0 || !g3 || !quality || lines < 2 || samples < 2)
+        return gfail(c, XSW_EINVAL, "grad_local_sqrt: bad argument (the raster needs 2 x 2 pixels)");
+    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_local_sqrt: raster too large");
+    if (dtype != XSW_F32 && dtype != XSW_F64) return gfail(c, XSW_EINVAL, "dtype must be XSW_F32 or XSW_F64");
+    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    const int L1 = (int)lines, S1 = (int)samples, L2 = L1 / 2, S2 = S1 / 2;
+    const size_t no = (size_t)L2 * S2;
+    const long long es = dtype == XSW_F32 ? 4 : 8;
+    Buf b[4] = {{sigma0, nullptr, (size_t)(lines * samples * es)}, {nullptr, g3, no * 8}, {nullptr, quality, no * 8}, {nullptr, g2, g2 ? no * 16 : 0}};
+    const dim3 grid((S2 + TILE - 1) / TILE, (L2 + TILE - 1) / TILE);
+    if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_local_sqrt: raster too large for one launch");
+    return run(c, mem, b, [&](Buf (&x)[4]) {
+        double2 *pg2 = g2 ? (double2 *)x[3].dev : nullptr;
+        if (dtype == XSW_F32)
+            hipLaunchKernelGGL((k_grad_local<float, true>), grid, dim3(256), 0, c->stream, (const float *)x[0].dev, pg2, (double *)x[1].dev,
+                               (double *)x[2].dev, L1, S1, L2, S2);
+        else
+            hipLaunchKernelGGL((k_grad_local<double, true>), grid, dim3(256), 0, c->stream, (const double *)x[0].dev, pg2, (double *)x[1].dev,
+                               (double *)x[2].dev, L1, S1, L2, S2);
+    }, "grad_local_sqrt");
+}
+
+extern "C" int xsw_grad_smooth(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, int32_t coarsen, const double *in, double *out)
+{
+    if (!c) return XSW_EINVAL;
+    const int64_t f = coarsen ? 2 : 1;
+    if (!in || !out || lines < f || samples < f) return gfail(c, XSW_EINVAL, "grad_smooth: bad argument");
+    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_smooth: raster too large");
+    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    const int S = (int)samples, Lo = (int)(lines / f), So = (int)(samples / f);
+    Buf b[2] = {{in, nullptr, (size_t)(lines * samples * 8)}, {nullptr, out, (size_t)Lo * So * 8}};
+    const dim3 grid((So + 63) / 64, (Lo + 3) / 4);
+    if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_smooth: raster too large for one launch");
+    return run(c, mem, b, [&](Buf (&x)[2]) {
+        if (coarsen)
+            hipLaunchKernelGGL(k_grad_smooth<true>, grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double *)x[1].dev, S, Lo, So);
+        else
+            hipLaunchKernelGGL(k_grad_smooth<false>, grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double *)x[1].dev, S, Lo, So);
+    }, "grad_smooth");
+}
+
+extern "C" int xsw_grad_mean(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, const double *in, double *out)
+{
+    if (!c) return XSW_EINVAL;
+    if (!in || !out || lines < 1 || samples < 1) return gfail(c, XSW_EINVAL, "grad_mean: bad argument");
+    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_mean: raster too large");
+    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    const int L = (int)lines, S = (int)samples;
+    Buf b[2] = {{in, nullptr, (size_t)L * S * 8}, {nullptr, out, (size_t)L * S * 8}};
+    const dim3 grid((S + MT - 1) / MT, (L + MT - 1) / MT);
+    if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_mean: raster too large for one launch");
+    return run(c, mem, b, [&](Buf (&x)[2]) {
+        hipLaunchKernelGGL(k_grad_mean, grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double *)x[1].dev, L, S);
+    }, "grad_mean");
+}
+
+extern "C" int xsw_grad_filter(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, const double *r2, const double *g3, const double *quality,
+                               const double *smooth4, double *out)
+{
+    if (!c) return XSW_EINVAL;
+    if (!r2 || !g3 || !quality || !smooth4 || !out || lines < 2 || samples < 2)
+        return gfail(c, XSW_EINVAL, "grad_filter: bad argument (the half-resolution raster needs 2 x 2 pixels)");
+    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_filter: raster too large");
+    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    const int L = (int)lines, S = (int)samples, L4 = L / 2, S4 = S / 2;
+    const size_t n = (size_t)L * S;
+    Buf b[5] = {{r2, nullptr, n * 8}, {g3, nullptr, n * 8}, {quality, nullptr, n * 8}, {smooth4, nullptr, (size_t)L4 * S4 * 8}, {nullptr, out, 5 * n * 8}};
+    const dim3 grid((S + MT - 1) / MT, (L + MT - 1) / MT);
+    if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_filter: raster too large for one launch");
+    // scipy's zoom factor of each axis, the same IEEE division
+    const double zy = (double)(L4 - 1) / (double)(L - 1), zx = (double)(S4 - 1) / (double)(S - 1);
+    return run(c, mem, b, [&](Buf (&x)[5]) {
+        hipLaunchKernelGGL(k_grad_filter, grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (const double *)x[1].dev, (const double *)x[2].dev,
+                           (const double *)x[3].dev, (double *)x[4].dev, L, S, L4, S4, zy, zx);
+    }, "grad_filter");
 }

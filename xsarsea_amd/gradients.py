@@ -2,6 +2,9 @@
 
     sigma0 -> [f x f box mean] -> ampl = sqrt(R2(sigma0)) -> local_gradients(ampl) -> per-window gradient_histogram
 
+and the rain / heterogeneity mask of the same module, `filtering_parameters(sigma0)` -> (f1, f2, f3, f4, F) in [0, 1] on the
+half-resolution grid, with its helpers `Mean` and `smoothing`.
+
 `Gradients(sigma0, windows_sizes, downscales_factors, window_step).histogram` is the notebook's entry point; `Gradients2D` is the
 mono-pol, single-window-size class it stacks.  The raster passes and the per-window histograms run in HIP kernels
 (csrc/xsw_gradients.hip, include/xsw.h: xsw_grad_*); window geometry is host arithmetic that copies the reference's expressions.
@@ -19,7 +22,7 @@ import numpy as np
 from . import _device, _lib, options
 
 __all__ = ["Gradients", "Gradients2D", "GradientsHistogram", "local_gradients", "R2", "gradient_histogram", "circ_smooth",
-           "angles_bins"]
+           "angles_bins", "filtering_parameters", "Mean", "smoothing"]
 
 
 def angles_bins(n_angles=72):
@@ -236,6 +239,71 @@ def local_gradients(image, line=None, sample=None):
     r = _Raster(image, line, sample)
     g2, g3, c = _local(r.values)
     return LocalGradients(g2, g3, c, coarsen_coords(r.line, 2), coarsen_coords(r.sample, 2))
+
+
+# ------------------------------------------------------------------------------------- rain / heterogeneity mask
+def _same_shape_filter(image, fn_name):
+    """Mean / smoothing: a 2-D raster through one same-shape float64 kernel."""
+    call = _Call(image)
+    x = call.prep(image, np.float64)
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{fn_name} needs a non-empty 2-D raster")
+    L, S = x.shape
+    out = call.empty((L, S), np.float64)
+    if fn_name == "Mean":
+        call.run(lambda ctx, mem: ctx.grad_mean_raw(L, S, mem, call.ptr(x), call.ptr(out)), [x])
+    else:
+        call.run(lambda ctx, mem: ctx.grad_smooth_raw(L, S, mem, False, call.ptr(x), call.ptr(out)), [x])
+    return out
+
+
+def Mean(image):
+    """Local mean operator (gradients.py:724-755): B4 smoothing then B42 (B4 dilated by 2, 9 x 9), both with the "symm"
+    border.  B42's zero taps multiply as in scipy's sum: one NaN makes its 9 x 9 footprint NaN.  float64, the input's shape
+    and container kind."""
+    return _same_shape_filter(_Raster(image).values, "Mean")
+
+
+def smoothing(image):
+    """3 x 3 B2 smoothing with the "symm" border (gradients.py:675-686).  float64, the input's shape and container kind."""
+    return _same_shape_filter(_Raster(image).values, "smoothing")
+
+
+class FilteringParameters(tuple):
+    """filtering_parameters' result: the reference's 5-tuple (f1, f2, f3, f4, F), which also carries the coordinates of
+    the half-resolution grid as `.line` / `.sample` and the rasters by name."""
+
+    def __new__(cls, f1, f2, f3, f4, F, line=None, sample=None):
+        self = super().__new__(cls, (f1, f2, f3, f4, F))
+        self.f1, self.f2, self.f3, self.f4, self.F, self.line, self.sample = f1, f2, f3, f4, F, line, sample
+        return self
+
+
+def filtering_parameters(image_ori, line=None, sample=None):
+    """Koch filters of a 2-D sigma0 raster (gradients.py:758-825): (f1, f2, f3, f4, F), each float64 in [0, 1] (NaN where the
+    input's NaN reaches) on the (lines // 2, samples // 2) grid; 0 flags heterogeneous sigma0 (rain cells, ships, land edges,
+    fronts).  With ampl = sqrt(sigma0) (in the input's dtype), r2 = R2(ampl) and G3, c of local_gradients(ampl):
+    f1 from the local standard deviation over mean of r2, f2 from r2 minus its quarter-resolution smoothing zoomed back
+    (scipy.ndimage.zoom, order 1), f3 from G3 / Mean(G3), f4 from sqrt(c), F = sqrt(mean(f_i**2)).  sqrt(sigma0) is taken
+    inside the kernels; no full-resolution temporary is made.  Needs at least 4 x 4 pixels (ValueError below that: the
+    quarter-resolution raster would be empty)."""
+    r = _Raster(image_ori, line, sample)
+    L, S = r.values.shape
+    if L < 4 or S < 4:  # the reference divides by the empty quarter-resolution raster's axis length there
+        raise ValueError(f"filtering_parameters needs at least 4 x 4 pixels, not {L} x {S}")
+    call = _Call(r.values)
+    x = call.prep(r.values)
+    L2, S2 = L // 2, S // 2
+    dt = call.xsw_dtype(x)
+    r2, g3, c = (call.empty((L2, S2), np.float64) for _ in range(3))
+    q4 = call.empty((L2 // 2, S2 // 2), np.float64)
+    out = call.empty((5, L2, S2), np.float64)
+    call.run(lambda ctx, mem: ctx.grad_r2_sqrt_raw(L, S, dt, mem, call.ptr(x), call.ptr(r2)), [x])
+    call.run(lambda ctx, mem: ctx.grad_local_sqrt_raw(L, S, dt, mem, call.ptr(x), None, call.ptr(g3), call.ptr(c)), [x])
+    call.run(lambda ctx, mem: ctx.grad_smooth_raw(L2, S2, mem, True, call.ptr(r2), call.ptr(q4)), [r2])
+    call.run(lambda ctx, mem: ctx.grad_filter_raw(L2, S2, mem, call.ptr(r2), call.ptr(g3), call.ptr(c), call.ptr(q4), call.ptr(out)),
+             [r2, g3, c, q4])
+    return FilteringParameters(out[0], out[1], out[2], out[3], out[4], coarsen_coords(r.line, 2), coarsen_coords(r.sample, 2))
 
 
 def _check_bins(call, g2, c, bins):
