@@ -9,6 +9,7 @@ CSRC = os.path.join(HERE, "csrc")
 SRC = os.path.join(CSRC, "xsw.hip")          # context, LUT install, C ABI, the HBM-bound kernels
 SRC_TU = os.path.join(CSRC, "xsw_invert_tu.hip")  # the search kernels of one (input dtype, output dtype) pair: -DXSW_PAIR=0..3
 SRC_GRAD = os.path.join(CSRC, "xsw_gradients.hip")  # wind-streak direction histograms (xsarsea_amd.gradients)
+SRC_STREAKS = os.path.join(CSRC, "xsw_streaks.hip")  # histograms -> streak directions -> a-priori wind raster (xsarsea_amd.streaks)
 DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".hpp"))] + [os.path.join(REPO, "include", "xsw.h")]
 LIB = os.environ.get("XSW_LIB") or os.path.join(HERE, "libxsw.so")  # XSW_LIB: experiment builds only
 OBJDIR = os.path.join(REPO, "build", "obj")
@@ -30,8 +31,8 @@ def needs_build():
 
 
 def build(force=False, verbose=False):
-    """Compile csrc/*.hip -> libxsw.so for gfx950: six translation units side by side (xsw.hip, the search kernels of each
-    dtype pair, the gradient-histogram kernels), then one link.  -ffp-contract=off: the kernels decide exact float64 orderings; FMAs appear only where
+    """Compile csrc/*.hip -> libxsw.so for gfx950: seven translation units side by side (xsw.hip, the search kernels of each
+    dtype pair, the gradient-histogram kernels, the streak-direction kernels), then one link.  -ffp-contract=off: the kernels decide exact float64 orderings; FMAs appear only where
     written explicitly."""
     if not force and not needs_build():
         return LIB
@@ -44,6 +45,7 @@ def build(force=False, verbose=False):
     jobs = [(SRC, os.path.join(OBJDIR, f"{tag}_main.o"), [])]
     jobs += [(SRC_TU, os.path.join(OBJDIR, f"{tag}_pair{k}.o"), [f"-DXSW_PAIR={k}"]) for k in range(4)]
     jobs += [(SRC_GRAD, os.path.join(OBJDIR, f"{tag}_gradients.o"), [])]
+    jobs += [(SRC_STREAKS, os.path.join(OBJDIR, f"{tag}_streaks.o"), [])]
     procs = []
     for src, obj, defs in jobs:
         cmd = common + defs + ["-c", src, "-o", obj]

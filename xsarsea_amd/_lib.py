@@ -26,6 +26,7 @@ EXPORTS = (
     "xsw_nesz_flatten", "xsw_lut_build", "xsw_lut_read", "xsw_timing_enable", "xsw_timing_read", "xsw_expand_codes", "xsw_expand_codes_on_stream",
     "xsw_host_alloc", "xsw_host_free", "xsw_set_host_threads", "xsw_grad_area", "xsw_grad_r2", "xsw_grad_local", "xsw_grad_hist",
     "xsw_grad_r2_sqrt", "xsw_grad_local_sqrt", "xsw_grad_smooth", "xsw_grad_mean", "xsw_grad_filter",
+    "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary",
 )
 
 
@@ -153,6 +154,11 @@ def load():
         lib.xsw_grad_smooth.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 2
         lib.xsw_grad_mean.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 2
         lib.xsw_grad_filter.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 5
+        lib.xsw_streaks_peak.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 5
+        lib.xsw_streaks_resolve.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 4 + [ctypes.c_double] * 2 + \
+            [ctypes.c_void_p]
+        lib.xsw_streaks_ancillary.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                              ctypes.c_int32] + [ctypes.c_void_p] * 6
         if lib.xsw_version() != ABI_VERSION:
             raise XswError(f"{_build.LIB} is version {lib.xsw_version()}, this package binds version {ABI_VERSION}: rebuild it")
         _cdll = lib
@@ -579,6 +585,30 @@ class Context:
         """Thin call of xsw_grad_filter: (f1, f2, f3, f4, F) as [5, lines, samples] on the half-resolution grid."""
         self._check(self._lib.xsw_grad_filter(self._h, int(lines), int(samples), mem, ctypes.c_void_p(r2_ptr), ctypes.c_void_p(g3_ptr),
                                               ctypes.c_void_p(c_ptr), ctypes.c_void_p(smooth4_ptr), ctypes.c_void_p(out_ptr)), "xsw_grad_filter")
+
+    # ---- streak directions -> a-priori wind raster (xsarsea_amd.streaks).  Pointers are ints (device or host addresses per `mem`).
+    @_locked
+    def streaks_peak_raw(self, n_lead, n_windows, n_angles, mem, smooth, weight_ptr, ratio_ptr, index_ptr, weight_out_ptr, ratio_out_ptr):
+        """Thin call of xsw_streaks_peak: mean over the leading axes, circular smoothing, peak bin of every window."""
+        self._check(self._lib.xsw_streaks_peak(self._h, int(n_lead), int(n_windows), int(n_angles), mem, int(bool(smooth)),
+                                               ctypes.c_void_p(weight_ptr), ctypes.c_void_p(ratio_ptr), ctypes.c_void_p(index_ptr),
+                                               ctypes.c_void_p(weight_out_ptr), ctypes.c_void_p(ratio_out_ptr)), "xsw_streaks_peak")
+
+    @_locked
+    def streaks_resolve_raw(self, n_windows, mem, dirs_ptr, weight_ptr, ratio_ptr, anc_ptr, min_weight, min_used_ratio, out_ptr):
+        """Thin call of xsw_streaks_resolve: the windows' unit vectors with the 180 degree ambiguity removed (NaN thresholds: off)."""
+        self._check(self._lib.xsw_streaks_resolve(self._h, int(n_windows), mem, ctypes.c_void_p(dirs_ptr), ctypes.c_void_p(weight_ptr),
+                                                  ctypes.c_void_p(ratio_ptr), ctypes.c_void_p(anc_ptr), float(min_weight), float(min_used_ratio),
+                                                  ctypes.c_void_p(out_ptr)), "xsw_streaks_resolve")
+
+    @_locked
+    def streaks_ancillary_raw(self, lines, samples, mem, anc_ptr, n_rows, n_cols, dirs_ptr, line_first_ptr, line_t_ptr, sample_first_ptr,
+                              sample_t_ptr, out_ptr):
+        """Thin call of xsw_streaks_ancillary: the complex128 a-priori raster from the resolved window directions."""
+        self._check(self._lib.xsw_streaks_ancillary(self._h, int(lines), int(samples), mem, ctypes.c_void_p(anc_ptr), int(n_rows), int(n_cols),
+                                                    ctypes.c_void_p(dirs_ptr), ctypes.c_void_p(line_first_ptr), ctypes.c_void_p(line_t_ptr),
+                                                    ctypes.c_void_p(sample_first_ptr), ctypes.c_void_p(sample_t_ptr), ctypes.c_void_p(out_ptr)),
+                    "xsw_streaks_ancillary")
 
     @_locked
     def detrend_raw(self, lines, samples, dtype, out_dtype, mem, sigma0_ptr, ratio_row, out_ptr):

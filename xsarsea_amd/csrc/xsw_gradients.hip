@@ -30,6 +30,7 @@
 #include <string>
 
 #include "xsw_host.hpp"
+#include "xsw_run.hpp"
 
 namespace {
 
@@ -622,61 +623,6 @@ __global__ __launch_bounds__(256) void k_grad_filter(const double *__restrict__ 
         out[4 * plane + p] = sqrt(1.0 / 4.0 * (f1 * f1 + f2 * f2 + f3 * f3 + f4 * f4));
     }
 }
-
-// ------------------------------------------------------------------------------------------------------------ host side
-static int gfail(xsw_ctx *c, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    c->err = buf;
-    return code;
-}
-
-// Host buffers of one call: uploaded to temporaries, the launch runs on the context's stream, outputs come back, all before
-// the call returns.  Device buffers: the launch alone, asynchronous on the context's stream.
-struct Buf {
-    const void *host_in;  // input: host pointer to upload (nullptr for outputs)
-    void *host_out;       // output: host pointer to fill (nullptr for inputs)
-    size_t bytes;
-    void *dev = nullptr;
-};
-
-template <size_t N, typename Launch>
-static int run(xsw_ctx *c, int32_t mem, Buf (&b)[N], Launch &&launch, const char *what)
-{
-    if (hipSetDevice(c->device) != hipSuccess) return gfail(c, XSW_EHIP, "%s: hipSetDevice failed", what);
-    if (mem == XSW_MEM_DEVICE) {
-        for (auto &x : b) x.dev = x.host_out ? x.host_out : (void *)x.host_in;
-        launch(b);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? XSW_OK : gfail(c, XSW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
-    }
-    int rc = XSW_OK;
-    hipError_t e = hipSuccess;
-    for (auto &x : b)
-        if (e == hipSuccess && x.bytes) e = hipMalloc(&x.dev, x.bytes);
-    if (e != hipSuccess) rc = gfail(c, XSW_ENOMEM, "%s: hipMalloc failed (%s)", what, hipGetErrorString(e));
-    for (auto &x : b)
-        if (!rc && x.host_in && x.bytes && (e = hipMemcpyAsync(x.dev, x.host_in, x.bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
-            rc = gfail(c, XSW_EHIP, "%s: upload failed (%s)", what, hipGetErrorString(e));
-    if (!rc) {
-        launch(b);
-        if ((e = hipGetLastError()) != hipSuccess) rc = gfail(c, XSW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
-    }
-    for (auto &x : b)
-        if (!rc && x.host_out && x.bytes && (e = hipMemcpyAsync(x.host_out, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
-            rc = gfail(c, XSW_EHIP, "%s: download failed (%s)", what, hipGetErrorString(e));
-    e = hipStreamSynchronize(c->stream);  // also before freeing after a failure: queued work may still use the temporaries
-    if (!rc && e != hipSuccess) rc = gfail(c, XSW_EHIP, "%s: %s", what, hipGetErrorString(e));
-    for (auto &x : b)
-        if (x.dev) (void)hipFree(x.dev);
-    return rc;
-}
-
-static bool bad_mem(int32_t mem) { return mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE; }
 
 }  // namespace
 
