@@ -353,6 +353,27 @@ int xsw_grad_hist(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, con
                   int32_t window_lines, int32_t window_samples, int32_t n_rows, const int32_t *rows, int32_t n_cols, const int32_t *cols, int32_t n_angles, double angle_start,
                   double angle_step, int32_t normalise, double *weight, double *used_ratio);
 
+/* xsw_grad_hist with a keep mask on the g2 / quality grid (`keep`: lines x samples bytes): a pixel whose byte is 0 behaves
+ * exactly as if its g2 were NaN -- it is not kept, stays out of the median, adds to no bin and does not count in used_ratio's
+ * numerator (the denominator stays window_lines * window_samples).  The thread -> pixel assignment and every summation order are
+ * xsw_grad_hist's: the result is bit-identical to xsw_grad_hist on a copy of g2 with NaN written at the masked pixels.  The mask
+ * byte is read before g2, so a masked pixel costs 1 B.  keep == NULL is XSW_EINVAL. */
+int xsw_grad_hist_masked(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, const double *g2, const double *quality,
+                         const uint8_t *keep, int32_t window_lines, int32_t window_samples, int32_t n_rows, const int32_t *rows,
+                         int32_t n_cols, const int32_t *cols, int32_t n_angles, double angle_start, double angle_step, int32_t normalise,
+                         double *weight, double *used_ratio);
+
+/* Keep masks for xsw_grad_hist_masked: out[i][j] = 1 iff every one of the block x block inputs src[block*i .. ][block*j .. ] is
+ * usable, else 0; out is (lines / block) x (samples / block) bytes, rows (samples / block) bytes apart, the remainder of src
+ * trimmed.  _f64: usable iff x >= threshold (an IEEE comparison: NaN is not usable; +-Inf thresholds are allowed, a NaN threshold is
+ * XSW_EINVAL).  _u8: usable iff non-zero.  and_with (may be NULL) is a mask on the OUTPUT grid that is AND-ed in (non-zero = keep).
+ * block is 2 for filtering_parameters' F (half -> quarter resolution) and 4 f for a mask on the sigma0 grid at downscale factor f.
+ * XSW_EINVAL for block < 1 or an empty output.  A streaming pass: each input read once, 1 B written per block. */
+int xsw_grad_keep_f64(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, const double *src, double threshold, int32_t block,
+                      const uint8_t *and_with, uint8_t *out);
+int xsw_grad_keep_u8(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, const uint8_t *src, int32_t block, const uint8_t *and_with,
+                     uint8_t *out);
+
 /* ---- rain / heterogeneity mask (filtering_parameters, gradients.py:758-825).  Additive to XSW_VERSION 4; conventions as above. */
 
 /* R2(sqrt(sigma0)) (gradients.py:773 and :776 with R2 :689-722): xsw_grad_r2 with the square root taken on load, in the input's

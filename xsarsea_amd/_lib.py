@@ -26,6 +26,7 @@ EXPORTS = (
     "xsw_nesz_flatten", "xsw_lut_build", "xsw_lut_read", "xsw_timing_enable", "xsw_timing_read", "xsw_expand_codes", "xsw_expand_codes_on_stream",
     "xsw_host_alloc", "xsw_host_free", "xsw_set_host_threads", "xsw_grad_area", "xsw_grad_r2", "xsw_grad_local", "xsw_grad_hist",
     "xsw_grad_r2_sqrt", "xsw_grad_local_sqrt", "xsw_grad_smooth", "xsw_grad_mean", "xsw_grad_filter",
+    "xsw_grad_hist_masked", "xsw_grad_keep_f64", "xsw_grad_keep_u8",
     "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary",
 )
 
@@ -149,6 +150,13 @@ def load():
         lib.xsw_grad_hist.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                       ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+        lib.xsw_grad_hist_masked.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 3 + \
+            [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+             ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+        lib.xsw_grad_keep_f64.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_double,
+                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+        lib.xsw_grad_keep_u8.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                         ctypes.c_void_p, ctypes.c_void_p]
         lib.xsw_grad_r2_sqrt.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 2
         lib.xsw_grad_local_sqrt.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 4
         lib.xsw_grad_smooth.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 2
@@ -554,6 +562,28 @@ class Context:
                                             int(window_lines), int(window_samples), int(n_rows), ctypes.c_void_p(rows_ptr), int(n_cols), ctypes.c_void_p(cols_ptr),
                                             int(n_angles), float(angle_start), float(angle_step), int(bool(normalise)), ctypes.c_void_p(weight_ptr),
                                             ctypes.c_void_p(ratio_ptr)), "xsw_grad_hist")
+
+    @_locked
+    def grad_hist_masked_raw(self, lines, samples, mem, g2_ptr, c_ptr, keep_ptr, window_lines, window_samples, n_rows, rows_ptr, n_cols,
+                             cols_ptr, n_angles, angle_start, angle_step, normalise, weight_ptr, ratio_ptr):
+        """Thin call of xsw_grad_hist_masked: xsw_grad_hist with a uint8 keep mask on the g2 grid (0 = the pixel behaves as a NaN g2)."""
+        self._check(self._lib.xsw_grad_hist_masked(self._h, int(lines), int(samples), mem, ctypes.c_void_p(g2_ptr), ctypes.c_void_p(c_ptr),
+                                                   ctypes.c_void_p(keep_ptr), int(window_lines), int(window_samples), int(n_rows),
+                                                   ctypes.c_void_p(rows_ptr), int(n_cols), ctypes.c_void_p(cols_ptr), int(n_angles),
+                                                   float(angle_start), float(angle_step), int(bool(normalise)), ctypes.c_void_p(weight_ptr),
+                                                   ctypes.c_void_p(ratio_ptr)), "xsw_grad_hist_masked")
+
+    @_locked
+    def grad_keep_raw(self, lines, samples, mem, src_ptr, threshold, block, and_with_ptr, out_ptr):
+        """Thin call of xsw_grad_keep_f64 (float64 src, usable iff >= threshold) or, with threshold None, xsw_grad_keep_u8 (uint8
+        src, usable iff non-zero): block x block reduction to a uint8 keep mask; and_with_ptr (None: absent) is AND-ed in."""
+        if threshold is None:
+            rc = self._lib.xsw_grad_keep_u8(self._h, int(lines), int(samples), mem, ctypes.c_void_p(src_ptr), int(block),
+                                            ctypes.c_void_p(and_with_ptr), ctypes.c_void_p(out_ptr))
+        else:
+            rc = self._lib.xsw_grad_keep_f64(self._h, int(lines), int(samples), mem, ctypes.c_void_p(src_ptr), float(threshold), int(block),
+                                             ctypes.c_void_p(and_with_ptr), ctypes.c_void_p(out_ptr))
+        self._check(rc, "xsw_grad_keep_u8" if threshold is None else "xsw_grad_keep_f64")
 
     @_locked
     def grad_r2_sqrt_raw(self, lines, samples, dtype, mem, in_ptr, out_ptr):

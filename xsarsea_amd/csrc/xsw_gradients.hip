@@ -8,6 +8,8 @@
 //                 same tiling; writes G2 = sqrt(R2(grad**2)), G3 = R2(|grad**2|) and the quality c
 //   k_grad_hist   gradient_histogram (:828-879) of one window per workgroup: exact median of |G2| by radix select on the
 //                 float64 bit patterns (integer LDS atomics on counters), then the bin sums in a fixed order (deterministic)
+//   k_grad_hist_masked  the same code with a uint8 keep mask on the G2 grid: a pixel whose byte is 0 behaves as a NaN G2
+//   k_grad_keep   b x b block reduction of a raster to that keep mask (xsw_grad_keep_f64 / xsw_grad_keep_u8)
 //
 // and the rain / heterogeneity mask filtering_parameters (:758-825; xsw_grad_r2_sqrt / xsw_grad_local_sqrt / xsw_grad_smooth /
 // xsw_grad_mean / xsw_grad_filter):
@@ -262,10 +264,14 @@ struct HistWin {
     int nr, nc;        // window rows / columns inside the raster (the rest is NaN padding: never kept)
 };
 
-__device__ inline bool kept(const double2 *g2, const HistWin &h, long long S, int p, double &a)
+// MASKED: the keep byte is read before the 16-byte G2 load, so a masked-out pixel costs 1 B
+template <bool MASKED>
+__device__ inline bool kept(const double2 *g2, const uint8_t *keep, const HistWin &h, long long S, int p, double &a)
 {
     const int i = p / h.nc, j = p - i * h.nc;
-    const double2 z = g2[(h.r0 + i) * S + h.c0 + j];
+    const long long o = (h.r0 + i) * S + h.c0 + j;
+    if (MASKED && !keep[o]) return false;
+    const double2 z = g2[o];
     a = hypot(z.x, z.y);
     return !isnan(a) && a > 0.0;
 }
@@ -278,10 +284,13 @@ __device__ inline unsigned long long bits_of(double a)
 // One window per workgroup.  Rows / columns outside the raster are the NaN padding of xarray's rolling(center=True): they
 // count in the window's size (wl*ws) and are never kept, so only the clipped rectangle is read.  weight receives the bin sums
 // (gradient_histogram's `grads`), divided by the window's pixel count when `normalise` (Gradients2D.histogram :118-120).
-__global__ __launch_bounds__(HIST_THREADS) void k_grad_hist(const double2 *__restrict__ g2, const double *__restrict__ cq, int L, int S,
-                                                            int wl, int ws, const int *__restrict__ rows, int n_rows, const int *__restrict__ cols,
-                                                            int n_cols, int n_angles, double start, double step, int normalise,
-                                                            double *__restrict__ weight, double *__restrict__ used_ratio)
+// MASKED: `keep` (L x S bytes) removes the pixels whose byte is 0 exactly as a NaN G2 would: not kept, so outside the median,
+// the bins and used_ratio's numerator.  The thread -> pixel assignment and every summation order are the same in both forms.
+template <bool MASKED>
+__device__ __forceinline__ void hist_window(const double2 *__restrict__ g2, const double *__restrict__ cq, const uint8_t *__restrict__ keep, int L,
+                                            int S, int wl, int ws, const int *__restrict__ rows, int n_rows, const int *__restrict__ cols, int n_cols,
+                                            int n_angles, double start, double step, int normalise, double *__restrict__ weight,
+                                            double *__restrict__ used_ratio)
 {
     __shared__ unsigned hist[2][RADIX];
     __shared__ unsigned long long s_prefix[2];
@@ -316,7 +325,7 @@ __global__ __launch_bounds__(HIST_THREADS) void k_grad_hist(const double2 *__res
         const bool same = p0 == p1;
         for (int p = tid; p < np; p += HIST_THREADS) {
             double a;
-            if (!kept(g2, h, S, p, a)) continue;
+            if (!kept<MASKED>(g2, keep, h, S, p, a)) continue;
             const unsigned long long key = bits_of(a);
             const unsigned d = (unsigned)(key >> sh) & dmask;
             if ((key & pmask) == p0) atomicAdd(&hist[0][d], 1u);
@@ -375,7 +384,7 @@ __global__ __launch_bounds__(HIST_THREADS) void k_grad_hist(const double2 *__res
         if (n > 0) {
             for (int p = tid; p < np; p += HIST_THREADS) {
                 double a;
-                if (!kept(g2, h, S, p, a)) continue;
+                if (!kept<MASKED>(g2, keep, h, S, p, a)) continue;
                 const int i = p / h.nc, j = p - i * h.nc;
                 const long long o = (h.r0 + i) * S + h.c0 + j;
                 const double2 z = g2[o];
@@ -406,6 +415,88 @@ __global__ __launch_bounds__(HIST_THREADS) void k_grad_hist(const double2 *__res
         __syncthreads();
     }
     if (tid == 0) used_ratio[win] = (double)n / wpix;
+}
+
+__global__ __launch_bounds__(HIST_THREADS) void k_grad_hist(const double2 *__restrict__ g2, const double *__restrict__ cq, int L, int S,
+                                                            int wl, int ws, const int *__restrict__ rows, int n_rows, const int *__restrict__ cols,
+                                                            int n_cols, int n_angles, double start, double step, int normalise,
+                                                            double *__restrict__ weight, double *__restrict__ used_ratio)
+{
+    hist_window<false>(g2, cq, nullptr, L, S, wl, ws, rows, n_rows, cols, n_cols, n_angles, start, step, normalise, weight, used_ratio);
+}
+
+__global__ __launch_bounds__(HIST_THREADS) void k_grad_hist_masked(const double2 *__restrict__ g2, const double *__restrict__ cq,
+                                                                   const uint8_t *__restrict__ keep, int L, int S, int wl, int ws,
+                                                                   const int *__restrict__ rows, int n_rows, const int *__restrict__ cols, int n_cols,
+                                                                   int n_angles, double start, double step, int normalise,
+                                                                   double *__restrict__ weight, double *__restrict__ used_ratio)
+{
+    hist_window<true>(g2, cq, keep, L, S, wl, ws, rows, n_rows, cols, n_cols, n_angles, start, step, normalise, weight, used_ratio);
+}
+
+// ---------------------------------------------------------------------------------------------------------- k_grad_keep
+// out[Y][X] = 1 iff every input of the b x b block (Y, X) is usable (and and_with[Y][X] != 0 when given), the remainder of the
+// raster trimmed.  Usable: x >= threshold for double (an IEEE comparison: NaN is not usable), non-zero for uint8.
+// A pure streaming pass shaped as k_detrend: grid.x tiles the output columns (one per thread), grid.y tiles blocks of output
+// rows, and a thread streams down its rows.  Each row of a block is read in vectors of W bytes (the host picks the widest W
+// that divides the block's row bytes and the raster's row bytes and to which the base is aligned: 16 for the even-width F
+// raster at b = 2); the loads of one output are independent of each other and of the next output's.
+template <int W> struct KeepVec;
+template <> struct KeepVec<16> { typedef uint4 type; };
+template <> struct KeepVec<8> { typedef uint2 type; };
+template <> struct KeepVec<4> { typedef unsigned type; };
+template <> struct KeepVec<1> { typedef uint8_t type; };
+
+__device__ inline bool word_nonzero_bytes(unsigned w) { return ((w - 0x01010101u) & ~w & 0x80808080u) == 0; }  // no zero byte
+
+template <typename T>
+struct KeepTest;
+template <>
+struct KeepTest<double> {
+    double thr;
+    __device__ bool ok(uint4 v) const
+    {
+        const double a = __hiloint2double((int)v.y, (int)v.x), b = __hiloint2double((int)v.w, (int)v.z);
+        return (a >= thr) & (b >= thr);
+    }
+    __device__ bool ok(uint2 v) const { return __hiloint2double((int)v.y, (int)v.x) >= thr; }
+};
+template <>
+struct KeepTest<uint8_t> {
+    __device__ bool ok(uint4 v) const
+    {
+        return word_nonzero_bytes(v.x) & word_nonzero_bytes(v.y) & word_nonzero_bytes(v.z) & word_nonzero_bytes(v.w);
+    }
+    __device__ bool ok(uint2 v) const { return word_nonzero_bytes(v.x) & word_nonzero_bytes(v.y); }
+    __device__ bool ok(unsigned v) const { return word_nonzero_bytes(v); }
+    __device__ bool ok(uint8_t v) const { return v != 0; }
+};
+
+// S: input row length in elements; nv = b * sizeof(T) / W vectors per block row.  B != 0 fixes b = B and nv = 1 at compile time
+// (the F raster's 2 x 2 blocks of doubles, 16 B per block row): four output rows, eight loads, in flight per lane.
+template <typename T, int W, int B>
+__global__ __launch_bounds__(256) void k_grad_keep(const T *__restrict__ in, const uint8_t *__restrict__ and_with, uint8_t *__restrict__ out,
+                                                   long long S, int b, int nv, long long Lo, long long So, long long rows_per_block,
+                                                   KeepTest<T> test)
+{
+    typedef typename KeepVec<W>::type vec_t;
+    const long long X = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (X >= So) return;
+    const long long y0 = (long long)blockIdx.y * rows_per_block;
+    const long long y1 = y0 + rows_per_block < Lo ? y0 + rows_per_block : Lo;
+    const int bb = B ? B : b, nvv = B ? 1 : nv;
+    const long long row_vecs = S * (long long)sizeof(T) / W;  // W divides the row bytes
+    const vec_t *col = (const vec_t *)in + X * nvv;
+#pragma unroll B ? 4 : 1
+    for (long long Y = y0; Y < y1; ++Y) {
+        const vec_t *p = col + Y * bb * row_vecs;
+        bool ok = and_with ? and_with[Y * So + X] != 0 : true;
+#pragma unroll B ? B : 2
+        for (int i = 0; i < bb; ++i, p += row_vecs)
+#pragma unroll B ? 1 : 2
+            for (int k = 0; k < nvv; ++k) ok &= test.ok(p[k]);
+        out[Y * So + X] = ok ? 1 : 0;
+    }
 }
 
 // ------------------------------------------------------------------------------------- k_grad_smooth / mean / filter
@@ -709,6 +800,90 @@ extern "C" int xsw_grad_hist(xsw_ctx *c, int64_t lines, int64_t samples, int32_t
                            (int)lines, (int)samples, (int)window_lines, (int)window_samples, (const int *)x[2].dev, (int)n_rows, (const int *)x[3].dev, (int)n_cols,
                            (int)n_angles, angle_start, angle_step, (int)(normalise != 0), (double *)x[4].dev, (double *)x[5].dev);
     }, "grad_hist");
+}
+
+extern "C" int xsw_grad_hist_masked(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, const double *g2, const double *quality,
+                                    const uint8_t *keep, int32_t window_lines, int32_t window_samples, int32_t n_rows, const int32_t *rows,
+                                    int32_t n_cols, const int32_t *cols, int32_t n_angles, double angle_start, double angle_step,
+                                    int32_t normalise, double *weight, double *used_ratio)
+{
+    if (!c) return XSW_EINVAL;
+    if (!keep) return gfail(c, XSW_EINVAL, "grad_hist_masked: keep is NULL (the unmasked histogram is xsw_grad_hist)");
+    if (!g2 || !quality || !rows || !cols || !weight || !used_ratio || lines < 1 || samples < 1 || window_lines < 1 || window_samples < 1 || n_rows < 1 ||
+        n_cols < 1 || n_angles < 1)
+        return gfail(c, XSW_EINVAL, "grad_hist_masked: bad argument");
+    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL || std::min<long long>(window_lines, lines) * std::min<long long>(window_samples, samples) > 0x7fffffffLL)
+        return gfail(c, XSW_EINVAL, "grad_hist_masked: raster or window too large");
+    if ((long long)n_rows * n_cols > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_hist_masked: too many windows");
+    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    const size_t npx = (size_t)lines * samples, nw = (size_t)n_rows * n_cols;
+    Buf b[7] = {{g2, nullptr, npx * 16}, {quality, nullptr, npx * 8}, {rows, nullptr, (size_t)n_rows * 4}, {cols, nullptr, (size_t)n_cols * 4},
+                {nullptr, weight, nw * n_angles * 8}, {nullptr, used_ratio, nw * 8}, {keep, nullptr, npx}};
+    return run(c, mem, b, [&](Buf (&x)[7]) {
+        hipLaunchKernelGGL(k_grad_hist_masked, dim3((unsigned)nw), dim3(HIST_THREADS), 0, c->stream, (const double2 *)x[0].dev, (const double *)x[1].dev,
+                           (const uint8_t *)x[6].dev, (int)lines, (int)samples, (int)window_lines, (int)window_samples, (const int *)x[2].dev, (int)n_rows,
+                           (const int *)x[3].dev, (int)n_cols, (int)n_angles, angle_start, angle_step, (int)(normalise != 0), (double *)x[4].dev,
+                           (double *)x[5].dev);
+    }, "grad_hist_masked");
+}
+
+// One launch of k_grad_keep: the widest vector the block's row bytes, the raster's row bytes and the base address allow.
+template <typename T>
+static int grad_keep(xsw_ctx *c, const char *what, int64_t lines, int64_t samples, int32_t mem, const T *src, KeepTest<T> test, int32_t block,
+                     const uint8_t *and_with, uint8_t *out)
+{
+    if (!src || !out || block < 1 || lines < block || samples < block) return gfail(c, XSW_EINVAL, "%s: bad argument (block < 1 or an empty output)", what);
+    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "%s: raster too large", what);
+    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    const long long Lo = lines / block, So = samples / block, es = (long long)sizeof(T);
+    const size_t no = (size_t)Lo * So;
+    Buf b[3] = {{src, nullptr, (size_t)(lines * samples * es)}, {and_with, nullptr, and_with ? no : 0}, {nullptr, out, no}};
+    // the grid of k_detrend: about 16 workgroups per CU, each a 256-column strip of a block of output rows
+    const long long gx = (So + 255) / 256;
+    long long gy = (256LL * 16 + gx - 1) / gx;
+    gy = std::max<long long>(1, std::min<long long>(std::min<long long>(gy, Lo), 65535));
+    const long long rpb = (Lo + gy - 1) / gy;
+    gy = (Lo + rpb - 1) / rpb;
+    const dim3 grid((unsigned)gx, (unsigned)gy);
+    return run(c, mem, b, [&](Buf (&x)[3]) {
+        const T *in = (const T *)x[0].dev;
+        const uint8_t *aw = and_with ? (const uint8_t *)x[1].dev : nullptr;
+        uint8_t *o = (uint8_t *)x[2].dev;
+        int W = (int)es;
+        for (int w = 16; w >= 4 && w > es; w >>= 1)
+            if ((block * es) % w == 0 && (samples * es) % w == 0 && (uintptr_t)in % w == 0) { W = w; break; }
+        const int nv = (int)(block * es / W);
+#define XSW_KEEP_LAUNCH(WW, BB)                                                                                                              \
+    hipLaunchKernelGGL((k_grad_keep<T, WW, BB>), grid, dim3(256), 0, c->stream, in, aw, o, (long long)samples, (int)block, nv, Lo, So, rpb, test)
+        if constexpr (sizeof(T) == 8) {
+            if (W == 16 && block == 2) XSW_KEEP_LAUNCH(16, 2);
+            else if (W == 16) XSW_KEEP_LAUNCH(16, 0);
+            else XSW_KEEP_LAUNCH(8, 0);
+        } else {
+            if (W == 16) XSW_KEEP_LAUNCH(16, 0);
+            else if (W == 8) XSW_KEEP_LAUNCH(8, 0);
+            else if (W == 4) XSW_KEEP_LAUNCH(4, 0);
+            else XSW_KEEP_LAUNCH(1, 0);
+        }
+#undef XSW_KEEP_LAUNCH
+    }, what);
+}
+
+extern "C" int xsw_grad_keep_f64(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, const double *src, double threshold, int32_t block,
+                                 const uint8_t *and_with, uint8_t *out)
+{
+    if (!c) return XSW_EINVAL;
+    if (std::isnan(threshold)) return gfail(c, XSW_EINVAL, "grad_keep_f64: the threshold is NaN");
+    KeepTest<double> test;
+    test.thr = threshold;
+    return grad_keep<double>(c, "grad_keep_f64", lines, samples, mem, src, test, block, and_with, out);
+}
+
+extern "C" int xsw_grad_keep_u8(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, const uint8_t *src, int32_t block, const uint8_t *and_with,
+                                uint8_t *out)
+{
+    if (!c) return XSW_EINVAL;
+    return grad_keep<uint8_t>(c, "grad_keep_u8", lines, samples, mem, src, KeepTest<uint8_t>(), block, and_with, out);
 }
 
 extern "C" int xsw_grad_r2_sqrt(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, const void *sigma0, double *out)

@@ -3,7 +3,9 @@
     sigma0 -> [f x f box mean] -> ampl = sqrt(R2(sigma0)) -> local_gradients(ampl) -> per-window gradient_histogram
 
 and the rain / heterogeneity mask of the same module, `filtering_parameters(sigma0)` -> (f1, f2, f3, f4, F) in [0, 1] on the
-half-resolution grid, with its helpers `Mean` and `smoothing`.
+half-resolution grid, with its helpers `Mean` and `smoothing`.  `Gradients(..., min_F=, mask=)` applies it (and / or a user's
+mask on the sigma0 grid) to the histograms: a masked-out pixel of the local-gradients grid behaves exactly as a NaN G2 (`keep_mask`,
+`gradient_histogram(..., keep=)`); the reference computes F and stops there, so this step is this package's own.
 
 `Gradients(sigma0, windows_sizes, downscales_factors, window_step).histogram` is the notebook's entry point; `Gradients2D` is the
 mono-pol, single-window-size class it stacks.  The raster passes and the per-window histograms run in HIP kernels
@@ -22,7 +24,7 @@ import numpy as np
 from . import _device, _lib, options
 
 __all__ = ["Gradients", "Gradients2D", "GradientsHistogram", "local_gradients", "R2", "gradient_histogram", "circ_smooth",
-           "angles_bins", "filtering_parameters", "Mean", "smoothing"]
+           "angles_bins", "filtering_parameters", "Mean", "smoothing", "keep_mask"]
 
 
 def angles_bins(n_angles=72):
@@ -117,7 +119,7 @@ class _Call:
     def empty(self, shape, dtype):
         if self.device:
             tdt = {np.float32: self.torch.float32, np.float64: self.torch.float64, np.complex128: self.torch.complex128,
-                   np.int32: self.torch.int32}[np.dtype(dtype).type]
+                   np.int32: self.torch.int32, np.uint8: self.torch.uint8}[np.dtype(dtype).type]
             return self.torch.empty(tuple(shape), dtype=tdt, device=self.dev)
         return np.empty(shape, dtype)
 
@@ -192,10 +194,37 @@ def _local(ampl):
     return g2, g3, c
 
 
-def _hist(g2, c, window, rows, cols, n_angles, bins=None, normalise=True):
+def _u8_kind(a):
+    """'u8' for a bool / uint8 array (numpy or tensor), 'float' for a floating one; TypeError for anything else."""
+    name = str(a.dtype).replace("torch.", "")
+    if name in ("bool", "uint8"):
+        return "u8"
+    if name in ("float16", "bfloat16", "float32", "float64"):
+        return "float"
+    raise TypeError(f"a mask must be bool or uint8 (or floating, with a threshold), not {a.dtype}")
+
+
+def _as_u8(call, a):
+    """Contiguous uint8 array of the call's container kind from a bool / uint8 array (bool is reinterpreted, not converted)."""
+    if call.device:
+        t = _device.as_tensor(a, call.dev).contiguous()
+        return t.view(call.torch.uint8) if t.dtype == call.torch.bool else t
+    if _is_tensor(a):
+        a = a.cpu().numpy()
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint8) if a.dtype == np.bool_ else a
+
+
+def _hist(g2, c, window, rows, cols, n_angles, bins=None, normalise=True, keep=None):
     """Bin sums [rows, cols, n_angles] (divided by the window's pixel count with `normalise`, as an IEEE division on the device
-    whatever the route) and used ratios [rows, cols] of the windows centred at (rows[a], cols[b])."""
-    call = _Call(g2, c)
+    whatever the route) and used ratios [rows, cols] of the windows centred at (rows[a], cols[b]).  keep: bool / uint8 array of
+    g2's shape, 0 = the pixel behaves as a NaN g2 (xsw_grad_hist_masked); None: the unmasked kernel."""
+    if keep is not None:
+        if tuple(keep.shape) != tuple(np.shape(g2)):
+            raise ValueError(f"keep {tuple(keep.shape)} must have g2's shape {tuple(np.shape(g2))}")
+        if _u8_kind(keep) != "u8":
+            raise TypeError(f"keep must be bool or uint8, not {keep.dtype}")
+    call = _Call(g2, c, keep)
     g2, c = call.prep(g2, np.complex128), call.prep(c, np.float64)
     L, S = g2.shape
     if c.shape != g2.shape:
@@ -206,7 +235,12 @@ def _hist(g2, c, window, rows, cols, n_angles, bins=None, normalise=True):
     cols = call.prep(np.asarray(cols, dtype=np.int32), np.int32)
     nr, nc = rows.shape[0], cols.shape[0]
     weight, ratio = call.empty((nr, nc, len(bins)), np.float64), call.empty((nr, nc), np.float64)
-    if nr and nc:
+    if nr and nc and keep is not None:
+        keep = _as_u8(call, keep)
+        call.run(lambda ctx, mem: ctx.grad_hist_masked_raw(L, S, mem, call.ptr(g2), call.ptr(c), call.ptr(keep), int(wl), int(ws), nr,
+                                                           call.ptr(rows), nc, call.ptr(cols), len(bins), bins[0], bins[1] - bins[0],
+                                                           normalise, call.ptr(weight), call.ptr(ratio)), [g2, c, keep, rows, cols])
+    elif nr and nc:
         call.run(lambda ctx, mem: ctx.grad_hist_raw(L, S, mem, call.ptr(g2), call.ptr(c), int(wl), int(ws), nr, call.ptr(rows), nc,
                                                     call.ptr(cols), len(bins), bins[0], bins[1] - bins[0], normalise, call.ptr(weight),
                                                     call.ptr(ratio)), [g2, c, rows, cols])
@@ -306,41 +340,97 @@ def filtering_parameters(image_ori, line=None, sample=None):
     return FilteringParameters(out[0], out[1], out[2], out[3], out[4], coarsen_coords(r.line, 2), coarsen_coords(r.sample, 2))
 
 
-def _check_bins(call, g2, c, bins):
+def keep_mask(values, threshold=None, block=2, and_with=None):
+    """Reduce a 2-D raster to a uint8 keep mask by block x block blocks, the remainder trimmed: out[i, j] = 1 iff every input of
+    the block is usable (xsw_grad_keep_f64 / xsw_grad_keep_u8).  Floating `values` (widened to float64) need `threshold`: usable
+    iff x >= threshold, an IEEE comparison, so NaN is never usable.  bool / uint8 `values` take no threshold: usable iff
+    non-zero.  `and_with`: a bool / uint8 mask on the OUTPUT grid, AND-ed in.  The result, (lines // block, samples // block), is
+    of the input's container kind: numpy, or a device tensor computed on the caller's current stream.
+
+    block = 2 takes `filtering_parameters(sigma0).F` to the local-gradients grid of the same sigma0; block = 4 f takes a mask on
+    the sigma0 grid to the local-gradients grid at downscale factor f.  For a threshold on F see `Gradients`' `min_F`: F sits on
+    plateaus, choose the threshold between them."""
+    values = getattr(values, "values", values) if not _is_tensor(values) else values
+    if not _is_tensor(values):
+        values = np.asarray(values)
+    if len(values.shape) != 2:
+        raise ValueError(f"keep_mask needs a 2-D raster, not {len(values.shape)}-D")
+    kind = _u8_kind(values)
+    if kind == "float" and threshold is None:
+        raise ValueError("a floating raster needs a threshold (usable iff x >= threshold)")
+    if kind == "u8" and threshold is not None:
+        raise ValueError("a bool / uint8 raster takes no threshold (usable iff non-zero)")
+    if threshold is not None and np.isnan(float(threshold)):
+        raise ValueError("the threshold is NaN")
+    block = int(block)
+    if block < 1:
+        raise ValueError(f"block must be at least 1, not {block}")
+    L, S = (int(v) for v in values.shape)
+    Lo, So = L // block, S // block
+    if Lo < 1 or So < 1:
+        raise ValueError(f"a {L} x {S} raster has no {block} x {block} block")
+    if and_with is not None:
+        if tuple(and_with.shape) != (Lo, So):
+            raise ValueError(f"and_with {tuple(and_with.shape)} must be on the output grid ({Lo}, {So})")
+        if _u8_kind(and_with) != "u8":
+            raise TypeError(f"and_with must be bool or uint8, not {and_with.dtype}")
+    call = _Call(values, and_with)
+    x = call.prep(values, np.float64) if kind == "float" else _as_u8(call, values)
+    aw = None if and_with is None else _as_u8(call, and_with)
+    out = call.empty((Lo, So), np.uint8)
+    thr = None if kind == "u8" else float(threshold)
+    call.run(lambda ctx, mem: ctx.grad_keep_raw(L, S, mem, call.ptr(x), thr, block, None if aw is None else call.ptr(aw), call.ptr(out)),
+             [x] if aw is None else [x, aw])
+    return out
+
+
+def _check_bins(call, g2, c, bins, keep=None):
     """IndexError, as the reference's np.add.at raises it, when a pixel that would be summed falls outside numpy's index range
     -n .. n - 1 (bin n is the documented fold onto bin 0).  Only a g2 that is not a principal square root can do that (G2 from
-    local_gradients never does).  Device input: one synchronising check."""
+    local_gradients never does).  Pixels masked out by `keep` are not summed and cannot raise.  Device input: one synchronising
+    check."""
     n, start, step = len(bins), float(bins[0]), float(bins[1] - bins[0])
     if call.device:
         t = call.torch
         a, cc = g2.abs(), call.prep(c, np.float64)
         k = t.round((t.angle(g2) - start) / step)  # round half to even, as numpy's
         bad = t.isfinite(a) & (a > 0) & ~t.isnan(cc) & ((k > n) | (k < -n))
+        if keep is not None:
+            bad &= _as_u8(call, keep) != 0
         first = int(k[bad][0].item()) if bool(bad.any()) else None
     else:
         a, cc = np.abs(g2), np.asarray(c, dtype=np.float64)
         with np.errstate(invalid="ignore"):
             k = np.round((np.angle(g2) - start) / step)
             bad = np.isfinite(a) & (a > 0) & ~np.isnan(cc) & ((k > n) | (k < -n))
+        if keep is not None:
+            bad &= _as_u8(call, keep) != 0
         first = int(k[bad][0]) if bad.any() else None
     if first is not None:
         raise IndexError(f"index {first} is out of bounds for axis 0 with size {n}")
 
 
-def gradient_histogram(g2, c, angles_bins):
+def gradient_histogram(g2, c, angles_bins, keep=None):
     """Direction histogram of ONE box (gradients.py:828-879): (bin sums [len(angles_bins)], used ratio).  Each pixel whose |g2|
     is not NaN and > 0 adds |g2| / (|g2| + median|g2|) * c into bin rint((angle(g2) - angles_bins[0]) / step).  Bin
     len(angles_bins) (angle +pi/2) is folded onto bin 0 where the reference raises IndexError; any other index outside
-    numpy's range raises IndexError as the reference does."""
-    call = _Call(g2, c)
-    g2 = call.prep(g2, np.complex128)
-    if g2.ndim != 2:
+    numpy's range raises IndexError as the reference does.  keep (bool / uint8, g2's shape; this package's own): a pixel whose
+    keep is 0 behaves exactly as if its g2 were NaN -- not kept, outside the median, in no bin, not counted in the used ratio's
+    numerator (the denominator stays g2.size)."""
+    if len(np.shape(g2)) != 2:
         raise ValueError("g2 must be 2-D")
-    if np.shape(c) != tuple(g2.shape):
+    if np.shape(c) != tuple(np.shape(g2)):
         raise ValueError("g2 and c must have one shape")
-    _check_bins(call, g2, c, np.asarray(angles_bins, dtype=np.float64))
+    if keep is not None:
+        if tuple(keep.shape) != tuple(np.shape(g2)):
+            raise ValueError(f"keep {tuple(keep.shape)} must have g2's shape {tuple(np.shape(g2))}")
+        if _u8_kind(keep) != "u8":
+            raise TypeError(f"keep must be bool or uint8, not {keep.dtype}")
+    call = _Call(g2, c, keep)
+    g2 = call.prep(g2, np.complex128)
+    _check_bins(call, g2, c, np.asarray(angles_bins, dtype=np.float64), keep)
     L, S = g2.shape
-    weight, ratio = _hist(g2, c, (L, S), [L // 2], [S // 2], len(angles_bins), angles_bins, normalise=False)
+    weight, ratio = _hist(g2, c, (L, S), [L // 2], [S // 2], len(angles_bins), angles_bins, normalise=False, keep=keep)
     return weight[0, 0], ratio[0, 0]
 
 
@@ -389,10 +479,16 @@ class _Field:
 
     Device intermediates are computed on the stream current at their first use; an event recorded there after the launches
     makes the stream current at any later use wait for them (on the device: the host does not block), so the cached
-    tensors stay ordered when `.histogram` is called again from another stream."""
+    tensors stay ordered when `.histogram` is called again from another stream.
 
-    def __init__(self, values, line, sample, factor=1):
+    mask (on the ORIGINAL sigma0 grid, non-zero = usable) and min_F (threshold on this field's own filtering_parameters F) give
+    the field's keep mask on its local-gradients grid, cached and ordered like the local gradients."""
+
+    def __init__(self, values, line, sample, factor=1, mask=None, min_F=None):
         self._src, self.factor = values, factor
+        self._mask, self._min_F = _checked_mask(mask, values), _checked_min_F(min_F)
+        self._keep = None
+        self._keep_ev = None
         self.line = coarsen_coords(line, factor) if factor > 1 else np.asarray(line)
         self.sample = coarsen_coords(sample, factor) if factor > 1 else np.asarray(sample)
         self._values = values if factor == 1 else None
@@ -436,24 +532,81 @@ class _Field:
             self._consume(self._lg_ev, self._lg[0])
         return self._lg
 
+    @property
+    def keep(self):
+        """uint8 keep mask on the local-gradients grid (None without mask and min_F): the sigma0-grid mask reduced by
+        4 f x 4 f blocks, AND F >= min_F reduced by 2 x 2, F = filtering_parameters of this field's own raster."""
+        if self._mask is None and self._min_F is None:
+            return None
+        if self._keep is None:
+            k = None
+            if self._mask is not None:
+                m = self._mask
+                if _is_tensor(self._src) != _is_tensor(m):  # the mask follows sigma0's container kind
+                    m = _device.as_tensor(m, _device.device_of(self._src)) if _is_tensor(self._src) else m.cpu().numpy()
+                k = keep_mask(m, block=4 * self.factor)
+            if self._min_F is not None:
+                k = keep_mask(filtering_parameters(self.values).F, threshold=self._min_F, block=2, and_with=k)
+            self._keep = k
+            self._keep_ev = self._produced(k)
+        else:
+            self._consume(self._keep_ev, self._keep)
+        return self._keep
+
+
+def _checked_mask(mask, values):
+    """The user's mask as an array of sigma0's (line, sample) shape, or ValueError / TypeError: host checks only."""
+    if mask is None:
+        return None
+    if not _is_tensor(mask):
+        mask = np.asarray(getattr(mask, "values", mask))
+    if tuple(mask.shape) != tuple(values.shape[-2:]):
+        raise ValueError(f"mask {tuple(mask.shape)} must have sigma0's (line, sample) shape {tuple(values.shape[-2:])}")
+    if _u8_kind(mask) != "u8":
+        raise TypeError(f"mask must be bool or uint8 (non-zero = usable), not {mask.dtype}")
+    return mask
+
+
+def _checked_min_F(min_F):
+    if min_F is None:
+        return None
+    min_F = float(min_F)
+    if np.isnan(min_F):
+        raise ValueError("min_F is NaN")
+    return min_F
+
 
 class Gradients2D:
     """Direction histograms of a mono-pol (line, sample) sigma0 for one window size (gradients.py:45-205).
 
     window_size: in units of the coordinates (1600 = 16 km windows for 10 m coordinates, whatever sigma0's resolution);
     window_step: window stepping as a fraction of the window (1: no overlap); windows_at: dict(line=, sample=) of window centre
-    coordinates.  window_step and windows_at are mutually exclusive."""
+    coordinates.  window_step and windows_at are mutually exclusive.
 
-    def __init__(self, sigma0, window_size=1600, window_step=None, windows_at=None, line=None, sample=None):
+    mask / min_F (this package's own; the reference computes `filtering_parameters` and applies it nowhere) remove pixels of the
+    local-gradients grid from every window's histogram exactly as a NaN G2 would: they are not kept, stay out of the median of
+    |G2|, add to no bin and do not count in used_ratio's numerator (the denominator stays w * w), so `Streaks.resolve(
+    min_used_ratio=)` drops the windows they empty.  Their neighbours' gradients are untouched, unlike with NaN written into sigma0.
+      mask:  bool / uint8 array on sigma0's (line, sample) grid, non-zero = usable (land, ice, an external rain flag); a pixel
+             of the local-gradients grid is kept iff its whole 4 x 4 sigma0 block is usable.
+      min_F: float; kept iff `filtering_parameters(sigma0).F >= min_F` on the pixel's whole 2 x 2 block of the half-resolution
+             grid (NaN F: not kept).  There is no default.  Where the four filters saturate at 0 or 1, F takes exactly the
+             plateau values 0.5, sqrt(1/2), sqrt(3/4) and 1, on many pixels; a threshold ON a plateau is decided by rounding.
+             Choose min_F between plateaus (e.g. 0.3, 0.6, 0.7).
+    Both given: AND.  ValueError for a mask of another shape, before any device call."""
+
+    def __init__(self, sigma0, window_size=1600, window_step=None, windows_at=None, line=None, sample=None, mask=None, min_F=None):
         if window_step is not None and windows_at is not None:
             raise ValueError("window_step and window_at are mutually exclusive")
         if window_step is None and windows_at is None:
             window_step = 1
         if isinstance(sigma0, _Field):
+            if mask is not None or min_F is not None:
+                raise ValueError("a shared field carries its own mask / min_F")
             self._field = sigma0
         else:
             r = _Raster(sigma0, line, sample)
-            self._field = _Field(r.values, r.line, r.sample)
+            self._field = _Field(r.values, r.line, r.sample, mask=mask, min_F=min_F)
         self.window_size = window_size
         self.n_angles = 72
         """Bin angles count, in the range [-pi/2, pi/2] (can be changed)"""
@@ -486,7 +639,7 @@ class Gradients2D:
         if w < 1:
             raise ValueError(f"window_size {self.window_size} is smaller than one pixel of the local-gradients grid")
         rows, cols = nearest_indexer(lg_line, at_line), nearest_indexer(lg_sample, at_sample)
-        weight, ratio = _hist(g2, c, w, rows, cols, self.n_angles)
+        weight, ratio = _hist(g2, c, w, rows, cols, self.n_angles, keep=self._field.keep)
         return weight, ratio, at_line, at_sample
 
     @property
@@ -502,9 +655,15 @@ class Gradients:
 
     sigma0: (line, sample) or (pol, line, sample); windows_sizes: window sizes in coordinate units; downscales_factors: integer
     box-mean reductions of sigma0 (cv2 INTER_AREA); window_step: stepping of the FIRST (pol, factor, size) combination, whose
-    window centres every other combination uses."""
+    window centres every other combination uses.
 
-    def __init__(self, sigma0, windows_sizes=[1600], downscales_factors=[1], window_step=1, line=None, sample=None, pol=None):
+    mask / min_F: as in `Gradients2D`.  mask lies on the INPUT sigma0 grid (line, sample), one for all pols, and is reduced by
+    4 f x 4 f blocks for the field of downscale factor f; min_F thresholds the F of each (pol, factor) field's OWN raster (the
+    box-averaged sigma0 for f > 1), reduced by 2 x 2.  Each field computes its keep mask once, for all its window sizes.
+    Choose min_F between F's plateaus 0.5, sqrt(1/2), sqrt(3/4), 1 (e.g. 0.3, 0.6, 0.7)."""
+
+    def __init__(self, sigma0, windows_sizes=[1600], downscales_factors=[1], window_step=1, line=None, sample=None, pol=None,
+                 mask=None, min_F=None):
         r = _Raster(sigma0, line, sample, pol, allow_pol=True)
         self._drop_pol = not r.has_pol
         self.windows_sizes, self.downscales_factors = list(windows_sizes), list(downscales_factors)
@@ -513,7 +672,7 @@ class Gradients:
         self.gradients_list = []
         for plane in planes:
             for df in self.downscales_factors:
-                field = _Field(plane, r.line, r.sample, int(df))
+                field = _Field(plane, r.line, r.sample, int(df), mask=mask, min_F=min_F)
                 for ws in self.windows_sizes:
                     self.gradients_list.append(Gradients2D(field, window_size=ws))
         # the 1st gradient defines windows_at from window_step for all the others (StackedGradients, :208-245)
