@@ -31,9 +31,9 @@ def needs_build():
 
 
 def build(force=False, verbose=False):
-    """Compile csrc/*.hip -> libxsw.so for gfx950: seven translation units side by side (xsw.hip, the search kernels of each
-    dtype pair, the gradient-histogram kernels, the streak-direction kernels), then one link.  -ffp-contract=off: the kernels decide exact float64 orderings; FMAs appear only where
-    written explicitly."""
+    """Compile csrc/*.hip -> libxsw.so for gfx950: seven translation units side by side (xsw.hip, xsw_invert_tu.hip once per
+    dtype pair, xsw_gradients.hip, xsw_streaks.hip), then one link; skipped, unless `force`, when libxsw.so is the newest file.
+    -ffp-contract=off: the kernels decide exact float64 orderings; FMAs appear only where written explicitly."""
     if not force and not needs_build():
         return LIB
     cc = hipcc()

@@ -31,6 +31,52 @@ EXPORTS = (
 )
 
 
+# The raster entries behind xsarsea_amd.gradients and xsarsea_amd.streaks: their C signature after the context, one letter per
+# argument (l int64, i int32, d double, p pointer: an int address, device or host per `mem`, or None).  `load` sets the argtypes
+# from it and every row becomes a Context method, e.g. `grad_area_raw(lines, samples, factor, dtype, mem, in_ptr, out_ptr)`.
+RASTER_ENTRIES = {
+    # (lines, samples, factor, dtype, mem, in, out): f x f box mean, output of the input's dtype
+    "xsw_grad_area": "lliiipp",
+    # (lines, samples, dtype, mem, take_sqrt, in, out): R2 (or sqrt(R2) with take_sqrt) -> float64 (lines // 2, samples // 2)
+    "xsw_grad_r2": "lliiipp",
+    # (lines, samples, mem, ampl, g2, g3, c): float64 ampl -> G2 (complex128), G3, c on the (lines // 2, samples // 2) grid
+    "xsw_grad_local": "llipppp",
+    # (lines, samples, mem, g2, c, window_lines, window_samples, n_rows, rows, n_cols, cols, n_angles, angle_start, angle_step,
+    # normalise, weight, ratio): per-window bin sums (divided by the window's pixel count with `normalise`) and used ratios
+    # (rows / cols: int32 window-centre indices)
+    "xsw_grad_hist": "llippiiipipiddipp",
+    # (lines, samples, dtype, mem, in, out): R2(sqrt(sigma0)) -> float64 (lines // 2, samples // 2)
+    "xsw_grad_r2_sqrt": "lliipp",
+    # (lines, samples, dtype, mem, in, g2, g3, c): local_gradients(sqrt(sigma0)); g2 None skips G2
+    "xsw_grad_local_sqrt": "lliipppp",
+    # (lines, samples, mem, coarsen, in, out): 3x3 B2 "symm" smoothing of `in` or, with coarsen, of its NaN-skipping 2 x 2 mean
+    "xsw_grad_smooth": "lliipp",
+    # (lines, samples, mem, in, out): Mean (B4 then B42, "symm") of a float64 raster
+    "xsw_grad_mean": "llipp",
+    # (lines, samples, mem, r2, g3, c, smooth4, out): (f1, f2, f3, f4, F) as [5, lines, samples] on the half-resolution grid
+    "xsw_grad_filter": "llippppp",
+    # xsw_grad_hist with a uint8 keep mask on the g2 grid after c (0 = the pixel behaves as a NaN g2)
+    "xsw_grad_hist_masked": "llipppiiipipiddipp",
+    # (lines, samples, mem, src, threshold, block, and_with, out): float64 src, usable iff >= threshold, reduced by block x
+    # block blocks to a uint8 keep mask; and_with (None: absent) is AND-ed in
+    "xsw_grad_keep_f64": "llipdipp",
+    # (lines, samples, mem, src, block, and_with, out): the same for a uint8 src, usable iff non-zero
+    "xsw_grad_keep_u8": "llipipp",
+    # (n_lead, n_windows, n_angles, mem, smooth, weight, ratio, index, weight_out, ratio_out): mean over the leading axes,
+    # circular smoothing, peak bin of every window
+    "xsw_streaks_peak": "lliiippppp",
+    # (n_windows, mem, dirs, weight, ratio, anc, min_weight, min_used_ratio, out): the windows' unit vectors with the 180 degree
+    # ambiguity removed (NaN thresholds: off)
+    "xsw_streaks_resolve": "lippppddp",
+    # (lines, samples, mem, anc, n_rows, n_cols, dirs, line_first, line_t, sample_first, sample_t, out): the complex128 a-priori
+    # raster from the resolved window directions
+    "xsw_streaks_ancillary": "llipiipppppp",
+}
+assert list(RASTER_ENTRIES) == [n for n in EXPORTS if n.startswith(("xsw_grad_", "xsw_streaks_"))]
+# letter -> (ctypes type, conversion the wrapper applies: ctypes alone refuses numpy scalars)
+_SIG = {"l": (ctypes.c_int64, int), "i": (ctypes.c_int32, int), "d": (ctypes.c_double, float), "p": (ctypes.c_void_p, lambda a: a)}
+
+
 class XswError(RuntimeError):
     pass
 
@@ -144,29 +190,8 @@ def load():
         lib.xsw_host_alloc.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
         lib.xsw_host_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         lib.xsw_set_host_threads.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        lib.xsw_grad_area.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 2
-        lib.xsw_grad_r2.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 2
-        lib.xsw_grad_local.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 4
-        lib.xsw_grad_hist.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                      ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-        lib.xsw_grad_hist_masked.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 3 + \
-            [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-             ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-        lib.xsw_grad_keep_f64.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_double,
-                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-        lib.xsw_grad_keep_u8.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                         ctypes.c_void_p, ctypes.c_void_p]
-        lib.xsw_grad_r2_sqrt.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 2
-        lib.xsw_grad_local_sqrt.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 4
-        lib.xsw_grad_smooth.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 2
-        lib.xsw_grad_mean.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 2
-        lib.xsw_grad_filter.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 5
-        lib.xsw_streaks_peak.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 5
-        lib.xsw_streaks_resolve.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 4 + [ctypes.c_double] * 2 + \
-            [ctypes.c_void_p]
-        lib.xsw_streaks_ancillary.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                              ctypes.c_int32] + [ctypes.c_void_p] * 6
+        for name, sig in RASTER_ENTRIES.items():
+            getattr(lib, name).argtypes = [ctypes.c_void_p] + [_SIG[k][0] for k in sig]
         if lib.xsw_version() != ABI_VERSION:
             raise XswError(f"{_build.LIB} is version {lib.xsw_version()}, this package binds version {ABI_VERSION}: rebuild it")
         _cdll = lib
@@ -534,111 +559,13 @@ class Context:
                                   noise.ctypes.data, inc.ctypes.data, out.ctypes.data)
         return out
 
-    # ---- wind-streak direction histograms (xsarsea_amd.gradients).  Pointers are ints (device or host addresses per `mem`).
-    @_locked
-    def grad_area_raw(self, lines, samples, factor, dtype, mem, in_ptr, out_ptr):
-        """Thin call of xsw_grad_area: f x f box mean, output of the input's dtype."""
-        self._check(self._lib.xsw_grad_area(self._h, int(lines), int(samples), int(factor), dtype, mem, ctypes.c_void_p(in_ptr),
-                                            ctypes.c_void_p(out_ptr)), "xsw_grad_area")
-
-    @_locked
-    def grad_r2_raw(self, lines, samples, dtype, mem, take_sqrt, in_ptr, out_ptr):
-        """Thin call of xsw_grad_r2: R2 (or sqrt(R2) with take_sqrt) -> float64 (lines // 2, samples // 2)."""
-        self._check(self._lib.xsw_grad_r2(self._h, int(lines), int(samples), dtype, mem, int(bool(take_sqrt)), ctypes.c_void_p(in_ptr),
-                                          ctypes.c_void_p(out_ptr)), "xsw_grad_r2")
-
-    @_locked
-    def grad_local_raw(self, lines, samples, mem, ampl_ptr, g2_ptr, g3_ptr, c_ptr):
-        """Thin call of xsw_grad_local: float64 ampl -> G2 (complex128), G3, c on the (lines // 2, samples // 2) grid."""
-        self._check(self._lib.xsw_grad_local(self._h, int(lines), int(samples), mem, ctypes.c_void_p(ampl_ptr), ctypes.c_void_p(g2_ptr),
-                                             ctypes.c_void_p(g3_ptr), ctypes.c_void_p(c_ptr)), "xsw_grad_local")
-
-    @_locked
-    def grad_hist_raw(self, lines, samples, mem, g2_ptr, c_ptr, window_lines, window_samples, n_rows, rows_ptr, n_cols, cols_ptr,
-                      n_angles, angle_start, angle_step, normalise, weight_ptr, ratio_ptr):
-        """Thin call of xsw_grad_hist: per-window bin sums (divided by the window's pixel count with `normalise`) and used ratios
-        (rows / cols: int32 window-centre indices)."""
-        self._check(self._lib.xsw_grad_hist(self._h, int(lines), int(samples), mem, ctypes.c_void_p(g2_ptr), ctypes.c_void_p(c_ptr),
-                                            int(window_lines), int(window_samples), int(n_rows), ctypes.c_void_p(rows_ptr), int(n_cols), ctypes.c_void_p(cols_ptr),
-                                            int(n_angles), float(angle_start), float(angle_step), int(bool(normalise)), ctypes.c_void_p(weight_ptr),
-                                            ctypes.c_void_p(ratio_ptr)), "xsw_grad_hist")
-
-    @_locked
-    def grad_hist_masked_raw(self, lines, samples, mem, g2_ptr, c_ptr, keep_ptr, window_lines, window_samples, n_rows, rows_ptr, n_cols,
-                             cols_ptr, n_angles, angle_start, angle_step, normalise, weight_ptr, ratio_ptr):
-        """Thin call of xsw_grad_hist_masked: xsw_grad_hist with a uint8 keep mask on the g2 grid (0 = the pixel behaves as a NaN g2)."""
-        self._check(self._lib.xsw_grad_hist_masked(self._h, int(lines), int(samples), mem, ctypes.c_void_p(g2_ptr), ctypes.c_void_p(c_ptr),
-                                                   ctypes.c_void_p(keep_ptr), int(window_lines), int(window_samples), int(n_rows),
-                                                   ctypes.c_void_p(rows_ptr), int(n_cols), ctypes.c_void_p(cols_ptr), int(n_angles),
-                                                   float(angle_start), float(angle_step), int(bool(normalise)), ctypes.c_void_p(weight_ptr),
-                                                   ctypes.c_void_p(ratio_ptr)), "xsw_grad_hist_masked")
-
     @_locked
     def grad_keep_raw(self, lines, samples, mem, src_ptr, threshold, block, and_with_ptr, out_ptr):
-        """Thin call of xsw_grad_keep_f64 (float64 src, usable iff >= threshold) or, with threshold None, xsw_grad_keep_u8 (uint8
-        src, usable iff non-zero): block x block reduction to a uint8 keep mask; and_with_ptr (None: absent) is AND-ed in."""
+        """xsw_grad_keep_f64 or, with threshold None, xsw_grad_keep_u8 (RASTER_ENTRIES)."""
         if threshold is None:
-            rc = self._lib.xsw_grad_keep_u8(self._h, int(lines), int(samples), mem, ctypes.c_void_p(src_ptr), int(block),
-                                            ctypes.c_void_p(and_with_ptr), ctypes.c_void_p(out_ptr))
+            self.grad_keep_u8_raw(lines, samples, mem, src_ptr, block, and_with_ptr, out_ptr)
         else:
-            rc = self._lib.xsw_grad_keep_f64(self._h, int(lines), int(samples), mem, ctypes.c_void_p(src_ptr), float(threshold), int(block),
-                                             ctypes.c_void_p(and_with_ptr), ctypes.c_void_p(out_ptr))
-        self._check(rc, "xsw_grad_keep_u8" if threshold is None else "xsw_grad_keep_f64")
-
-    @_locked
-    def grad_r2_sqrt_raw(self, lines, samples, dtype, mem, in_ptr, out_ptr):
-        """Thin call of xsw_grad_r2_sqrt: R2(sqrt(sigma0)) -> float64 (lines // 2, samples // 2)."""
-        self._check(self._lib.xsw_grad_r2_sqrt(self._h, int(lines), int(samples), dtype, mem, ctypes.c_void_p(in_ptr),
-                                               ctypes.c_void_p(out_ptr)), "xsw_grad_r2_sqrt")
-
-    @_locked
-    def grad_local_sqrt_raw(self, lines, samples, dtype, mem, in_ptr, g2_ptr, g3_ptr, c_ptr):
-        """Thin call of xsw_grad_local_sqrt: local_gradients(sqrt(sigma0)); g2_ptr None skips G2."""
-        self._check(self._lib.xsw_grad_local_sqrt(self._h, int(lines), int(samples), dtype, mem, ctypes.c_void_p(in_ptr),
-                                                  ctypes.c_void_p(g2_ptr), ctypes.c_void_p(g3_ptr), ctypes.c_void_p(c_ptr)),
-                    "xsw_grad_local_sqrt")
-
-    @_locked
-    def grad_smooth_raw(self, lines, samples, mem, coarsen, in_ptr, out_ptr):
-        """Thin call of xsw_grad_smooth: 3x3 B2 "symm" smoothing of `in` or, with coarsen, of its NaN-skipping 2 x 2 mean."""
-        self._check(self._lib.xsw_grad_smooth(self._h, int(lines), int(samples), mem, int(bool(coarsen)), ctypes.c_void_p(in_ptr),
-                                              ctypes.c_void_p(out_ptr)), "xsw_grad_smooth")
-
-    @_locked
-    def grad_mean_raw(self, lines, samples, mem, in_ptr, out_ptr):
-        """Thin call of xsw_grad_mean: Mean (B4 then B42, "symm") of a float64 raster."""
-        self._check(self._lib.xsw_grad_mean(self._h, int(lines), int(samples), mem, ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr)),
-                    "xsw_grad_mean")
-
-    @_locked
-    def grad_filter_raw(self, lines, samples, mem, r2_ptr, g3_ptr, c_ptr, smooth4_ptr, out_ptr):
-        """Thin call of xsw_grad_filter: (f1, f2, f3, f4, F) as [5, lines, samples] on the half-resolution grid."""
-        self._check(self._lib.xsw_grad_filter(self._h, int(lines), int(samples), mem, ctypes.c_void_p(r2_ptr), ctypes.c_void_p(g3_ptr),
-                                              ctypes.c_void_p(c_ptr), ctypes.c_void_p(smooth4_ptr), ctypes.c_void_p(out_ptr)), "xsw_grad_filter")
-
-    # ---- streak directions -> a-priori wind raster (xsarsea_amd.streaks).  Pointers are ints (device or host addresses per `mem`).
-    @_locked
-    def streaks_peak_raw(self, n_lead, n_windows, n_angles, mem, smooth, weight_ptr, ratio_ptr, index_ptr, weight_out_ptr, ratio_out_ptr):
-        """Thin call of xsw_streaks_peak: mean over the leading axes, circular smoothing, peak bin of every window."""
-        self._check(self._lib.xsw_streaks_peak(self._h, int(n_lead), int(n_windows), int(n_angles), mem, int(bool(smooth)),
-                                               ctypes.c_void_p(weight_ptr), ctypes.c_void_p(ratio_ptr), ctypes.c_void_p(index_ptr),
-                                               ctypes.c_void_p(weight_out_ptr), ctypes.c_void_p(ratio_out_ptr)), "xsw_streaks_peak")
-
-    @_locked
-    def streaks_resolve_raw(self, n_windows, mem, dirs_ptr, weight_ptr, ratio_ptr, anc_ptr, min_weight, min_used_ratio, out_ptr):
-        """Thin call of xsw_streaks_resolve: the windows' unit vectors with the 180 degree ambiguity removed (NaN thresholds: off)."""
-        self._check(self._lib.xsw_streaks_resolve(self._h, int(n_windows), mem, ctypes.c_void_p(dirs_ptr), ctypes.c_void_p(weight_ptr),
-                                                  ctypes.c_void_p(ratio_ptr), ctypes.c_void_p(anc_ptr), float(min_weight), float(min_used_ratio),
-                                                  ctypes.c_void_p(out_ptr)), "xsw_streaks_resolve")
-
-    @_locked
-    def streaks_ancillary_raw(self, lines, samples, mem, anc_ptr, n_rows, n_cols, dirs_ptr, line_first_ptr, line_t_ptr, sample_first_ptr,
-                              sample_t_ptr, out_ptr):
-        """Thin call of xsw_streaks_ancillary: the complex128 a-priori raster from the resolved window directions."""
-        self._check(self._lib.xsw_streaks_ancillary(self._h, int(lines), int(samples), mem, ctypes.c_void_p(anc_ptr), int(n_rows), int(n_cols),
-                                                    ctypes.c_void_p(dirs_ptr), ctypes.c_void_p(line_first_ptr), ctypes.c_void_p(line_t_ptr),
-                                                    ctypes.c_void_p(sample_first_ptr), ctypes.c_void_p(sample_t_ptr), ctypes.c_void_p(out_ptr)),
-                    "xsw_streaks_ancillary")
+            self.grad_keep_f64_raw(lines, samples, mem, src_ptr, threshold, block, and_with_ptr, out_ptr)
 
     @_locked
     def detrend_raw(self, lines, samples, dtype, out_dtype, mem, sigma0_ptr, ratio_row, out_ptr):
@@ -662,6 +589,23 @@ class Context:
                                           XSW_F32 if out.dtype == np.float32 else XSW_F64, MEM_HOST,
                                           _ptr(sigma0), _ptr(ratio_row), _ptr(out)), "xsw_detrend")
         return out
+
+
+
+def _raw_method(name, sig):
+    convert = [_SIG[k][1] for k in sig]
+
+    def method(self, *args):
+        if len(args) != len(convert):
+            raise TypeError(f"{name} takes {len(convert)} arguments after the context, not {len(args)}")
+        self._check(getattr(self._lib, name)(self._h, *[f(a) for f, a in zip(convert, args)]), name)
+    method.__name__ = name[len("xsw_"):] + "_raw"
+    method.__doc__ = f"Thin call of {name}: see RASTER_ENTRIES for the arguments."
+    return _locked(method)
+
+
+for _name, _sig in RASTER_ENTRIES.items():
+    setattr(Context, _name[len("xsw_"):] + "_raw", _raw_method(_name, _sig))
 
 
 _default_ctx = {}

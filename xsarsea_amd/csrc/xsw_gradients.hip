@@ -1,5 +1,5 @@
 // Wind-streak direction histograms (Koch 2004; reference: src/xsarsea/gradients.py): the kernels behind
-// xsarsea_amd.gradients and their C ABI (xsw_grad_area / xsw_grad_r2 / xsw_grad_local / xsw_grad_hist, include/xsw.h).
+// xsarsea_amd.gradients and their C ABI (the twelve xsw_grad_* entries of include/xsw.h, at the end of this file).
 //
 //   k_grad_area   f x f box mean (cv2.resize INTER_AREA at an integer factor, Gradients._sigma0_resample :343-367)
 //   k_grad_r2     R2 (:689-722): 5x5 B4 "symm" convolution, 2x2 NaN-skipping mean, 3x3 B2 "symm" convolution, optional sqrt;
@@ -737,46 +737,101 @@ extern "C" int xsw_grad_area(xsw_ctx *c, int64_t lines, int64_t samples, int32_t
     }, "grad_area");
 }
 
-extern "C" int xsw_grad_r2(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, int32_t take_sqrt, const void *in,
-                           double *out)
+// xsw_grad_r2 (SQ false: take_sqrt roots the result) and xsw_grad_r2_sqrt (SQ true: the kernel roots sigma0 on load).  SQ is a
+// template flag so that each entry instantiates its own kernels where it stands, as it did: their order in the code object.
+template <bool SQ>
+static int grad_r2(xsw_ctx *c, const char *what, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, int32_t take_sqrt,
+                   const void *in, double *out)
 {
     if (!c) return XSW_EINVAL;
-    if (!in || !out || lines < 2 || samples < 2) return gfail(c, XSW_EINVAL, "grad_r2: bad argument (the raster needs 2 x 2 pixels)");
-    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_r2: raster too large");
+    if (!in || !out || lines < 2 || samples < 2) return gfail(c, XSW_EINVAL, "%s: bad argument (the raster needs 2 x 2 pixels)", what);
+    if (int rc = check_dims(c, what, lines, samples)) return rc;
     if (dtype != XSW_F32 && dtype != XSW_F64) return gfail(c, XSW_EINVAL, "dtype must be XSW_F32 or XSW_F64");
     if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
-    const int L1 = (int)lines, S1 = (int)samples, L2 = L1 / 2, S2 = S1 / 2;
+    const int L1 = (int)lines, S1 = (int)samples, L2 = L1 / 2, S2 = S1 / 2, root = (int)(take_sqrt != 0);
     const long long es = dtype == XSW_F32 ? 4 : 8;
     Buf b[2] = {{in, nullptr, (size_t)(lines * samples * es)}, {nullptr, out, (size_t)L2 * S2 * 8}};
     const dim3 grid((S2 + TILE - 1) / TILE, (L2 + TILE - 1) / TILE);
-    if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_r2: raster too large for one launch");
+    if (int rc = check_grid(c, what, grid)) return rc;
     return run(c, mem, b, [&](Buf (&x)[2]) {
         if (dtype == XSW_F32)
-            hipLaunchKernelGGL((k_grad_r2<float, false>), grid, dim3(256), 0, c->stream, (const float *)x[0].dev, (double *)x[1].dev, L1, S1, L2, S2,
-                               (int)(take_sqrt != 0));
+            hipLaunchKernelGGL((k_grad_r2<float, SQ>), grid, dim3(256), 0, c->stream, (const float *)x[0].dev, (double *)x[1].dev, L1, S1, L2, S2,
+                               root);
         else
-            hipLaunchKernelGGL((k_grad_r2<double, false>), grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double *)x[1].dev, L1, S1, L2,
-                               S2, (int)(take_sqrt != 0));
-    }, "grad_r2");
+            hipLaunchKernelGGL((k_grad_r2<double, SQ>), grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double *)x[1].dev, L1, S1, L2, S2,
+                               root);
+    }, what);
+}
+
+extern "C" int xsw_grad_r2(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, int32_t take_sqrt, const void *in,
+                           double *out)
+{
+    return grad_r2<false>(c, "grad_r2", lines, samples, dtype, mem, take_sqrt, in, out);
+}
+
+// xsw_grad_local (SQ false: float64 ampl, g2 required) and xsw_grad_local_sqrt (SQ true: sqrt(sigma0) on load, g2 optional).
+template <bool SQ>
+static int grad_local(xsw_ctx *c, const char *what, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, const void *in,
+                      double *g2, double *g3, double *quality)
+{
+    if (!c) return XSW_EINVAL;
+    if (!in || (!g2 && !SQ) || !g3 || !quality || lines < 2 || samples < 2)
+        return gfail(c, XSW_EINVAL, "%s: bad argument (the raster needs 2 x 2 pixels)", what);
+    if (int rc = check_dims(c, what, lines, samples)) return rc;
+    if (dtype != XSW_F32 && dtype != XSW_F64) return gfail(c, XSW_EINVAL, "dtype must be XSW_F32 or XSW_F64");
+    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    const int L1 = (int)lines, S1 = (int)samples, L2 = L1 / 2, S2 = S1 / 2;
+    const size_t no = (size_t)L2 * S2;
+    const long long es = dtype == XSW_F32 ? 4 : 8;
+    Buf b[4] = {{in, nullptr, (size_t)(lines * samples * es)}, {nullptr, g3, no * 8}, {nullptr, quality, no * 8}, {nullptr, g2, g2 ? no * 16 : 0}};
+    const dim3 grid((S2 + TILE - 1) / TILE, (L2 + TILE - 1) / TILE);
+    if (int rc = check_grid(c, what, grid)) return rc;
+    return run(c, mem, b, [&](Buf (&x)[4]) {
+        double2 *pg2 = g2 ? (double2 *)x[3].dev : nullptr;
+        double *pg3 = (double *)x[1].dev, *pq = (double *)x[2].dev;
+        if constexpr (SQ) {  // xsw_grad_local takes float64 only: there is no k_grad_local<float, false>
+            if (dtype == XSW_F32) {
+                hipLaunchKernelGGL((k_grad_local<float, true>), grid, dim3(256), 0, c->stream, (const float *)x[0].dev, pg2, pg3, pq, L1, S1, L2, S2);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((k_grad_local<double, SQ>), grid, dim3(256), 0, c->stream, (const double *)x[0].dev, pg2, pg3, pq, L1, S1, L2, S2);
+    }, what);
 }
 
 extern "C" int xsw_grad_local(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, const double *ampl, double *g2, double *g3,
                               double *quality)
 {
-    if (!c) return XSW_EINVAL;
-    if (!ampl || !g2 || !g3 || !quality || lines < 2 || samples < 2)
-        return gfail(c, XSW_EINVAL, "grad_local: bad argument (the raster needs 2 x 2 pixels)");
-    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_local: raster too large");
+    return grad_local<false>(c, "grad_local", lines, samples, XSW_F64, mem, ampl, g2, g3, quality);
+}
+
+// xsw_grad_hist (keep nullptr: k_grad_hist) and xsw_grad_hist_masked (k_grad_hist_masked).
+static int grad_hist(xsw_ctx *c, const char *what, int64_t lines, int64_t samples, int32_t mem, const double *g2, const double *quality,
+                     const uint8_t *keep, int32_t window_lines, int32_t window_samples, int32_t n_rows, const int32_t *rows, int32_t n_cols,
+                     const int32_t *cols, int32_t n_angles, double angle_start, double angle_step, int32_t normalise, double *weight,
+                     double *used_ratio)
+{
+    if (!g2 || !quality || !rows || !cols || !weight || !used_ratio || lines < 1 || samples < 1 || window_lines < 1 || window_samples < 1 || n_rows < 1 ||
+        n_cols < 1 || n_angles < 1)
+        return gfail(c, XSW_EINVAL, "%s: bad argument", what);
+    if (!fits_int(lines, samples) || !fits_int(std::min<long long>(window_lines, lines) * std::min<long long>(window_samples, samples)))
+        return gfail(c, XSW_EINVAL, "%s: raster or window too large", what);
+    if (!fits_int((long long)n_rows * n_cols)) return gfail(c, XSW_EINVAL, "%s: too many windows", what);
     if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
-    const int L1 = (int)lines, S1 = (int)samples, L2 = L1 / 2, S2 = S1 / 2;
-    const size_t no = (size_t)L2 * S2;
-    Buf b[4] = {{ampl, nullptr, (size_t)(lines * samples * 8)}, {nullptr, g2, no * 16}, {nullptr, g3, no * 8}, {nullptr, quality, no * 8}};
-    const dim3 grid((S2 + TILE - 1) / TILE, (L2 + TILE - 1) / TILE);
-    if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_local: raster too large for one launch");
-    return run(c, mem, b, [&](Buf (&x)[4]) {
-        hipLaunchKernelGGL((k_grad_local<double, false>), grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double2 *)x[1].dev, (double *)x[2].dev,
-                           (double *)x[3].dev, L1, S1, L2, S2);
-    }, "grad_local");
+    const size_t npx = (size_t)lines * samples, nw = (size_t)n_rows * n_cols;
+    Buf b[7] = {{g2, nullptr, npx * 16}, {quality, nullptr, npx * 8}, {rows, nullptr, (size_t)n_rows * 4}, {cols, nullptr, (size_t)n_cols * 4},
+                {nullptr, weight, nw * n_angles * 8}, {nullptr, used_ratio, nw * 8}, {keep, nullptr, keep ? npx : 0}};
+    return run(c, mem, b, [&](Buf (&x)[7]) {
+        if (keep)
+            hipLaunchKernelGGL(k_grad_hist_masked, dim3((unsigned)nw), dim3(HIST_THREADS), 0, c->stream, (const double2 *)x[0].dev, (const double *)x[1].dev,
+                               (const uint8_t *)x[6].dev, (int)lines, (int)samples, (int)window_lines, (int)window_samples, (const int *)x[2].dev, (int)n_rows,
+                               (const int *)x[3].dev, (int)n_cols, (int)n_angles, angle_start, angle_step, (int)(normalise != 0), (double *)x[4].dev,
+                               (double *)x[5].dev);
+        else
+            hipLaunchKernelGGL(k_grad_hist, dim3((unsigned)nw), dim3(HIST_THREADS), 0, c->stream, (const double2 *)x[0].dev, (const double *)x[1].dev,
+                               (int)lines, (int)samples, (int)window_lines, (int)window_samples, (const int *)x[2].dev, (int)n_rows, (const int *)x[3].dev,
+                               (int)n_cols, (int)n_angles, angle_start, angle_step, (int)(normalise != 0), (double *)x[4].dev, (double *)x[5].dev);
+    }, what);
 }
 
 extern "C" int xsw_grad_hist(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, const double *g2, const double *quality,
@@ -785,21 +840,8 @@ extern "C" int xsw_grad_hist(xsw_ctx *c, int64_t lines, int64_t samples, int32_t
                              double *weight, double *used_ratio)
 {
     if (!c) return XSW_EINVAL;
-    if (!g2 || !quality || !rows || !cols || !weight || !used_ratio || lines < 1 || samples < 1 || window_lines < 1 || window_samples < 1 || n_rows < 1 ||
-        n_cols < 1 || n_angles < 1)
-        return gfail(c, XSW_EINVAL, "grad_hist: bad argument");
-    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL || std::min<long long>(window_lines, lines) * std::min<long long>(window_samples, samples) > 0x7fffffffLL)
-        return gfail(c, XSW_EINVAL, "grad_hist: raster or window too large");
-    if ((long long)n_rows * n_cols > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_hist: too many windows");
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
-    const size_t npx = (size_t)lines * samples, nw = (size_t)n_rows * n_cols;
-    Buf b[6] = {{g2, nullptr, npx * 16}, {quality, nullptr, npx * 8}, {rows, nullptr, (size_t)n_rows * 4}, {cols, nullptr, (size_t)n_cols * 4},
-                {nullptr, weight, nw * n_angles * 8}, {nullptr, used_ratio, nw * 8}};
-    return run(c, mem, b, [&](Buf (&x)[6]) {
-        hipLaunchKernelGGL(k_grad_hist, dim3((unsigned)nw), dim3(HIST_THREADS), 0, c->stream, (const double2 *)x[0].dev, (const double *)x[1].dev,
-                           (int)lines, (int)samples, (int)window_lines, (int)window_samples, (const int *)x[2].dev, (int)n_rows, (const int *)x[3].dev, (int)n_cols,
-                           (int)n_angles, angle_start, angle_step, (int)(normalise != 0), (double *)x[4].dev, (double *)x[5].dev);
-    }, "grad_hist");
+    return grad_hist(c, "grad_hist", lines, samples, mem, g2, quality, nullptr, window_lines, window_samples, n_rows, rows, n_cols, cols, n_angles,
+                     angle_start, angle_step, normalise, weight, used_ratio);
 }
 
 extern "C" int xsw_grad_hist_masked(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, const double *g2, const double *quality,
@@ -809,22 +851,8 @@ extern "C" int xsw_grad_hist_masked(xsw_ctx *c, int64_t lines, int64_t samples, 
 {
     if (!c) return XSW_EINVAL;
     if (!keep) return gfail(c, XSW_EINVAL, "grad_hist_masked: keep is NULL (the unmasked histogram is xsw_grad_hist)");
-    if (!g2 || !quality || !rows || !cols || !weight || !used_ratio || lines < 1 || samples < 1 || window_lines < 1 || window_samples < 1 || n_rows < 1 ||
-        n_cols < 1 || n_angles < 1)
-        return gfail(c, XSW_EINVAL, "grad_hist_masked: bad argument");
-    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL || std::min<long long>(window_lines, lines) * std::min<long long>(window_samples, samples) > 0x7fffffffLL)
-        return gfail(c, XSW_EINVAL, "grad_hist_masked: raster or window too large");
-    if ((long long)n_rows * n_cols > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_hist_masked: too many windows");
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
-    const size_t npx = (size_t)lines * samples, nw = (size_t)n_rows * n_cols;
-    Buf b[7] = {{g2, nullptr, npx * 16}, {quality, nullptr, npx * 8}, {rows, nullptr, (size_t)n_rows * 4}, {cols, nullptr, (size_t)n_cols * 4},
-                {nullptr, weight, nw * n_angles * 8}, {nullptr, used_ratio, nw * 8}, {keep, nullptr, npx}};
-    return run(c, mem, b, [&](Buf (&x)[7]) {
-        hipLaunchKernelGGL(k_grad_hist_masked, dim3((unsigned)nw), dim3(HIST_THREADS), 0, c->stream, (const double2 *)x[0].dev, (const double *)x[1].dev,
-                           (const uint8_t *)x[6].dev, (int)lines, (int)samples, (int)window_lines, (int)window_samples, (const int *)x[2].dev, (int)n_rows,
-                           (const int *)x[3].dev, (int)n_cols, (int)n_angles, angle_start, angle_step, (int)(normalise != 0), (double *)x[4].dev,
-                           (double *)x[5].dev);
-    }, "grad_hist_masked");
+    return grad_hist(c, "grad_hist_masked", lines, samples, mem, g2, quality, keep, window_lines, window_samples, n_rows, rows, n_cols, cols,
+                     n_angles, angle_start, angle_step, normalise, weight, used_ratio);
 }
 
 // One launch of k_grad_keep: the widest vector the block's row bytes, the raster's row bytes and the base address allow.
@@ -833,18 +861,14 @@ static int grad_keep(xsw_ctx *c, const char *what, int64_t lines, int64_t sample
                      const uint8_t *and_with, uint8_t *out)
 {
     if (!src || !out || block < 1 || lines < block || samples < block) return gfail(c, XSW_EINVAL, "%s: bad argument (block < 1 or an empty output)", what);
-    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "%s: raster too large", what);
+    if (int rc = check_dims(c, what, lines, samples)) return rc;
     if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
     const long long Lo = lines / block, So = samples / block, es = (long long)sizeof(T);
     const size_t no = (size_t)Lo * So;
     Buf b[3] = {{src, nullptr, (size_t)(lines * samples * es)}, {and_with, nullptr, and_with ? no : 0}, {nullptr, out, no}};
-    // the grid of k_detrend: about 16 workgroups per CU, each a 256-column strip of a block of output rows
-    const long long gx = (So + 255) / 256;
-    long long gy = (256LL * 16 + gx - 1) / gx;
-    gy = std::max<long long>(1, std::min<long long>(std::min<long long>(gy, Lo), 65535));
-    const long long rpb = (Lo + gy - 1) / gy;
-    gy = (Lo + rpb - 1) / rpb;
-    const dim3 grid((unsigned)gx, (unsigned)gy);
+    const Strips g = strip_grid(Lo, So);
+    const long long rpb = g.rows_per_block;
+    const dim3 grid((unsigned)g.gx, (unsigned)g.gy);
     return run(c, mem, b, [&](Buf (&x)[3]) {
         const T *in = (const T *)x[0].dev;
         const uint8_t *aw = and_with ? (const uint8_t *)x[1].dev : nullptr;
@@ -888,48 +912,13 @@ extern "C" int xsw_grad_keep_u8(xsw_ctx *c, int64_t lines, int64_t samples, int3
 
 extern "C" int xsw_grad_r2_sqrt(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, const void *sigma0, double *out)
 {
-    if (!c) return XSW_EINVAL;
-    if (!sigma0 || !out || lines < 2 || samples < 2) return gfail(c, XSW_EINVAL, "grad_r2_sqrt: bad argument (the raster needs 2 x 2 pixels)");
-    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_r2_sqrt: raster too large");
-    if (dtype != XSW_F32 && dtype != XSW_F64) return gfail(c, XSW_EINVAL, "dtype must be XSW_F32 or XSW_F64");
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
-    const int L1 = (int)lines, S1 = (int)samples, L2 = L1 / 2, S2 = S1 / 2;
-    const long long es = dtype == XSW_F32 ? 4 : 8;
-    Buf b[2] = {{sigma0, nullptr, (size_t)(lines * samples * es)}, {nullptr, out, (size_t)L2 * S2 * 8}};
-    const dim3 grid((S2 + TILE - 1) / TILE, (L2 + TILE - 1) / TILE);
-    if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_r2_sqrt: raster too large for one launch");
-    return run(c, mem, b, [&](Buf (&x)[2]) {
-        if (dtype == XSW_F32)
-            hipLaunchKernelGGL((k_grad_r2<float, true>), grid, dim3(256), 0, c->stream, (const float *)x[0].dev, (double *)x[1].dev, L1, S1, L2, S2, 0);
-        else
-            hipLaunchKernelGGL((k_grad_r2<double, true>), grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double *)x[1].dev, L1, S1, L2, S2, 0);
-    }, "grad_r2_sqrt");
+    return grad_r2<true>(c, "grad_r2_sqrt", lines, samples, dtype, mem, 0, sigma0, out);
 }
 
 extern "C" int xsw_grad_local_sqrt(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, const void *sigma0, double *g2,
                                    double *g3, double *quality)
 {
-    if (!c) return XSW_EINVAL;
-    if (!sigma0 || !g3 || !quality || lines < 2 || samples < 2)
-        return gfail(c, XSW_EINVAL, "grad_local_sqrt: bad argument (the raster needs 2 x 2 pixels)");
-    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_local_sqrt: raster too large");
-    if (dtype != XSW_F32 && dtype != XSW_F64) return gfail(c, XSW_EINVAL, "dtype must be XSW_F32 or XSW_F64");
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
-    const int L1 = (int)lines, S1 = (int)samples, L2 = L1 / 2, S2 = S1 / 2;
-    const size_t no = (size_t)L2 * S2;
-    const long long es = dtype == XSW_F32 ? 4 : 8;
-    Buf b[4] = {{sigma0, nullptr, (size_t)(lines * samples * es)}, {nullptr, g3, no * 8}, {nullptr, quality, no * 8}, {nullptr, g2, g2 ? no * 16 : 0}};
-    const dim3 grid((S2 + TILE - 1) / TILE, (L2 + TILE - 1) / TILE);
-    if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_local_sqrt: raster too large for one launch");
-    return run(c, mem, b, [&](Buf (&x)[4]) {
-        double2 *pg2 = g2 ? (double2 *)x[3].dev : nullptr;
-        if (dtype == XSW_F32)
-            hipLaunchKernelGGL((k_grad_local<float, true>), grid, dim3(256), 0, c->stream, (const float *)x[0].dev, pg2, (double *)x[1].dev,
-                               (double *)x[2].dev, L1, S1, L2, S2);
-        else
-            hipLaunchKernelGGL((k_grad_local<double, true>), grid, dim3(256), 0, c->stream, (const double *)x[0].dev, pg2, (double *)x[1].dev,
-                               (double *)x[2].dev, L1, S1, L2, S2);
-    }, "grad_local_sqrt");
+    return grad_local<true>(c, "grad_local_sqrt", lines, samples, dtype, mem, sigma0, g2, g3, quality);
 }
 
 extern "C" int xsw_grad_smooth(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, int32_t coarsen, const double *in, double *out)
@@ -937,12 +926,12 @@ extern "C" int xsw_grad_smooth(xsw_ctx *c, int64_t lines, int64_t samples, int32
     if (!c) return XSW_EINVAL;
     const int64_t f = coarsen ? 2 : 1;
     if (!in || !out || lines < f || samples < f) return gfail(c, XSW_EINVAL, "grad_smooth: bad argument");
-    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_smooth: raster too large");
+    if (int rc = check_dims(c, "grad_smooth", lines, samples)) return rc;
     if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
     const int S = (int)samples, Lo = (int)(lines / f), So = (int)(samples / f);
     Buf b[2] = {{in, nullptr, (size_t)(lines * samples * 8)}, {nullptr, out, (size_t)Lo * So * 8}};
     const dim3 grid((So + 63) / 64, (Lo + 3) / 4);
-    if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_smooth: raster too large for one launch");
+    if (int rc = check_grid(c, "grad_smooth", grid)) return rc;
     return run(c, mem, b, [&](Buf (&x)[2]) {
         if (coarsen)
             hipLaunchKernelGGL(k_grad_smooth<true>, grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double *)x[1].dev, S, Lo, So);
@@ -955,12 +944,12 @@ extern "C" int xsw_grad_mean(xsw_ctx *c, int64_t lines, int64_t samples, int32_t
 {
     if (!c) return XSW_EINVAL;
     if (!in || !out || lines < 1 || samples < 1) return gfail(c, XSW_EINVAL, "grad_mean: bad argument");
-    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_mean: raster too large");
+    if (int rc = check_dims(c, "grad_mean", lines, samples)) return rc;
     if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
     const int L = (int)lines, S = (int)samples;
     Buf b[2] = {{in, nullptr, (size_t)L * S * 8}, {nullptr, out, (size_t)L * S * 8}};
     const dim3 grid((S + MT - 1) / MT, (L + MT - 1) / MT);
-    if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_mean: raster too large for one launch");
+    if (int rc = check_grid(c, "grad_mean", grid)) return rc;
     return run(c, mem, b, [&](Buf (&x)[2]) {
         hipLaunchKernelGGL(k_grad_mean, grid, dim3(256), 0, c->stream, (const double *)x[0].dev, (double *)x[1].dev, L, S);
     }, "grad_mean");
@@ -972,13 +961,13 @@ extern "C" int xsw_grad_filter(xsw_ctx *c, int64_t lines, int64_t samples, int32
     if (!c) return XSW_EINVAL;
     if (!r2 || !g3 || !quality || !smooth4 || !out || lines < 2 || samples < 2)
         return gfail(c, XSW_EINVAL, "grad_filter: bad argument (the half-resolution raster needs 2 x 2 pixels)");
-    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "grad_filter: raster too large");
+    if (int rc = check_dims(c, "grad_filter", lines, samples)) return rc;
     if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
     const int L = (int)lines, S = (int)samples, L4 = L / 2, S4 = S / 2;
     const size_t n = (size_t)L * S;
     Buf b[5] = {{r2, nullptr, n * 8}, {g3, nullptr, n * 8}, {quality, nullptr, n * 8}, {smooth4, nullptr, (size_t)L4 * S4 * 8}, {nullptr, out, 5 * n * 8}};
     const dim3 grid((S + MT - 1) / MT, (L + MT - 1) / MT);
-    if (grid.y > 65535) return gfail(c, XSW_EINVAL, "grad_filter: raster too large for one launch");
+    if (int rc = check_grid(c, "grad_filter", grid)) return rc;
     // scipy's zoom factor of each axis, the same IEEE division
     const double zy = (double)(L4 - 1) / (double)(L - 1), zx = (double)(S4 - 1) / (double)(S - 1);
     return run(c, mem, b, [&](Buf (&x)[5]) {

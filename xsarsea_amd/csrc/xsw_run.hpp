@@ -1,8 +1,9 @@
-// Host side of the raster entry points outside xsw.hip (xsw_gradients.hip, xsw_streaks.hip): the error text, and one call's
-// buffers on the XSW_MEM_HOST and XSW_MEM_DEVICE routes.
+// Host side of the raster entry points outside xsw.hip (xsw_gradients.hip, xsw_streaks.hip): the error text, the argument
+// checks and launch grids they share, and one call's buffers on the XSW_MEM_HOST and XSW_MEM_DEVICE routes.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 
@@ -63,5 +64,35 @@ static int run(xsw_ctx *c, int32_t mem, Buf (&b)[N], Launch &&launch, const char
 }
 
 static bool bad_mem(int32_t mem) { return mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE; }
+
+// The kernels index a raster's axes (and count windows) with int.
+static bool fits_int(int64_t a, int64_t b = 0) { return a <= 0x7fffffffLL && b <= 0x7fffffffLL; }
+
+// XSW_OK, or XSW_EINVAL with "<what>: raster too large" for a raster whose axes do not fit int.
+static int check_dims(xsw_ctx *c, const char *what, int64_t lines, int64_t samples)
+{
+    return fits_int(lines, samples) ? XSW_OK : gfail(c, XSW_EINVAL, "%s: raster too large", what);
+}
+
+// XSW_OK, or XSW_EINVAL when a 2-D grid of tiles has more rows than one launch takes.
+static int check_grid(xsw_ctx *c, const char *what, const dim3 &grid)
+{
+    return grid.y <= 65535 ? XSW_OK : gfail(c, XSW_EINVAL, "%s: raster too large for one launch", what);
+}
+
+// The grid of k_detrend for a rows x cols raster: about 16 workgroups per CU, each a 256-column strip of a block of rows.
+struct Strips {
+    long long gx, gy, rows_per_block;
+};
+static Strips strip_grid(long long rows, long long cols)
+{
+    Strips s;
+    s.gx = (cols + 255) / 256;
+    s.gy = (256LL * 16 + s.gx - 1) / s.gx;
+    s.gy = std::max<long long>(1, std::min<long long>(std::min<long long>(s.gy, rows), 65535));
+    s.rows_per_block = (rows + s.gy - 1) / s.gy;
+    s.gy = (rows + s.rows_per_block - 1) / s.rows_per_block;
+    return s;
+}
 
 }  // namespace

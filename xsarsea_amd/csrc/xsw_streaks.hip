@@ -201,7 +201,7 @@ extern "C" int xsw_streaks_peak(xsw_ctx *c, int64_t n_lead, int64_t n_windows, i
         return gfail(c, XSW_EINVAL, "streaks_peak: bad argument");
     if (n_angles < PEAK_MIN_ANGLES || n_angles > PEAK_MAX_ANGLES)
         return gfail(c, XSW_EINVAL, "streaks_peak: n_angles must be %d .. %d, not %d", PEAK_MIN_ANGLES, PEAK_MAX_ANGLES, (int)n_angles);
-    if (n_windows > 0x7fffffffLL || n_lead > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "streaks_peak: too many windows");
+    if (!fits_int(n_windows, n_lead)) return gfail(c, XSW_EINVAL, "streaks_peak: too many windows");
     if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
     const size_t nw = (size_t)n_windows, C = (size_t)n_lead;
     Buf b[5] = {{weight, nullptr, C * nw * n_angles * 8}, {used_ratio, nullptr, C * nw * 8}, {nullptr, index, nw * 4}, {nullptr, weight_out, nw * 8},
@@ -219,7 +219,7 @@ extern "C" int xsw_streaks_resolve(xsw_ctx *c, int64_t n_windows, int32_t mem, c
 {
     if (!c) return XSW_EINVAL;
     if (!dirs || !weight || !used_ratio || !ancillary || !out || n_windows < 1) return gfail(c, XSW_EINVAL, "streaks_resolve: bad argument");
-    if (n_windows > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "streaks_resolve: too many windows");
+    if (!fits_int(n_windows)) return gfail(c, XSW_EINVAL, "streaks_resolve: too many windows");
     if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
     const size_t nw = (size_t)n_windows;
     Buf b[5] = {{dirs, nullptr, nw * 16}, {weight, nullptr, nw * 8}, {used_ratio, nullptr, nw * 8}, {ancillary, nullptr, nw * 16}, {nullptr, out, nw * 16}};
@@ -237,20 +237,16 @@ extern "C" int xsw_streaks_ancillary(xsw_ctx *c, int64_t lines, int64_t samples,
     if (!c) return XSW_EINVAL;
     if (!ancillary || !dirs || !line_first || !line_t || !sample_first || !sample_t || !out || lines < 1 || samples < 1 || n_rows < 1 || n_cols < 1)
         return gfail(c, XSW_EINVAL, "streaks_ancillary: bad argument");
-    if (lines > 0x7fffffffLL || samples > 0x7fffffffLL) return gfail(c, XSW_EINVAL, "streaks_ancillary: raster too large");
+    if (int rc = check_dims(c, "streaks_ancillary", lines, samples)) return rc;
     if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
     const size_t npx = (size_t)lines * samples;
     Buf b[7] = {{ancillary, nullptr, npx * 16}, {dirs, nullptr, (size_t)n_rows * n_cols * 16}, {line_first, nullptr, (size_t)lines * 4},
                 {line_t, nullptr, (size_t)lines * 8}, {sample_first, nullptr, (size_t)samples * 4}, {sample_t, nullptr, (size_t)samples * 8},
                 {nullptr, out, npx * 16}};
-    // the grid of k_detrend: about 16 workgroups per CU, each a 256-sample column strip of a block of lines
-    const long long gx = (samples + 255) / 256;
-    long long gy = (256LL * 16 + gx - 1) / gx;
-    gy = std::max<long long>(1, std::min<long long>(std::min<long long>(gy, lines), 65535));
-    const long long lpb = (lines + gy - 1) / gy;
-    gy = (lines + lpb - 1) / lpb;
+    const Strips g = strip_grid(lines, samples);
+    const long long lpb = g.rows_per_block;
     return run(c, mem, b, [&](Buf (&x)[7]) {
-        hipLaunchKernelGGL(k_streaks_ancillary, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, c->stream, (const double2 *)x[0].dev,
+        hipLaunchKernelGGL(k_streaks_ancillary, dim3((unsigned)g.gx, (unsigned)g.gy), dim3(256), 0, c->stream, (const double2 *)x[0].dev,
                            (double2 *)x[6].dev, (long long)lines, (long long)samples, (const double2 *)x[1].dev, (int)n_rows, (int)n_cols,
                            (const int *)x[2].dev, (const double *)x[3].dev, (const int *)x[4].dev, (const double *)x[5].dev, lpb);
     }, "streaks_ancillary");

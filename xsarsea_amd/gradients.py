@@ -21,7 +21,8 @@ reference's np.add.at raises IndexError there, this port folds it onto bin 0 (pi
 """
 import numpy as np
 
-from . import _device, _lib, options
+from . import _device, _lib
+from ._raster import _as_u8, _Call, _coord_values, _is_tensor, _Raster, _u8_kind, _unwrap
 
 __all__ = ["Gradients", "Gradients2D", "GradientsHistogram", "local_gradients", "R2", "gradient_histogram", "circ_smooth",
            "angles_bins", "filtering_parameters", "Mean", "smoothing", "keep_mask"]
@@ -60,110 +61,14 @@ def nearest_indexer(index, target):
     return np.where((left_dist < right_dist) | (right_m == -1), left, right_m)
 
 
-def _coord_values(v):
-    return np.asarray(getattr(v, "values", v))
-
-
-class _Raster:
-    """A 2-D or 3-D raster (numpy or device tensor) with its coordinates."""
-
-    def __init__(self, sigma0, line=None, sample=None, pol=None, allow_pol=False):
-        self.device = _device.is_device_array(sigma0)
-        dims = tuple(getattr(sigma0, "dims", ()) or ())
-        if self.device:
-            values = _device.as_tensor(sigma0, _device.device_of(sigma0))
-        elif hasattr(sigma0, "values") and not isinstance(sigma0, np.ndarray):
-            values = np.asarray(sigma0.values)
-            if dims:
-                order = [d for d in ("pol", "line", "sample") if d in dims]
-                if sorted(order) != sorted(dims) or "line" not in order or "sample" not in order:
-                    raise ValueError(f"sigma0 dims must be (line, sample) with an optional pol, not {dims}")
-                values = np.transpose(values, [dims.index(d) for d in order])
-            line = _coord_values(sigma0.line) if line is None and hasattr(sigma0, "line") else line
-            sample = _coord_values(sigma0.sample) if sample is None and hasattr(sigma0, "sample") else sample
-            if pol is None and "pol" in dims:
-                pol = _coord_values(sigma0.pol)
-        else:
-            values = np.asarray(sigma0)
-        if values.ndim not in ((2, 3) if allow_pol else (2,)):
-            raise ValueError(f"sigma0 must be {'2-D or 3-D' if allow_pol else '2-D'}, not {values.ndim}-D")
-        self.values = values
-        self.has_pol = values.ndim == 3
-        shape = tuple(values.shape[-2:])
-        self.line = np.arange(shape[0]) if line is None else _coord_values(line)
-        self.sample = np.arange(shape[1]) if sample is None else _coord_values(sample)
-        if self.line.shape != (shape[0],) or self.sample.shape != (shape[1],):
-            raise ValueError("line / sample coordinates do not match the raster's shape")
-        self.pol = (np.arange(values.shape[0]) if pol is None else _coord_values(pol)) if self.has_pol else None
-
-
 # ------------------------------------------------------------------------------------------------------ device calls
-def _is_tensor(a):
-    return _device.is_device_array(a)
-
-
-class _Call:
-    """Where one kernel call runs: the default context of the array's device on torch's current stream (device arrays), or of
-    options.device with host buffers."""
-
-    def __init__(self, *arrays):
-        self.device = any(_is_tensor(a) for a in arrays)
-        if self.device:
-            import torch
-            self.torch = torch
-            self.dev = _device.device_of(*[a for a in arrays if _is_tensor(a)])
-            self.ctx = _lib.default_context(self.dev.index if self.dev.index is not None else torch.cuda.current_device())
-        else:
-            self.ctx = _lib.default_context(options.device)
-
-    def empty(self, shape, dtype):
-        if self.device:
-            tdt = {np.float32: self.torch.float32, np.float64: self.torch.float64, np.complex128: self.torch.complex128,
-                   np.int32: self.torch.int32, np.uint8: self.torch.uint8}[np.dtype(dtype).type]
-            return self.torch.empty(tuple(shape), dtype=tdt, device=self.dev)
-        return np.empty(shape, dtype)
-
-    def prep(self, a, dtype=None):
-        """Contiguous array of a kernel's input dtype (float32 / float64 rasters pass as they are, anything else -> float64)."""
-        if self.device:
-            t = _device.as_tensor(a, self.dev)
-            if dtype is not None:
-                t = t.to({np.float64: self.torch.float64, np.complex128: self.torch.complex128, np.int32: self.torch.int32}[np.dtype(dtype).type])
-            elif t.dtype not in (self.torch.float32, self.torch.float64):
-                t = t.double()
-            return t.contiguous()
-        a = np.asarray(a)
-        if dtype is not None:
-            return np.ascontiguousarray(a, dtype=dtype)
-        return np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
-
-    @staticmethod
-    def ptr(a):
-        return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
-
-    def xsw_dtype(self, a):
-        if self.device:
-            return _device.xsw_dtype(a)
-        return _lib.XSW_F32 if a.dtype == np.float32 else _lib.XSW_F64
-
-    def run(self, fn, inputs):
-        """fn(ctx, mem) on the context; device inputs are recorded on the launch stream (the caching allocator keeps them)."""
-        if not self.device:
-            return fn(self.ctx, _lib.MEM_HOST)
-        with _device.on_current_stream(self.ctx, self.dev):
-            fn(self.ctx, _lib.MEM_DEVICE)
-            cur = self.torch.cuda.current_stream(self.dev)
-            for t in inputs:
-                t.record_stream(cur)
-
-
 def _area(values, factor):
     """f x f box mean of a 2-D raster, the input's dtype (float32 / float64) kept (xsw_grad_area)."""
     call = _Call(values)
     x = call.prep(values)
     L, S = x.shape
     out = call.empty((L // factor, S // factor), np.float32 if call.xsw_dtype(x) == _lib.XSW_F32 else np.float64)
-    call.run(lambda ctx, mem: ctx.grad_area_raw(L, S, factor, call.xsw_dtype(x), mem, call.ptr(x), call.ptr(out)), [x])
+    call.launch("grad_area_raw", L, S, factor, call.xsw_dtype(x), call.mem, x, out)
     return out
 
 
@@ -176,7 +81,7 @@ def _r2(values, take_sqrt):
     if L < 2 or S < 2:
         raise ValueError("R2 needs at least 2 x 2 pixels")
     out = call.empty((L // 2, S // 2), np.float64)
-    call.run(lambda ctx, mem: ctx.grad_r2_raw(L, S, call.xsw_dtype(x), mem, take_sqrt, call.ptr(x), call.ptr(out)), [x])
+    call.launch("grad_r2_raw", L, S, call.xsw_dtype(x), call.mem, take_sqrt, x, out)
     return out
 
 
@@ -190,41 +95,25 @@ def _local(ampl):
         raise ValueError("local_gradients needs at least 2 x 2 pixels")
     shape = (L // 2, S // 2)
     g2, g3, c = call.empty(shape, np.complex128), call.empty(shape, np.float64), call.empty(shape, np.float64)
-    call.run(lambda ctx, mem: ctx.grad_local_raw(L, S, mem, call.ptr(x), call.ptr(g2), call.ptr(g3), call.ptr(c)), [x])
+    call.launch("grad_local_raw", L, S, call.mem, x, g2, g3, c)
     return g2, g3, c
 
 
-def _u8_kind(a):
-    """'u8' for a bool / uint8 array (numpy or tensor), 'float' for a floating one; TypeError for anything else."""
-    name = str(a.dtype).replace("torch.", "")
-    if name in ("bool", "uint8"):
-        return "u8"
-    if name in ("float16", "bfloat16", "float32", "float64"):
-        return "float"
-    raise TypeError(f"a mask must be bool or uint8 (or floating, with a threshold), not {a.dtype}")
-
-
-def _as_u8(call, a):
-    """Contiguous uint8 array of the call's container kind from a bool / uint8 array (bool is reinterpreted, not converted)."""
-    if call.device:
-        t = _device.as_tensor(a, call.dev).contiguous()
-        return t.view(call.torch.uint8) if t.dtype == call.torch.bool else t
-    if _is_tensor(a):
-        a = a.cpu().numpy()
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint8) if a.dtype == np.bool_ else a
+def _checked_keep(keep, g2):
+    """keep (or None) after the host checks: a bool / uint8 array of g2's shape."""
+    if keep is not None:
+        if tuple(keep.shape) != tuple(np.shape(g2)):
+            raise ValueError(f"keep {tuple(keep.shape)} must have g2's shape {tuple(np.shape(g2))}")
+        if _u8_kind(keep) != "u8":
+            raise TypeError(f"keep must be bool or uint8, not {keep.dtype}")
+    return keep
 
 
 def _hist(g2, c, window, rows, cols, n_angles, bins=None, normalise=True, keep=None):
     """Bin sums [rows, cols, n_angles] (divided by the window's pixel count with `normalise`, as an IEEE division on the device
     whatever the route) and used ratios [rows, cols] of the windows centred at (rows[a], cols[b]).  keep: bool / uint8 array of
     g2's shape, 0 = the pixel behaves as a NaN g2 (xsw_grad_hist_masked); None: the unmasked kernel."""
-    if keep is not None:
-        if tuple(keep.shape) != tuple(np.shape(g2)):
-            raise ValueError(f"keep {tuple(keep.shape)} must have g2's shape {tuple(np.shape(g2))}")
-        if _u8_kind(keep) != "u8":
-            raise TypeError(f"keep must be bool or uint8, not {keep.dtype}")
-    call = _Call(g2, c, keep)
+    call = _Call(g2, c, _checked_keep(keep, g2))
     g2, c = call.prep(g2, np.complex128), call.prep(c, np.float64)
     L, S = g2.shape
     if c.shape != g2.shape:
@@ -235,15 +124,10 @@ def _hist(g2, c, window, rows, cols, n_angles, bins=None, normalise=True, keep=N
     cols = call.prep(np.asarray(cols, dtype=np.int32), np.int32)
     nr, nc = rows.shape[0], cols.shape[0]
     weight, ratio = call.empty((nr, nc, len(bins)), np.float64), call.empty((nr, nc), np.float64)
-    if nr and nc and keep is not None:
-        keep = _as_u8(call, keep)
-        call.run(lambda ctx, mem: ctx.grad_hist_masked_raw(L, S, mem, call.ptr(g2), call.ptr(c), call.ptr(keep), int(wl), int(ws), nr,
-                                                           call.ptr(rows), nc, call.ptr(cols), len(bins), bins[0], bins[1] - bins[0],
-                                                           normalise, call.ptr(weight), call.ptr(ratio)), [g2, c, keep, rows, cols])
-    elif nr and nc:
-        call.run(lambda ctx, mem: ctx.grad_hist_raw(L, S, mem, call.ptr(g2), call.ptr(c), int(wl), int(ws), nr, call.ptr(rows), nc,
-                                                    call.ptr(cols), len(bins), bins[0], bins[1] - bins[0], normalise, call.ptr(weight),
-                                                    call.ptr(ratio)), [g2, c, rows, cols])
+    if nr and nc:
+        masked = () if keep is None else (_as_u8(call, keep),)
+        call.launch("grad_hist_raw" if keep is None else "grad_hist_masked_raw", L, S, call.mem, g2, c, *masked, wl, ws, nr, rows, nc, cols,
+                    len(bins), bins[0], bins[1] - bins[0], normalise, weight, ratio)
     return weight, ratio
 
 
@@ -285,9 +169,9 @@ def _same_shape_filter(image, fn_name):
     L, S = x.shape
     out = call.empty((L, S), np.float64)
     if fn_name == "Mean":
-        call.run(lambda ctx, mem: ctx.grad_mean_raw(L, S, mem, call.ptr(x), call.ptr(out)), [x])
+        call.launch("grad_mean_raw", L, S, call.mem, x, out)
     else:
-        call.run(lambda ctx, mem: ctx.grad_smooth_raw(L, S, mem, False, call.ptr(x), call.ptr(out)), [x])
+        call.launch("grad_smooth_raw", L, S, call.mem, False, x, out)
     return out
 
 
@@ -332,11 +216,10 @@ def filtering_parameters(image_ori, line=None, sample=None):
     r2, g3, c = (call.empty((L2, S2), np.float64) for _ in range(3))
     q4 = call.empty((L2 // 2, S2 // 2), np.float64)
     out = call.empty((5, L2, S2), np.float64)
-    call.run(lambda ctx, mem: ctx.grad_r2_sqrt_raw(L, S, dt, mem, call.ptr(x), call.ptr(r2)), [x])
-    call.run(lambda ctx, mem: ctx.grad_local_sqrt_raw(L, S, dt, mem, call.ptr(x), None, call.ptr(g3), call.ptr(c)), [x])
-    call.run(lambda ctx, mem: ctx.grad_smooth_raw(L2, S2, mem, True, call.ptr(r2), call.ptr(q4)), [r2])
-    call.run(lambda ctx, mem: ctx.grad_filter_raw(L2, S2, mem, call.ptr(r2), call.ptr(g3), call.ptr(c), call.ptr(q4), call.ptr(out)),
-             [r2, g3, c, q4])
+    call.launch("grad_r2_sqrt_raw", L, S, dt, call.mem, x, r2)
+    call.launch("grad_local_sqrt_raw", L, S, dt, call.mem, x, None, g3, c)
+    call.launch("grad_smooth_raw", L2, S2, call.mem, True, r2, q4)
+    call.launch("grad_filter_raw", L2, S2, call.mem, r2, g3, c, q4, out)
     return FilteringParameters(out[0], out[1], out[2], out[3], out[4], coarsen_coords(r.line, 2), coarsen_coords(r.sample, 2))
 
 
@@ -350,7 +233,7 @@ def keep_mask(values, threshold=None, block=2, and_with=None):
     block = 2 takes `filtering_parameters(sigma0).F` to the local-gradients grid of the same sigma0; block = 4 f takes a mask on
     the sigma0 grid to the local-gradients grid at downscale factor f.  For a threshold on F see `Gradients`' `min_F`: F sits on
     plateaus, choose the threshold between them."""
-    values = getattr(values, "values", values) if not _is_tensor(values) else values
+    values = _unwrap(values)
     if not _is_tensor(values):
         values = np.asarray(values)
     if len(values.shape) != 2:
@@ -379,8 +262,7 @@ def keep_mask(values, threshold=None, block=2, and_with=None):
     aw = None if and_with is None else _as_u8(call, and_with)
     out = call.empty((Lo, So), np.uint8)
     thr = None if kind == "u8" else float(threshold)
-    call.run(lambda ctx, mem: ctx.grad_keep_raw(L, S, mem, call.ptr(x), thr, block, None if aw is None else call.ptr(aw), call.ptr(out)),
-             [x] if aw is None else [x, aw])
+    call.launch("grad_keep_raw", L, S, call.mem, x, thr, block, aw, out)
     return out
 
 
@@ -421,12 +303,7 @@ def gradient_histogram(g2, c, angles_bins, keep=None):
         raise ValueError("g2 must be 2-D")
     if np.shape(c) != tuple(np.shape(g2)):
         raise ValueError("g2 and c must have one shape")
-    if keep is not None:
-        if tuple(keep.shape) != tuple(np.shape(g2)):
-            raise ValueError(f"keep {tuple(keep.shape)} must have g2's shape {tuple(np.shape(g2))}")
-        if _u8_kind(keep) != "u8":
-            raise TypeError(f"keep must be bool or uint8, not {keep.dtype}")
-    call = _Call(g2, c, keep)
+    call = _Call(g2, c, _checked_keep(keep, g2))
     g2 = call.prep(g2, np.complex128)
     _check_bins(call, g2, c, np.asarray(angles_bins, dtype=np.float64), keep)
     L, S = g2.shape
@@ -559,7 +436,7 @@ def _checked_mask(mask, values):
     if mask is None:
         return None
     if not _is_tensor(mask):
-        mask = np.asarray(getattr(mask, "values", mask))
+        mask = np.asarray(_unwrap(mask))
     if tuple(mask.shape) != tuple(values.shape[-2:]):
         raise ValueError(f"mask {tuple(mask.shape)} must have sigma0's (line, sample) shape {tuple(values.shape[-2:])}")
     if _u8_kind(mask) != "u8":

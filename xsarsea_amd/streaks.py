@@ -15,7 +15,8 @@ angles are radians from the sample axis towards the line axis.
 """
 import numpy as np
 
-from .gradients import GradientsHistogram, _Call, _coord_values, _is_tensor, _Raster, nearest_indexer
+from ._raster import _Call, _coord_values, _is_tensor, _Raster, _small, _unwrap
+from .gradients import GradientsHistogram, nearest_indexer
 
 __all__ = ["Streaks", "streaks_direction", "ancillary_from_streaks", "bracket"]
 
@@ -35,14 +36,6 @@ def bracket(centres, coords):
     with np.errstate(invalid="ignore", divide="ignore"):
         t = np.where(inside, (x - c[first]) / np.where(inside, c[nxt] - c[first], 1.0), 0.0)
     return first.astype(np.int32), t
-
-
-def _small(call, a, dtype):
-    """A small host table as the call's kernels want it.  On the device route it goes through page-locked staging and an
-    asynchronous copy on the current stream: the host does not wait for the work queued there."""
-    if not call.device or _is_tensor(a):
-        return call.prep(a, dtype)
-    return call.torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).pin_memory().to(call.dev, non_blocking=True)
 
 
 class Streaks:
@@ -76,7 +69,7 @@ class Streaks:
         a NaN part or is 0, and where weight < min_weight or used_ratio < min_used_ratio when these are given."""
         call = _Call(self.angle, self.weight, self.used_ratio, ancillary_wind)
         shape = tuple(self.weight.shape)
-        anc = getattr(ancillary_wind, "values", ancillary_wind) if not _is_tensor(ancillary_wind) else ancillary_wind
+        anc = _unwrap(ancillary_wind)
         if tuple(anc.shape) != shape:
             r = _Raster(ancillary_wind, line, sample)
             rows, cols = nearest_indexer(r.line, _coord_values(self.line)), nearest_indexer(r.sample, _coord_values(self.sample))
@@ -92,8 +85,7 @@ class Streaks:
         lo_w = np.nan if min_weight is None else float(min_weight)
         lo_r = np.nan if min_used_ratio is None else float(min_used_ratio)
         if nw:
-            call.run(lambda ctx, mem: ctx.streaks_resolve_raw(nw, mem, call.ptr(d0), call.ptr(weight), call.ptr(ratio), call.ptr(anc), lo_w, lo_r,
-                                                              call.ptr(out)), [d0, weight, ratio, anc])
+            call.launch("streaks_resolve_raw", nw, call.mem, d0, weight, ratio, anc, lo_w, lo_r, out)
         return out
 
 
@@ -108,7 +100,7 @@ def streaks_direction(hist, smooth=True, orthogonal=True, angles=None, line=None
     if isinstance(hist, GradientsHistogram):
         weight, ratio, angles, line, sample = hist.weight, hist.used_ratio, hist.angles, hist.line, hist.sample
     else:
-        weight, ratio = getattr(hist, "values", hist) if not _is_tensor(hist) else hist, None
+        weight, ratio = _unwrap(hist), None
         if angles is None:
             raise ValueError("a bare weight array needs the bin centres: angles=")
     angles = np.asarray(angles, dtype=np.float64)
@@ -126,8 +118,7 @@ def streaks_direction(hist, smooth=True, orthogonal=True, angles=None, line=None
     table = angles + np.pi / 2 if orthogonal else angles
     index, wout, rout = call.empty((nl, ns), np.int32), call.empty((nl, ns), np.float64), call.empty((nl, ns), np.float64)
     if nl * ns:
-        call.run(lambda ctx, mem: ctx.streaks_peak_raw(w.shape[0], nl * ns, n, mem, smooth, call.ptr(w), call.ptr(r), call.ptr(index),
-                                                       call.ptr(wout), call.ptr(rout)), [w, r])
+        call.launch("streaks_peak_raw", w.shape[0], nl * ns, n, call.mem, smooth, w, r, index, wout, rout)
     angle = _small(call, table, np.float64)[index.long()] if call.device else table[index]
     line = np.arange(nl) if line is None else _coord_values(line)
     sample = np.arange(ns) if sample is None else _coord_values(sample)
@@ -152,7 +143,7 @@ def ancillary_from_streaks(streaks_or_dirs, ancillary_wind, line=None, sample=No
             raise TypeError(f"unexpected arguments for an already resolved field: {sorted(resolve_kwargs)}")
         if windows_line is None or windows_sample is None:
             raise ValueError("a resolved direction field needs its window centres: windows_line=, windows_sample=")
-        dirs = getattr(streaks_or_dirs, "values", streaks_or_dirs) if not _is_tensor(streaks_or_dirs) else streaks_or_dirs
+        dirs = _unwrap(streaks_or_dirs)
         at_line, at_sample = _coord_values(windows_line), _coord_values(windows_sample)
     if tuple(dirs.shape) != (len(at_line), len(at_sample)):
         raise ValueError(f"directions {tuple(dirs.shape)} do not match the window centres ({len(at_line)}, {len(at_sample)})")
@@ -166,6 +157,5 @@ def ancillary_from_streaks(streaks_or_dirs, ancillary_wind, line=None, sample=No
     if L * S:
         if not len(at_line) * len(at_sample):
             raise ValueError("no window")
-        call.run(lambda ctx, mem: ctx.streaks_ancillary_raw(L, S, mem, call.ptr(anc), len(at_line), len(at_sample), call.ptr(dirs), call.ptr(lf),
-                                                            call.ptr(lt), call.ptr(sf), call.ptr(st), call.ptr(out)), [anc, dirs, lf, lt, sf, st])
+        call.launch("streaks_ancillary_raw", L, S, call.mem, anc, len(at_line), len(at_sample), dirs, lf, lt, sf, st, out)
     return out
