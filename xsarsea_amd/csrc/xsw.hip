@@ -25,19 +25,6 @@ using namespace xsw;
 
 #include "xsw_host.hpp"
 
-static thread_local std::string g_create_err;
-
-static int fail(xsw_ctx *c, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) c->err = buf; else g_create_err = buf;
-    return code;
-}
-
 #define HIPCHK(c, expr)                                                                          \
     do {                                                                                         \
         hipError_t e_ = (expr);                                                                  \
@@ -55,7 +42,7 @@ extern "C" int xsw_device_count(void)
     return n;
 }
 
-extern "C" const char *xsw_last_error(const xsw_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
+extern "C" const char *xsw_last_error(const xsw_ctx *ctx) { return ctx ? ctx->err.c_str() : create_err().c_str(); }
 
 extern "C" int xsw_ctx_create(int device, xsw_ctx **out)
 {
@@ -101,7 +88,7 @@ extern "C" int xsw_ctx_destroy(xsw_ctx *c)
     free_all(c->cr_allocs);
     if (c->d_stats) (void)hipFree(c->d_stats);
     if (c->d_ratio) (void)hipFree(c->d_ratio);
-    if (c->d_list) (void)hipFree(c->d_list);
+    if (c->lists.base) (void)hipFree(c->lists.base);
     if (c->nesz_scratch) (void)hipFree(c->nesz_scratch);
     for (hipEvent_t e : c->timing_events) (void)hipEventDestroy(e);
     if (c->arena) (void)hipFree(c->arena);
@@ -157,7 +144,7 @@ static void worker_release(xsw_ctx::Worker &w)
 // larger of its page-locked and its device buffer) are released, largest first -- a later call allocates them again (a few ms each).
 static void trim_staging(xsw_ctx *c)
 {
-    static const size_t keep = (size_t)(getenv("XSW_STAGING_KEEP_MB") ? std::max(0LL, atoll(getenv("XSW_STAGING_KEEP_MB"))) : 1536) << 20;
+    static const size_t keep = (size_t)env_int("XSW_STAGING_KEEP_MB", 1536, 0) << 20;
     // a worker counts with the larger of its two buffers: the pinned-input paths (XSW_MEM_HOST_PINNED, the pinned detrend) hold
     // no page-locked staging at all, and the device side of a worker (inputs + codes + its work lists and records) outgrows
     // the pinned side
@@ -248,9 +235,9 @@ extern "C" int xsw_timing_read(xsw_ctx *c, xsw_timing *out)
     out->last_band2_pixels = 0;
     out->last_list_pixels = 0;
     out->last_blocks_pixels = 0;
-    if (c->d_list) {
+    if (c->lists.base) {
         unsigned cnt[3] = {0, 0, 0};
-        HIPCHK(c, hipMemcpy(cnt, c->d_list, sizeof cnt, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(cnt, c->lists.count(WorkLists::G), sizeof cnt, hipMemcpyDeviceToHost));
         out->last_list_pixels = (int64_t)cnt[0];
         out->last_band2_pixels = (int64_t)cnt[1];
         out->last_blocks_pixels = (int64_t)cnt[2];
@@ -401,7 +388,7 @@ static int install_co(xsw_ctx *c, const xsw_lut *l, const double *d_dense)
         }
         T.mono_rows = d_mono;
         T.tail_min = nullptr;
-        static const bool tail_off = getenv("XSW_NO_TAIL_CUT") != nullptr;  // A/B measurements only
+        static const bool tail_off = env_flag("XSW_NO_TAIL_CUT");  // A/B measurements only
         if (e == hipSuccess && !tail_off) {
             double *d_tail = nullptr;
             if (hipMalloc((void **)&d_tail, (size_t)nI * (XSW_TAIL_LEVELS + 1) * ppad * sizeof(double) + 64) == hipSuccess) {
@@ -435,7 +422,7 @@ static int install_co(xsw_ctx *c, const xsw_lut *l, const double *d_dense)
         T.ncr = (T.nbr + XSW_CELL_R - 1) / XSW_CELL_R; T.ncc = (T.nbc + XSW_CELL_C - 1) / XSW_CELL_C;
         T.blk_g = std::max(1, 64 / T.nbc);
         T.nbands = (T.nbr + T.blk_g - 1) / T.blk_g;
-        static const bool blocks_off = getenv("XSW_NO_BLOCKS") != nullptr;
+        static const bool blocks_off = env_flag("XSW_NO_BLOCKS");
         if (e == hipSuccess && !blocks_off && (long long)nI * T.nbr * T.nbc < (1LL << 31)) {
             float2 *d_blk = nullptr, *d_band = nullptr;
             const long long nblk = (long long)nI * T.nbr * T.nbc, nband = (long long)nI * T.nbands;
@@ -463,7 +450,7 @@ static int install_co(xsw_ctx *c, const xsw_lut *l, const double *d_dense)
             // the same per sub-block of XSW_BLK_C4 directions (k_invert_blocks bounds the quarters of a kept block before sweeping:
             // sigma0 varies faster with the direction than with the speed where the GMF saturates, so a block 16 directions wide
             // nearly always straddles the contour); 23 MB at the default size.  XSW_NO_BLK4=1: not built (A/B, tests of the old sweep)
-            static const bool blk4_off = getenv("XSW_NO_BLK4") != nullptr;
+            static const bool blk4_off = env_flag("XSW_NO_BLK4");
             if (T.blk && !blk4_off && (long long)nI * T.nbr * T.nbc4 < (1LL << 31)) {
                 float2 *d_blk4 = nullptr;
                 const long long nblk4 = (long long)nI * T.nbr * T.nbc4;
@@ -677,34 +664,19 @@ static int dispatch_invert(xsw_ctx *c, const KArgs &A, int dtype, int out_dtype,
     return xsw_launch_invert_dd(c, A, algo, lc, err);
 }
 
-// Work list of the device-raster path: an eighth of the raster's pixels (the benchmark scene leaves 0.06 %; a scene that
-// leaves more than an eighth overflows it, see k_invert_list).  A failed allocation selects the one-kernel path.
-static size_t list_entries_for(long long n)
-{
-    static const char *test_cap = getenv("XSW_LIST_CAP_TEST");  // tests: a tiny capacity, so that the overflow route runs
-    if (test_cap) return (size_t)std::max(atoll(test_cap), 16LL);
-    return (size_t)std::max<long long>(n / 8, 1 << 16);
-}
-// strips of 64 samples a raster of n pixels in `lines` lines can have, however it is cut (as given, or into lines of 4096)
-static size_t strips_for(long long n, long long lines) { return (size_t)(n / 64 + std::max<long long>(lines, n / 4096) + 64); }
+// Work lists of the device-raster path (capacities: xsw_plan.hpp).  A failed allocation selects the one-kernel path.
 static void ensure_list(xsw_ctx *c, long long n, long long lines)
 {
-    const size_t want = (list_entries_for(n) + 1) & ~(size_t)1, want_strips = strips_for(n, lines);  // even: the masks stay 8-byte aligned
-    if (want <= c->list_cap && want_strips <= c->mask_strips) return;
-    (void)hipStreamSynchronize(c->stream);  // the old list may still be in use
-    if (c->d_list) (void)hipFree(c->d_list);
-    c->d_list = nullptr;
-    c->d_masks = nullptr;
-    c->d_rec = nullptr;
-    c->list_cap = c->mask_strips = 0;
-    static const bool no_list = getenv("XSW_FAIL_LIST_ALLOC") != nullptr;  // tests: the allocation-failure route
-    // list G (`want` entries), B (XSW_LIST_B_SHARE x want) and C (XSW_LIST_C_SHARE x want), the two strip masks (0.25 B per pixel), list B's records
-    if (!no_list && hipMalloc((void **)&c->d_list, (XSW_LISTS_TOTAL * want + 16) * sizeof(unsigned) + 2 * want_strips * sizeof(unsigned long long) + (size_t)XSW_LIST_B_SHARE * want * XSW_REC_BYTES) == hipSuccess) {
-        c->list_cap = want;
-        c->d_masks = (unsigned long long *)(c->d_list + 16 + XSW_LISTS_TOTAL * want);
-        c->d_rec = (void *)(c->d_masks + 2 * want_strips);
-        c->mask_strips = want_strips;
-    } else { c->d_list = nullptr; (void)hipGetLastError(); }
+    static const long long test_cap = env_int("XSW_LIST_CAP_TEST", 0, 16);  // tests: a tiny capacity, so that the overflow route runs
+    const size_t want = context_list_cap(n, test_cap), want_strips = strips_for(n, lines);
+    if (want <= c->lists.list_cap && want_strips <= c->lists.mask_strips) return;
+    (void)hipStreamSynchronize(c->stream);  // the old lists may still be in use
+    if (c->lists.base) (void)hipFree(c->lists.base);
+    c->lists = WorkLists{};
+    static const bool no_list = env_flag("XSW_FAIL_LIST_ALLOC");  // tests: the allocation-failure route
+    WorkLists w{nullptr, want, want_strips};
+    if (!no_list && hipMalloc((void **)&w.base, w.bytes()) == hipSuccess) c->lists = w;
+    else (void)hipGetLastError();
 }
 
 // ---- grid codes -> complex winds (xsw.h: xsw_expand_codes)
@@ -855,8 +827,7 @@ static int host_thread_count(const xsw_ctx *c)
 {
     int n = c->host_threads;
     if (n <= 0) {
-        const char *e = getenv("XSW_HOST_THREADS");
-        n = e ? atoi(e) : 12;
+        n = (int)env_int("XSW_HOST_THREADS", 12);  // read on every call
     }
     return std::max(1, std::min(n, 32));
 }
@@ -918,6 +889,31 @@ static int run_chunks(xsw_ctx *c, long long nchunks, Body &&body)
     return XSW_OK;
 }
 
+// One raster of a chunk: host -> (page-locked staging ->) device, at offset `off` of the worker's two buffers.  The caller's
+// staging callback may fill the staging area itself (numpy's own log10 on the bit-parity route); page-locked caller rasters
+// (pinned_in) are read by the DMA engine directly.  A raster that is not given (h == nullptr) is nothing to do.
+static int stage_upload(const xsw_invert_args *a, xsw_ctx::Worker &w, const ChunkPlan::Chunk &ch, bool pinned_in, int which,
+                        const void *h, size_t off, size_t elem, std::string &err)
+{
+    if (!h) return XSW_OK;
+    const char *src = (const char *)h + ch.px0 * elem;
+    int staged = 0;
+    if (a->stage) {
+        staged = a->stage(a->stage_user, which, (int64_t)ch.px0, (int64_t)ch.npx, w.pin + off);
+        if (staged < 0) return seterr(err, XSW_EINVAL, "the staging callback failed for raster %d, pixels [%zu, %zu)", which, ch.px0, ch.px0 + ch.npx);
+    }
+    if (staged > 0) src = w.pin + off;
+    else if (!pinned_in) { memcpy(w.pin + off, src, ch.npx * elem); src = w.pin + off; }
+    const hipError_t e = hipMemcpyAsync(w.dev + off, src, ch.npx * elem, hipMemcpyHostToDevice, w.s);
+    return e == hipSuccess ? XSW_OK : seterr(err, XSW_EHIP, "H2D copy failed: %s", hipGetErrorString(e));
+}
+
+// A worker's own work lists for the chunks of `plan`, after `staged` bytes of its device buffer (dev == nullptr: the sizes only).
+static WorkLists worker_lists(const ChunkPlan &plan, char *dev, size_t staged)
+{
+    return WorkLists{dev ? (unsigned *)(dev + staged) : nullptr, worker_list_cap(plan.max_px), strips_for((long long)plan.max_px, plan.lines_per_chunk)};
+}
+
 extern "C" int xsw_invert(xsw_ctx *c, const xsw_invert_args *a)
 {
     if (!c || !a) return XSW_EINVAL;
@@ -956,38 +952,23 @@ extern "C" int xsw_invert(xsw_ctx *c, const xsw_invert_args *a)
         A.stats_chain = c->stats_chain ? 1 : 0;
     }
 
-    if (a->mem == XSW_MEM_DEVICE) {
-        A.inc = a->inc; A.s_co = a->sigma0_co; A.s_cr = a->sigma0_cr; A.dsig_cr = a->dsig_cr; A.anc = a->anc;
+    const size_t es = a->dtype == XSW_F32 ? 4 : 8, os = a->out_dtype == XSW_F32 ? 8 : 16;
+    const int dtype = a->dtype, out_dtype = a->out_dtype;
+    if (a->mem == XSW_MEM_DEVICE || a->mem == XSW_MEM_DEVICE_SIGMA0_HOST) {  // the caller's device rasters
+        A.inc = a->inc; A.dsig_cr = a->dsig_cr; A.anc = a->anc;
         A.out_co = a->out_co; A.out_cr = a->out_cr; A.out_idx = a->out_idx;
         A.code_co = a->out_code_co; A.code_cr = a->out_code_cr;
+    }
+
+    if (a->mem == XSW_MEM_DEVICE) {
+        A.s_co = a->sigma0_co; A.s_cr = a->sigma0_cr;
         if (algo == XSW_ALGO_PRUNED) ensure_list(c, n, a->lines);
         std::string err;
-        const LaunchCtl lc{c->stream, c->d_list, c->list_cap, c->timing_on, c->d_masks, c->mask_strips, c->d_rec};
-        int rc;
-        if (a->lines < 16 && n >= (1LL << 16)) {
-            // a flat raster (a long vector of pixels: 1-D inputs arrive as one line) is re-cut into lines of 4096 samples + a
-            // tail, as on the host path: the core dimension is only a loop (windspeed.py:190), and a one-line raster would leave
-            // three of a workgroup's four waves idle
-            const size_t es = a->dtype == XSW_F32 ? 4 : 8, os = a->out_dtype == XSW_F32 ? 8 : 16;
-            const long long S = 4096, Lv = n / S, tail = n - Lv * S;
-            auto shift = [](const void *p, size_t bytes) -> const void * { return p ? (const char *)p + bytes : nullptr; };
-            KArgs M = A;
-            M.lines = Lv; M.samples = S; M.n = Lv * S;
-            rc = dispatch_invert(c, M, a->dtype, a->out_dtype, algo, lc, err);
-            if (!rc && tail) {
-                const size_t px = (size_t)(Lv * S);
-                KArgs Tl = A;
-                Tl.lines = 1; Tl.samples = tail; Tl.n = tail;
-                Tl.inc = shift(A.inc, px * es); Tl.s_co = shift(A.s_co, px * es); Tl.s_cr = shift(A.s_cr, px * es);
-                Tl.dsig_cr = shift(A.dsig_cr, px * es); Tl.anc = shift(A.anc, px * es * 2);
-                Tl.out_co = (void *)shift(A.out_co, px * os); Tl.out_cr = (void *)shift(A.out_cr, px * os);
-                Tl.out_idx = (int *)shift(A.out_idx, px * 12);
-                Tl.code_co = (unsigned *)shift(A.code_co, px * 4); Tl.code_cr = (unsigned *)shift(A.code_cr, px * 4);
-                rc = dispatch_invert(c, Tl, a->dtype, a->out_dtype, algo, lc, err);  // same stream, same work list: in order
-            }
-        } else {
-            rc = dispatch_invert(c, A, a->dtype, a->out_dtype, algo, lc, err);
-        }
+        const LaunchCtl lc{c->stream, c->timing_on, c->lists};
+        // one launch; a flat raster is re-cut as on the host path (ChunkPlan), which makes two: same stream, same work lists, in order
+        const ChunkPlan plan(a->lines, a->samples, 0, 1, true);
+        int rc = XSW_OK;
+        for (long long k = 0; k < plan.nchunks && !rc; ++k) rc = dispatch_invert(c, slice(A, plan.chunk(k), es, os), dtype, out_dtype, algo, lc, err);
         return rc ? fail(c, rc, "%s", err.c_str()) : XSW_OK;
     }
 
@@ -997,140 +978,71 @@ extern "C" int xsw_invert(xsw_ctx *c, const xsw_invert_args *a)
         // raster, the kernels on the worker's stream with the caller's device pointers advanced to the chunk, results in place.
         if (a->out_idx || a->lines < 4) return fail(c, XSW_EINVAL, "XSW_MEM_DEVICE_SIGMA0_HOST: out_idx is not supported, and the raster needs 4 lines or more");
         HIPCHK(c, hipStreamSynchronize(c->stream));  // the resident rasters' producers, and the statistics reset
-        const size_t es = a->dtype == XSW_F32 ? 4 : 8, os = a->out_dtype == XSW_F32 ? 8 : 16;
-        const long long lines = a->lines, samples = a->samples;
-        const long long target_px = std::min<long long>(4LL << 20, std::max<long long>(1LL << 16, n / 16));
-        long long lpc = (std::max<long long>((target_px + samples - 1) / samples, 4) + 3) & ~3LL;
-        const long long nchunks = (lines + lpc - 1) / lpc;
-        const size_t max_px = (size_t)std::min<long long>(lpc, lines) * samples;
-        auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t o_co = 0, o_cr = o_co + (a->sigma0_co ? pad(max_px * es) : 0), o_end = o_cr + (a->sigma0_cr ? pad(max_px * es) : 0);
-        const size_t list_cap = std::max<size_t>(max_px / 8, 1 << 14) & ~(size_t)1, mask_strips = strips_for((long long)max_px, lpc);
-        const size_t o_masks = o_end + pad((XSW_LISTS_TOTAL * list_cap + 16) * sizeof(unsigned)), o_rec = o_masks + 2 * mask_strips * sizeof(unsigned long long), dev_bytes = o_rec + XSW_LIST_B_SHARE * list_cap * XSW_REC_BYTES;
-        const int dtype = a->dtype, out_dtype = a->out_dtype;
-        auto shift = [](const void *p, size_t bytes) -> const void * { return p ? (const char *)p + bytes : nullptr; };
-        const int rc_all = run_chunks(c, nchunks, [&](long long k, xsw_ctx::Worker &w, std::string &err) -> int {
-            int rc = worker_reserve(w, o_end, dev_bytes, err);
+        const ChunkPlan plan(a->lines, a->samples, 4LL << 20, 4, false);
+        const ChunkStaging st(plan.max_px, es, false, a->sigma0_co, a->sigma0_cr, false, false, false, false);
+        const size_t dev_bytes = st.o_end + worker_lists(plan, nullptr, 0).bytes();
+        const int rc_all = run_chunks(c, plan.nchunks, [&](long long k, xsw_ctx::Worker &w, std::string &err) -> int {
+            int rc = worker_reserve(w, st.o_end, dev_bytes, err);
             if (rc) return rc;
-            const long long l0 = k * lpc, l1 = std::min(lines, l0 + lpc);
-            const size_t px0 = (size_t)l0 * samples, npx = (size_t)(l1 - l0) * samples;
-            hipError_t e = hipSuccess;
-            auto up = [&](int which, const void *h, size_t off) {
-                if (!h || e != hipSuccess || rc) return;
-                int staged = 0;
-                if (a->stage) {
-                    staged = a->stage(a->stage_user, which, (int64_t)px0, (int64_t)npx, w.pin + off);
-                    if (staged < 0) { rc = seterr(err, XSW_EINVAL, "the staging callback failed for raster %d, pixels [%zu, %zu)", which, px0, px0 + npx); return; }
-                }
-                if (staged <= 0) memcpy(w.pin + off, (const char *)h + px0 * es, npx * es);
-                e = hipMemcpyAsync(w.dev + off, w.pin + off, npx * es, hipMemcpyHostToDevice, w.s);
-            };
-            up(1, a->sigma0_co, o_co); up(2, a->sigma0_cr, o_cr);
+            const ChunkPlan::Chunk ch = plan.chunk(k);
+            if ((rc = stage_upload(a, w, ch, false, 1, a->sigma0_co, st.o_co, es, err)) || (rc = stage_upload(a, w, ch, false, 2, a->sigma0_cr, st.o_cr, es, err))) return rc;
+            KArgs B = slice(A, ch, es, os);
+            B.s_co = a->sigma0_co ? w.dev + st.o_co : nullptr;
+            B.s_cr = a->sigma0_cr ? w.dev + st.o_cr : nullptr;
+            rc = dispatch_invert(c, B, dtype, out_dtype, algo, LaunchCtl{w.s, false, worker_lists(plan, w.dev, st.o_end)}, err);
             if (rc) return rc;
-            if (e != hipSuccess) return seterr(err, XSW_EHIP, "H2D copy failed: %s", hipGetErrorString(e));
-            KArgs B = A;
-            B.lines = l1 - l0;
-            B.n = (long long)npx;
-            B.inc = shift(a->inc, px0 * es);
-            B.s_co = a->sigma0_co ? w.dev + o_co : nullptr;
-            B.s_cr = a->sigma0_cr ? w.dev + o_cr : nullptr;
-            B.dsig_cr = shift(a->dsig_cr, px0 * es);
-            B.anc = shift(a->anc, px0 * es * 2);
-            B.out_co = (void *)shift(a->out_co, px0 * os);
-            B.out_cr = (void *)shift(a->out_cr, px0 * os);
-            B.code_co = (unsigned *)shift(a->out_code_co, px0 * 4);
-            B.code_cr = (unsigned *)shift(a->out_code_cr, px0 * 4);
-            const LaunchCtl lc{w.s, (unsigned *)(w.dev + o_end), list_cap, false, (unsigned long long *)(w.dev + o_masks), mask_strips, (void *)(w.dev + o_rec)};
-            rc = dispatch_invert(c, B, dtype, out_dtype, algo, lc, err);
-            if (rc) return rc;
-            e = hipStreamSynchronize(w.s);
+            const hipError_t e = hipStreamSynchronize(w.s);
             return e == hipSuccess ? XSW_OK : seterr(err, XSW_EHIP, "kernel execution failed: %s", hipGetErrorString(e));
         });
         trim_staging(c);
         return rc_all;
     }
 
-    // Host rasters.  Chunks of whole 4-line tile rows (~2 Mpx) go through the workers: stage the chunk's inputs into the
-    // worker's page-locked buffer (XSW_MEM_HOST_PINNED: skipped), ONE upload, the kernels on the worker's stream, ONE download
-    // of the grid codes, then the codes are expanded into the caller's rasters by the worker's thread while the other
-    // workers' chunks are in other phases.
+    // Host rasters.  Chunks of whole 4-line tile rows (~2 Mpx; a flat raster re-cut, see ChunkPlan, so that the chunks pipeline)
+    // go through the workers: stage the chunk's inputs into the worker's page-locked buffer (XSW_MEM_HOST_PINNED: skipped), ONE
+    // upload, the kernels on the worker's stream, ONE download of the grid codes, then the codes are expanded into the caller's
+    // rasters by the worker's thread while the other workers' chunks are in other phases.
     if (c->stats_on) HIPCHK(c, hipStreamSynchronize(c->stream));  // the counters were reset on the context's stream
     const bool pinned_in = a->mem == XSW_MEM_HOST_PINNED;
-    const size_t es = a->dtype == XSW_F32 ? 4 : 8;
     const bool want_co = a->sigma0_co || a->out_co || a->out_code_co;
     const bool want_cr = a->out_cr || a->out_code_cr || (a->sigma0_cr && a->out_idx);
-    // A flat raster (a long vector of pixels -- the core dimension is only a loop, windspeed.py:190; 1-D inputs arrive as one
-    // line) is re-cut into lines of 4096 samples + a tail: pixels are independent, and whole 4-line tiles keep the workgroups
-    // full (a one-line raster leaves three of a workgroup's four waves idle) and let the chunks pipeline.
-    long long lines = a->lines, samples = a->samples, tail_px = 0;
-    if (lines < 16 && n >= (1LL << 16)) { samples = 4096; lines = n / samples; tail_px = n - lines * samples; }
-    A.samples = samples;
-    const long long target_px = std::min<long long>(2LL << 20, std::max<long long>(1LL << 16, n / 16));
-    long long lines_per_chunk = samples > 0 ? (target_px + samples - 1) / samples : lines;
-    lines_per_chunk = (std::max<long long>(lines_per_chunk, 4) + 3) & ~3LL;  // whole 4-line tile rows
-    const long long nmain = (lines + lines_per_chunk - 1) / lines_per_chunk, nchunks = nmain + (tail_px ? 1 : 0);
-    const size_t max_px = (size_t)std::max<long long>(std::min<long long>(lines_per_chunk, lines) * samples, tail_px);
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // staging layout of a chunk (the same offsets in the page-locked and the device buffer): inputs, then codes; list after
-    const size_t o_inc = 0, o_co = o_inc + pad(max_px * es), o_cr = o_co + (a->sigma0_co ? pad(max_px * es) : 0),
-                 o_dsig = o_cr + (a->sigma0_cr ? pad(max_px * es) : 0), o_anc = o_dsig + (a->dsig_cr ? pad(max_px * es) : 0),
-                 o_cc = o_anc + (a->anc ? pad(max_px * es * 2) : 0), o_ccr = o_cc + (want_co ? pad(max_px * 4) : 0),
-                 o_end = o_ccr + (want_cr ? pad(max_px * 4) : 0);
-    const size_t list_cap = std::max<size_t>(max_px / 8, 1 << 14) & ~(size_t)1, mask_strips = strips_for((long long)max_px, lines_per_chunk);
-    const size_t o_masks = o_end + pad((XSW_LISTS_TOTAL * list_cap + 16) * sizeof(unsigned)), o_rec = o_masks + 2 * mask_strips * sizeof(unsigned long long), dev_bytes = o_rec + XSW_LIST_B_SHARE * list_cap * XSW_REC_BYTES;  // lists G, B and C, strip masks, list B's records
-    const int dtype = a->dtype, out_dtype = a->out_dtype;
-    static const bool prof = getenv("XSW_HOST_PROFILE") != nullptr;  // phase times of the pipeline on stderr (experiments)
+    const ChunkPlan plan(a->lines, a->samples, 2LL << 20, 4, true);
+    const ChunkStaging st(plan.max_px, es, true, a->sigma0_co, a->sigma0_cr, a->dsig_cr, a->anc, want_co, want_cr);
+    const size_t dev_bytes = st.o_end + worker_lists(plan, nullptr, 0).bytes();
+    static const bool prof = env_flag("XSW_HOST_PROFILE");  // phase times of the pipeline on stderr (experiments)
     std::atomic<long long> t_stage{0}, t_gpu{0}, t_expand{0}, t_reserve{0};
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto us = [](std::chrono::steady_clock::time_point a0, std::chrono::steady_clock::time_point b0) {
         return (long long)std::chrono::duration_cast<std::chrono::microseconds>(b0 - a0).count(); };
     const auto t_begin = now();
-    const int rc_all = run_chunks(c, nchunks, [&](long long k, xsw_ctx::Worker &w, std::string &err) -> int {
+    const int rc_all = run_chunks(c, plan.nchunks, [&](long long k, xsw_ctx::Worker &w, std::string &err) -> int {
         const auto t0 = now();
-        int rc = worker_reserve(w, o_end, dev_bytes, err);
+        int rc = worker_reserve(w, st.o_end, dev_bytes, err);
         if (rc) return rc;
         const auto t1 = now();
-        const bool is_tail = k >= nmain;  // the last pixels of a re-cut flat raster, as one short line
-        const long long l0 = is_tail ? lines : k * lines_per_chunk, l1 = is_tail ? lines + 1 : std::min(lines, l0 + lines_per_chunk);
-        const size_t px0 = (size_t)l0 * samples, npx = is_tail ? (size_t)tail_px : (size_t)(l1 - l0) * samples;
-        hipError_t e = hipSuccess;
-        // one raster of the chunk: host -> (page-locked staging ->) device.  The caller's staging callback may fill the staging
-        // area itself; page-locked caller rasters are read by the DMA engine directly
-        auto up = [&](int which, const void *h, size_t off, size_t elem) {
-            if (!h || e != hipSuccess || rc) return;
-            const char *src = (const char *)h + px0 * elem;
-            int staged = 0;
-            if (a->stage) {
-                staged = a->stage(a->stage_user, which, (int64_t)px0, (int64_t)npx, w.pin + off);
-                if (staged < 0) { rc = seterr(err, XSW_EINVAL, "the staging callback failed for raster %d, pixels [%zu, %zu)", which, px0, px0 + npx); return; }
-            }
-            if (staged > 0) src = w.pin + off;
-            else if (!pinned_in) { memcpy(w.pin + off, src, npx * elem); src = w.pin + off; }
-            e = hipMemcpyAsync(w.dev + off, src, npx * elem, hipMemcpyHostToDevice, w.s);
-        };
-        up(0, a->inc, o_inc, es); up(1, a->sigma0_co, o_co, es); up(2, a->sigma0_cr, o_cr, es); up(3, a->dsig_cr, o_dsig, es); up(4, a->anc, o_anc, es * 2);
-        if (rc) return rc;
+        const ChunkPlan::Chunk ch = plan.chunk(k);
+        const size_t px0 = ch.px0, npx = ch.npx;
+        auto up = [&](int which, const void *h, size_t off, size_t elem) { return stage_upload(a, w, ch, pinned_in, which, h, off, elem, err); };
+        if ((rc = up(0, a->inc, st.o_inc, es)) || (rc = up(1, a->sigma0_co, st.o_co, es)) || (rc = up(2, a->sigma0_cr, st.o_cr, es)) ||
+            (rc = up(3, a->dsig_cr, st.o_dsig, es)) || (rc = up(4, a->anc, st.o_anc, es * 2)))
+            return rc;
         const auto t2 = now();
-        if (e != hipSuccess) return seterr(err, XSW_EHIP, "H2D copy failed: %s", hipGetErrorString(e));
-        KArgs B = A;
-        B.lines = l1 - l0;
-        B.n = (long long)npx;
-        if (is_tail) B.samples = tail_px;
-        B.inc = w.dev + o_inc;
-        B.s_co = a->sigma0_co ? w.dev + o_co : nullptr;
-        B.s_cr = a->sigma0_cr ? w.dev + o_cr : nullptr;
-        B.dsig_cr = a->dsig_cr ? w.dev + o_dsig : nullptr;
-        B.anc = a->anc ? w.dev + o_anc : nullptr;
-        B.code_co = want_co ? (unsigned *)(w.dev + o_cc) : nullptr;
-        B.code_cr = want_cr ? (unsigned *)(w.dev + o_ccr) : nullptr;
-        const LaunchCtl lc{w.s, (unsigned *)(w.dev + o_end), list_cap, false, (unsigned long long *)(w.dev + o_masks), mask_strips, (void *)(w.dev + o_rec)};
-        rc = dispatch_invert(c, B, dtype, out_dtype, algo, lc, err);
+        KArgs B = slice(A, ch, es, os);  // (A holds no raster: the inputs are the worker's staging, the answer its grid codes)
+        B.inc = w.dev + st.o_inc;
+        B.s_co = a->sigma0_co ? w.dev + st.o_co : nullptr;
+        B.s_cr = a->sigma0_cr ? w.dev + st.o_cr : nullptr;
+        B.dsig_cr = a->dsig_cr ? w.dev + st.o_dsig : nullptr;
+        B.anc = a->anc ? w.dev + st.o_anc : nullptr;
+        B.code_co = want_co ? (unsigned *)(w.dev + st.o_cc) : nullptr;
+        B.code_cr = want_cr ? (unsigned *)(w.dev + st.o_ccr) : nullptr;
+        rc = dispatch_invert(c, B, dtype, out_dtype, algo, LaunchCtl{w.s, false, worker_lists(plan, w.dev, st.o_end)}, err);
         if (rc) return rc;
-        if (o_end > o_cc) e = hipMemcpyAsync(w.pin + o_cc, w.dev + o_cc, o_end - o_cc, hipMemcpyDeviceToHost, w.s);
+        hipError_t e = hipSuccess;
+        if (st.o_end > st.o_cc) e = hipMemcpyAsync(w.pin + st.o_cc, w.dev + st.o_cc, st.o_end - st.o_cc, hipMemcpyDeviceToHost, w.s);
         if (e == hipSuccess) e = hipStreamSynchronize(w.s);
         if (e != hipSuccess) return seterr(err, XSW_EHIP, "kernel execution failed: %s", hipGetErrorString(e));
         const auto t3 = now();
-        const uint32_t *cc = want_co ? (const uint32_t *)(w.pin + o_cc) : nullptr, *ccr = want_cr ? (const uint32_t *)(w.pin + o_ccr) : nullptr;
+        const uint32_t *cc = want_co ? (const uint32_t *)(w.pin + st.o_cc) : nullptr, *ccr = want_cr ? (const uint32_t *)(w.pin + st.o_ccr) : nullptr;
         if (a->out_code_co && cc) memcpy(a->out_code_co + px0, cc, npx * 4);
         if (a->out_code_cr && ccr) memcpy(a->out_code_cr + px0, ccr, npx * 4);
         int32_t *idx = a->out_idx ? a->out_idx + 3 * px0 : nullptr;
@@ -1146,7 +1058,7 @@ extern "C" int xsw_invert(xsw_ctx *c, const xsw_invert_args *a)
     trim_staging(c);
     if (prof)
         fprintf(stderr, "[xsw host] %lld px, %lld chunks, %d threads: wall %.2f ms; summed over workers: reserve %.2f, stage %.2f, upload+kernels+download %.2f, expand %.2f ms\n",
-                n, nchunks, (int)std::min<long long>(host_thread_count(c), nchunks), us(t_begin, now()) / 1e3, t_reserve / 1e3, t_stage / 1e3, t_gpu / 1e3, t_expand / 1e3);
+                n, plan.nchunks, (int)std::min<long long>(host_thread_count(c), plan.nchunks), us(t_begin, now()) / 1e3, t_reserve / 1e3, t_stage / 1e3, t_gpu / 1e3, t_expand / 1e3);
     return rc_all;
 }
 
@@ -1371,18 +1283,12 @@ template <typename T, typename TO>
 static void launch_detrend(hipStream_t s, const void *in, const double *ratio, const double *rinv, bool fast, void *out,
                            long long lines, long long samples)
 {
-    const long long quads = (samples + 3) / 4;
-    const unsigned gx = (unsigned)((quads + 255) / 256);
 #ifndef XSW_DETREND_WG_PER_CU
 #define XSW_DETREND_WG_PER_CU 16
 #endif
-    long long gy = (256LL * XSW_DETREND_WG_PER_CU + gx - 1) / gx;  // workgroups per CU
-    if (gy > lines) gy = lines;
-    if (gy > 65535) gy = 65535;
-    if (gy < 1) gy = 1;
-    const long long lpb = (lines + gy - 1) / gy;
-    gy = (lines + lpb - 1) / lpb;
-    const dim3 grid(gx, (unsigned)gy);
+    const Strips g = strip_grid(lines, (samples + 3) / 4, XSW_DETREND_WG_PER_CU);  // columns: quads of samples
+    const dim3 grid((unsigned)g.gx, (unsigned)g.gy);
+    const long long lpb = g.rows_per_block;
     if (fast)
         hipLaunchKernelGGL((k_detrend<T, TO, 1>), grid, dim3(256), 0, s, (const T *)in, ratio, rinv, (TO *)out, lines, samples, lpb);
     else
@@ -1438,23 +1344,19 @@ extern "C" int xsw_detrend(xsw_ctx *c, int64_t lines, int64_t samples, int32_t d
     // worker: staging copies, uploads, kernels and downloads of different chunks overlap).
     if (e != hipSuccess) return fail(c, XSW_EHIP, "detrend failed: %s", hipGetErrorString(e));
     const bool pinned = mem == XSW_MEM_HOST_PINNED;
-    const long long target_px = std::min<long long>(4LL << 20, std::max<long long>(1LL << 16, n / 16));
-    long long lpc = samples > 0 ? (target_px + samples - 1) / samples : lines;
-    if (lpc < 1) lpc = 1;
-    const long long nchunks = (lines + lpc - 1) / lpc;
-    const size_t max_px = (size_t)std::min<long long>(lpc, lines) * samples;
-    const size_t o_out = ((size_t)max_px * es + 255) & ~(size_t)255, total = o_out + max_px * os;
-    const int rc_det = run_chunks(c, nchunks, [&](long long k, xsw_ctx::Worker &w, std::string &err) -> int {
+    const ChunkPlan plan(lines, samples, 4LL << 20, 1, false);  // ~4 Mpx of whole lines
+    const size_t o_out = pad256(plan.max_px * es), total = o_out + plan.max_px * os;
+    const int rc_det = run_chunks(c, plan.nchunks, [&](long long k, xsw_ctx::Worker &w, std::string &err) -> int {
         int rc = worker_reserve(w, pinned ? 0 : total, total, err);
         if (rc) return rc;
-        const long long l0 = k * lpc, l1 = std::min((long long)lines, l0 + lpc);
-        const size_t px0 = (size_t)l0 * samples, npx = (size_t)(l1 - l0) * samples;
+        const ChunkPlan::Chunk ch = plan.chunk(k);
+        const size_t px0 = ch.px0, npx = ch.npx;
         const char *src = (const char *)sigma0 + px0 * es;
         char *dst = (char *)out + px0 * os;
         hipError_t ee;
         if (pinned) ee = hipMemcpyAsync(w.dev, src, npx * es, hipMemcpyHostToDevice, w.s);
         else { memcpy(w.pin, src, npx * es); ee = hipMemcpyAsync(w.dev, w.pin, npx * es, hipMemcpyHostToDevice, w.s); }
-        if (ee == hipSuccess) ee = launch(w.dev, w.dev + o_out, l1 - l0, w.s);
+        if (ee == hipSuccess) ee = launch(w.dev, w.dev + o_out, ch.lines, w.s);
         if (ee == hipSuccess) ee = hipMemcpyAsync(pinned ? dst : w.pin + o_out, w.dev + o_out, npx * os, hipMemcpyDeviceToHost, w.s);
         if (ee == hipSuccess) ee = hipStreamSynchronize(w.s);
         if (ee != hipSuccess) return seterr(err, XSW_EHIP, "detrend failed: %s", hipGetErrorString(ee));
@@ -1481,11 +1383,8 @@ static hipError_t launch_nesz(hipStream_t s, const void *noise, const void *inc,
     hipLaunchKernelGGL((k_nesz_fit<T>), dim3((unsigned)((lines + XSW_NESZ_LINES - 1) / XSW_NESZ_LINES)), dim3(XSW_NESZ_THREADS), 0, s, (const T *)noise, col,
                        x0, fit, lines, samples);
     // the write pass: column groups x line blocks, ~16 workgroups per CU
-    const long long egx = (samples + 256LL * XSW_NESZ_EV - 1) / (256LL * XSW_NESZ_EV);
-    long long enb = std::max<long long>(1, std::min<long long>((256LL * 16 + egx - 1) / egx, std::min<long long>(lines, 65535)));
-    const long long elpb = (lines + enb - 1) / enb;
-    enb = (lines + elpb - 1) / elpb;
-    hipLaunchKernelGGL((k_nesz_eval<sizeof(T) == 4>), dim3((unsigned)egx, (unsigned)enb), dim3(256), 0, s, col, fit, out, lines, samples, elpb);
+    const Strips e = strip_grid(lines, (samples + XSW_NESZ_EV - 1) / XSW_NESZ_EV);  // columns: groups of XSW_NESZ_EV samples
+    hipLaunchKernelGGL((k_nesz_eval<sizeof(T) == 4>), dim3((unsigned)e.gx, (unsigned)e.gy), dim3(256), 0, s, col, fit, out, lines, samples, e.rows_per_block);
     return hipGetLastError();
 }
 

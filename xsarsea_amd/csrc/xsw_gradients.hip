@@ -721,9 +721,9 @@ extern "C" int xsw_grad_area(xsw_ctx *c, int64_t lines, int64_t samples, int32_t
                              void *out)
 {
     if (!c) return XSW_EINVAL;
-    if (!in || !out || factor < 1 || lines < factor || samples < factor) return gfail(c, XSW_EINVAL, "grad_area: bad argument");
-    if (dtype != XSW_F32 && dtype != XSW_F64) return gfail(c, XSW_EINVAL, "dtype must be XSW_F32 or XSW_F64");
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    if (!in || !out || factor < 1 || lines < factor || samples < factor) return fail(c, XSW_EINVAL, "grad_area: bad argument");
+    if (dtype != XSW_F32 && dtype != XSW_F64) return fail(c, XSW_EINVAL, "dtype must be XSW_F32 or XSW_F64");
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
     const long long Lo = lines / factor, So = samples / factor, es = dtype == XSW_F32 ? 4 : 8;
     Buf b[2] = {{in, nullptr, (size_t)(lines * samples * es)}, {nullptr, out, (size_t)(Lo * So * es)}};
     const long long nblk = std::min<long long>((Lo * So + 255) / 256, 65536);
@@ -744,10 +744,10 @@ static int grad_r2(xsw_ctx *c, const char *what, int64_t lines, int64_t samples,
                    const void *in, double *out)
 {
     if (!c) return XSW_EINVAL;
-    if (!in || !out || lines < 2 || samples < 2) return gfail(c, XSW_EINVAL, "%s: bad argument (the raster needs 2 x 2 pixels)", what);
+    if (!in || !out || lines < 2 || samples < 2) return fail(c, XSW_EINVAL, "%s: bad argument (the raster needs 2 x 2 pixels)", what);
     if (int rc = check_dims(c, what, lines, samples)) return rc;
-    if (dtype != XSW_F32 && dtype != XSW_F64) return gfail(c, XSW_EINVAL, "dtype must be XSW_F32 or XSW_F64");
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    if (dtype != XSW_F32 && dtype != XSW_F64) return fail(c, XSW_EINVAL, "dtype must be XSW_F32 or XSW_F64");
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
     const int L1 = (int)lines, S1 = (int)samples, L2 = L1 / 2, S2 = S1 / 2, root = (int)(take_sqrt != 0);
     const long long es = dtype == XSW_F32 ? 4 : 8;
     Buf b[2] = {{in, nullptr, (size_t)(lines * samples * es)}, {nullptr, out, (size_t)L2 * S2 * 8}};
@@ -776,10 +776,10 @@ static int grad_local(xsw_ctx *c, const char *what, int64_t lines, int64_t sampl
 {
     if (!c) return XSW_EINVAL;
     if (!in || (!g2 && !SQ) || !g3 || !quality || lines < 2 || samples < 2)
-        return gfail(c, XSW_EINVAL, "%s: bad argument (the raster needs 2 x 2 pixels)", what);
+        return fail(c, XSW_EINVAL, "%s: bad argument (the raster needs 2 x 2 pixels)", what);
     if (int rc = check_dims(c, what, lines, samples)) return rc;
-    if (dtype != XSW_F32 && dtype != XSW_F64) return gfail(c, XSW_EINVAL, "dtype must be XSW_F32 or XSW_F64");
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    if (dtype != XSW_F32 && dtype != XSW_F64) return fail(c, XSW_EINVAL, "dtype must be XSW_F32 or XSW_F64");
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
     const int L1 = (int)lines, S1 = (int)samples, L2 = L1 / 2, S2 = S1 / 2;
     const size_t no = (size_t)L2 * S2;
     const long long es = dtype == XSW_F32 ? 4 : 8;
@@ -813,11 +813,11 @@ static int grad_hist(xsw_ctx *c, const char *what, int64_t lines, int64_t sample
 {
     if (!g2 || !quality || !rows || !cols || !weight || !used_ratio || lines < 1 || samples < 1 || window_lines < 1 || window_samples < 1 || n_rows < 1 ||
         n_cols < 1 || n_angles < 1)
-        return gfail(c, XSW_EINVAL, "%s: bad argument", what);
+        return fail(c, XSW_EINVAL, "%s: bad argument", what);
     if (!fits_int(lines, samples) || !fits_int(std::min<long long>(window_lines, lines) * std::min<long long>(window_samples, samples)))
-        return gfail(c, XSW_EINVAL, "%s: raster or window too large", what);
-    if (!fits_int((long long)n_rows * n_cols)) return gfail(c, XSW_EINVAL, "%s: too many windows", what);
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+        return fail(c, XSW_EINVAL, "%s: raster or window too large", what);
+    if (!fits_int((long long)n_rows * n_cols)) return fail(c, XSW_EINVAL, "%s: too many windows", what);
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
     const size_t npx = (size_t)lines * samples, nw = (size_t)n_rows * n_cols;
     Buf b[7] = {{g2, nullptr, npx * 16}, {quality, nullptr, npx * 8}, {rows, nullptr, (size_t)n_rows * 4}, {cols, nullptr, (size_t)n_cols * 4},
                 {nullptr, weight, nw * n_angles * 8}, {nullptr, used_ratio, nw * 8}, {keep, nullptr, keep ? npx : 0}};
@@ -850,7 +850,7 @@ extern "C" int xsw_grad_hist_masked(xsw_ctx *c, int64_t lines, int64_t samples, 
                                     int32_t normalise, double *weight, double *used_ratio)
 {
     if (!c) return XSW_EINVAL;
-    if (!keep) return gfail(c, XSW_EINVAL, "grad_hist_masked: keep is NULL (the unmasked histogram is xsw_grad_hist)");
+    if (!keep) return fail(c, XSW_EINVAL, "grad_hist_masked: keep is NULL (the unmasked histogram is xsw_grad_hist)");
     return grad_hist(c, "grad_hist_masked", lines, samples, mem, g2, quality, keep, window_lines, window_samples, n_rows, rows, n_cols, cols,
                      n_angles, angle_start, angle_step, normalise, weight, used_ratio);
 }
@@ -860,9 +860,9 @@ template <typename T>
 static int grad_keep(xsw_ctx *c, const char *what, int64_t lines, int64_t samples, int32_t mem, const T *src, KeepTest<T> test, int32_t block,
                      const uint8_t *and_with, uint8_t *out)
 {
-    if (!src || !out || block < 1 || lines < block || samples < block) return gfail(c, XSW_EINVAL, "%s: bad argument (block < 1 or an empty output)", what);
+    if (!src || !out || block < 1 || lines < block || samples < block) return fail(c, XSW_EINVAL, "%s: bad argument (block < 1 or an empty output)", what);
     if (int rc = check_dims(c, what, lines, samples)) return rc;
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
     const long long Lo = lines / block, So = samples / block, es = (long long)sizeof(T);
     const size_t no = (size_t)Lo * So;
     Buf b[3] = {{src, nullptr, (size_t)(lines * samples * es)}, {and_with, nullptr, and_with ? no : 0}, {nullptr, out, no}};
@@ -897,7 +897,7 @@ extern "C" int xsw_grad_keep_f64(xsw_ctx *c, int64_t lines, int64_t samples, int
                                  const uint8_t *and_with, uint8_t *out)
 {
     if (!c) return XSW_EINVAL;
-    if (std::isnan(threshold)) return gfail(c, XSW_EINVAL, "grad_keep_f64: the threshold is NaN");
+    if (std::isnan(threshold)) return fail(c, XSW_EINVAL, "grad_keep_f64: the threshold is NaN");
     KeepTest<double> test;
     test.thr = threshold;
     return grad_keep<double>(c, "grad_keep_f64", lines, samples, mem, src, test, block, and_with, out);
@@ -925,9 +925,9 @@ extern "C" int xsw_grad_smooth(xsw_ctx *c, int64_t lines, int64_t samples, int32
 {
     if (!c) return XSW_EINVAL;
     const int64_t f = coarsen ? 2 : 1;
-    if (!in || !out || lines < f || samples < f) return gfail(c, XSW_EINVAL, "grad_smooth: bad argument");
+    if (!in || !out || lines < f || samples < f) return fail(c, XSW_EINVAL, "grad_smooth: bad argument");
     if (int rc = check_dims(c, "grad_smooth", lines, samples)) return rc;
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
     const int S = (int)samples, Lo = (int)(lines / f), So = (int)(samples / f);
     Buf b[2] = {{in, nullptr, (size_t)(lines * samples * 8)}, {nullptr, out, (size_t)Lo * So * 8}};
     const dim3 grid((So + 63) / 64, (Lo + 3) / 4);
@@ -943,9 +943,9 @@ extern "C" int xsw_grad_smooth(xsw_ctx *c, int64_t lines, int64_t samples, int32
 extern "C" int xsw_grad_mean(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, const double *in, double *out)
 {
     if (!c) return XSW_EINVAL;
-    if (!in || !out || lines < 1 || samples < 1) return gfail(c, XSW_EINVAL, "grad_mean: bad argument");
+    if (!in || !out || lines < 1 || samples < 1) return fail(c, XSW_EINVAL, "grad_mean: bad argument");
     if (int rc = check_dims(c, "grad_mean", lines, samples)) return rc;
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
     const int L = (int)lines, S = (int)samples;
     Buf b[2] = {{in, nullptr, (size_t)L * S * 8}, {nullptr, out, (size_t)L * S * 8}};
     const dim3 grid((S + MT - 1) / MT, (L + MT - 1) / MT);
@@ -960,9 +960,9 @@ extern "C" int xsw_grad_filter(xsw_ctx *c, int64_t lines, int64_t samples, int32
 {
     if (!c) return XSW_EINVAL;
     if (!r2 || !g3 || !quality || !smooth4 || !out || lines < 2 || samples < 2)
-        return gfail(c, XSW_EINVAL, "grad_filter: bad argument (the half-resolution raster needs 2 x 2 pixels)");
+        return fail(c, XSW_EINVAL, "grad_filter: bad argument (the half-resolution raster needs 2 x 2 pixels)");
     if (int rc = check_dims(c, "grad_filter", lines, samples)) return rc;
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
     const int L = (int)lines, S = (int)samples, L4 = L / 2, S4 = S / 2;
     const size_t n = (size_t)L * S;
     Buf b[5] = {{r2, nullptr, n * 8}, {g3, nullptr, n * 8}, {quality, nullptr, n * 8}, {smooth4, nullptr, (size_t)L4 * S4 * 8}, {nullptr, out, 5 * n * 8}};

@@ -3,13 +3,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "xsw.h"
 #include "xsw_device.hpp"
+#include "xsw_plan.hpp"
 
 #ifndef XSW_ARENA_KEEP
 #define XSW_ARENA_KEEP ((size_t)24 << 30)
@@ -26,11 +30,7 @@ struct xsw_ctx {
     bool stats_chain = false;               // xsw_stats_enable(ctx, 2): the production chain keeps running, its kernels count what they score
     bool timing_on = false;                 // xsw_timing_enable: HIP events around the kernels of every device-memory inversion
     std::vector<hipEvent_t> timing_events;  // quintuples (start, after k_invert_band, k_invert_band2, k_invert_blocks, k_invert_list) on the launch stream
-    unsigned *d_list = nullptr;  // hand-over k_invert_band -> k_invert_list: [0] = count, [16..] = pixel indices
-    size_t list_cap = 0;         // entries (context-owned, grown on demand: an eighth of the largest raster seen)
-    unsigned long long *d_masks = nullptr;  // strip masks (2 x mask_strips words, after the lists in the same allocation)
-    void *d_rec = nullptr;                  // list B's records (after the masks)
-    size_t mask_strips = 0;
+    WorkLists lists;  // of the device-raster path (context-owned, grown on demand: list G an eighth of the largest raster seen)
     double *d_ratio = nullptr;  // detrend ratio row (context-owned, grown on demand)
     size_t ratio_cap = 0;
     void *nesz_scratch = nullptr;  // xsw_nesz_flatten: column partials + means (context-owned, grown on demand)
@@ -70,32 +70,54 @@ static inline int seterr(std::string &e, int code, const char *fmt, ...)
     return code;
 }
 
-// Where an inversion launches: its stream and the work list that hands pixels from k_invert_band to k_invert_list (device
+// The text xsw_last_error returns: the context's, or this thread's when there is no context yet (xsw_ctx_create).
+inline std::string &create_err()
+{
+    static thread_local std::string e;
+    return e;
+}
+static inline int fail(xsw_ctx *c, int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    (c ? c->err : create_err()) = buf;
+    return code;
+}
+
+// Environment knobs (experiments, A/B measurements, the tests' forced routes).  A caller keeps the value in a function-local
+// static, so a knob is read once per process.  env_int: the variable's integer clamped to [lo, hi], or dflt when it is unset.
+static inline long long env_int(const char *name, long long dflt, long long lo = LLONG_MIN, long long hi = LLONG_MAX)
+{
+    const char *v = getenv(name);
+    return v ? std::min(std::max(atoll(v), lo), hi) : dflt;
+}
+static inline bool env_flag(const char *name) { return getenv(name) != nullptr; }
+
+// Where an inversion launches: its stream and the work lists that hand pixels from k_invert_band to the other kernels (device
 // rasters: the context's; host rasters: the worker's own, so that the chunks of different workers run side by side).
 struct LaunchCtl {
     hipStream_t stream;
-    unsigned *list;    // [0] = count, [16 ..] = entries; nullptr: one-kernel path
-    size_t list_cap;   // entries
-    bool timing;       // xsw_timing_enable events (context stream only)
-    unsigned long long *masks = nullptr;  // strip masks (KArgs::mask_g, then mask_b), mask_strips words each; nullptr: none
-    size_t mask_strips = 0;
-    void *rec_b = nullptr;  // XSW_LIST_B_SHARE * list_cap records of XSW_REC_BYTES (KArgs::rec_b); nullptr: list B holds pixel indices
+    bool timing;      // xsw_timing_enable events (context stream only)
+    WorkLists lists;  // base == nullptr: one-kernel path
 };
 
-
-// Work lists of one launch, side by side in one allocation: [0..15] counters, then list G (k_invert_list) of LaunchCtl::list_cap
-// entries, list B (k_invert_band2) of XSW_LIST_B_SHARE times as many and list C (k_invert_blocks) of XSW_LIST_C_SHARE times as
-// many: on the scenes whose a-priori wind is far from the sigma0 contour HALF the pixels are k_invert_band2's (an overflowing
-// list B sends the rest through the strip mask, where stage 1 is redone for them).  With list_cap = an eighth of the raster the
-// lists take 4.5 B and list B's records 24 B per pixel of the largest raster seen.
-#ifndef XSW_LIST_B_SHARE
-#define XSW_LIST_B_SHARE 4
-#endif
-#ifndef XSW_LIST_C_SHARE
-#define XSW_LIST_C_SHARE 4
-#endif
-#define XSW_LISTS_TOTAL (1 + XSW_LIST_B_SHARE + XSW_LIST_C_SHARE)
-#define XSW_REC_BYTES 48  // sizeof(BandRec) (xsw_band.hpp; static_assert in xsw_invert_tu.hip): list B's records follow the strip masks
+// A for one chunk of its raster: the chunk's shape, and every raster pointer that is set moved to the chunk's first pixel
+// (es: bytes of an input element, os: of an output pixel).
+static inline xsw::KArgs slice(const xsw::KArgs &A, const ChunkPlan::Chunk &ch, size_t es, size_t os)
+{
+    auto shift = [&](auto *p, size_t elem) -> decltype(p) { return p ? (decltype(p))((uintptr_t)p + ch.px0 * elem) : nullptr; };
+    xsw::KArgs B = A;
+    B.lines = ch.lines; B.samples = ch.samples; B.n = (long long)ch.npx;
+    B.inc = shift(A.inc, es); B.s_co = shift(A.s_co, es); B.s_cr = shift(A.s_cr, es);
+    B.dsig_cr = shift(A.dsig_cr, es); B.anc = shift(A.anc, es * 2);
+    B.out_co = shift(A.out_co, os); B.out_cr = shift(A.out_cr, os);
+    B.out_idx = shift(A.out_idx, 12);
+    B.code_co = shift(A.code_co, 4); B.code_cr = shift(A.code_cr, 4);
+    return B;
+}
 
 // One (input dtype, output dtype) pair of the inversion launches per translation unit (xsw_invert_tu.hip, -DXSW_PAIR=0..3:
 // f32->f32, f32->f64, f64->f32, f64->f64), so that the four sets of kernel instantiations compile side by side.

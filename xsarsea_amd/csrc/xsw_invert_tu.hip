@@ -3,7 +3,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <string>
 
 #include "xsw_host.hpp"
@@ -54,15 +53,14 @@ static int launch_invert(xsw_ctx *c, const KArgs &A_in, int algo, const LaunchCt
     // Two-kernel fast path: k_invert_band finishes every pixel the band rule decides (monotone LUT rows, finite inputs,
     // unique minimum; cross-pol by the interval rule) and appends the rest to a work list; k_invert_list inverts those
     // (all tiles, should the list overflow).
-    static const int block_min_env = getenv("XSW_BLOCK_MIN") ? std::max(0, atoi(getenv("XSW_BLOCK_MIN"))) : XSW_BLOCK_MIN;
+    static const int block_min_env = (int)env_int("XSW_BLOCK_MIN", XSW_BLOCK_MIN, 0);
     A.block_min = block_min_env;  // windows of at least this many candidates: block pyramid (general kernel)
-    static const bool band_off = getenv("XSW_NO_BAND") != nullptr;  // experiments / A-B measurements only
-    if (algo == XSW_ALGO_PRUNED && !band_off && lc.list && A.s_co && c->T.prunable && c->T.mono_rows && c->T.inv_rows && c->T.co_off32 && c->T.band_mul24 &&
+    static const bool band_off = env_flag("XSW_NO_BAND");  // experiments / A-B measurements only
+    if (algo == XSW_ALGO_PRUNED && !band_off && lc.lists.base && A.s_co && c->T.prunable && c->T.mono_rows && c->T.inv_rows && c->T.co_off32 && c->T.band_mul24 &&
         (!A.s_cr || c->T.cr_monotone) && A.n < (1LL << 32)) {
         KArgs B = A;
-        B.list_count = lc.list;
-        B.list = lc.list + 16;
-        B.list_cap = (unsigned)std::min<size_t>(lc.list_cap, 0xfffffff0u);
+        const WorkLists &wl = lc.lists;
+        B.list_count = wl.count(WorkLists::G); B.list = wl.entries(WorkLists::G); B.list_cap = wl.cap(WorkLists::G);
         // list B (k_invert_band -> k_invert_band2) follows list G: a pixel whose band holds XSW_LONG_RUN (5) or more rows along the
         // a-priori direction is handed to k_invert_band2 -- one such pixel holds up every pixel of its pass in k_invert_band, and
         // where the a-priori wind is far from the sigma0 contour most pixels are such.  XSW_LONG_RUN=0: never (k_invert_band
@@ -70,44 +68,44 @@ static int launch_invert(xsw_ctx *c, const KArgs &A_in, int algo, const LaunchCt
         // (5 since round 5: with the stage-1 live arc and the cheaper k_invert_band2 re-measured on the hard scenes, 4 / 5 / 6 / 8 rows: cyclone band
         // 7669 / 8052 / 7971 / 7489 Mpx/s, outliers 5 % 3640 / 3885 / 3955 / 3860, a-priori x 0.6 1925 / 2073 / 2081 / 1908, x 1.6 1586 / 1610 /
         // 1571 / 1480, inc 17-33 x 1.6 979 / 1009 / 1030 / 990; the 20000 x 20000 benchmark scene 37.31 / 37.44 / 37.77 ms: within its noise for 4 / 5)
-        static const int long_run_env = getenv("XSW_LONG_RUN") ? std::max(0, atoi(getenv("XSW_LONG_RUN"))) : XSW_LONG_RUN_DEFAULT;
+        static const int long_run_env = (int)env_int("XSW_LONG_RUN", XSW_LONG_RUN_DEFAULT, 0);
         const bool count_inst = A.stats && !A.stats_chain;  // the statistics instantiation: k_invert_band sweeps every window itself and counts
         const bool band2 = long_run_env > 0 && !count_inst;
-        if (band2) { B.list_b_count = lc.list + 1; B.list_b = lc.list + 16 + lc.list_cap; B.list_b_cap = (unsigned)std::min<size_t>(XSW_LIST_B_SHARE * lc.list_cap, 0xfffffff0u); }
-        static const bool records_off = getenv("XSW_NO_RECORDS") != nullptr;  // A/B measurements and the tests of the index-list route
-        static_assert(sizeof(BandRec) == XSW_REC_BYTES, "XSW_REC_BYTES (xsw_host.hpp) is sizeof(BandRec)");
-        B.rec_b = (band2 && !records_off) ? lc.rec_b : nullptr;
+        if (band2) { B.list_b_count = wl.count(WorkLists::B); B.list_b = wl.entries(WorkLists::B); B.list_b_cap = wl.cap(WorkLists::B); }
+        static const bool records_off = env_flag("XSW_NO_RECORDS");  // A/B measurements and the tests of the index-list route
+        static_assert(sizeof(BandRec) == XSW_REC_BYTES, "XSW_REC_BYTES (xsw_plan.hpp) is sizeof(BandRec)");
+        B.rec_b = (band2 && !records_off) ? wl.records() : nullptr;
         // list C (k_invert_band -> k_invert_blocks): the finite pixels the band rule is not for.  XSW_NO_BLOCKS_KERNEL=1: they stay on
         // list G, i.e. with k_invert_list (A/B measurements and the tests of that route)
-        static const bool blocks_kernel_off = getenv("XSW_NO_BLOCKS_KERNEL") != nullptr;
+        static const bool blocks_kernel_off = env_flag("XSW_NO_BLOCKS_KERNEL");
         const bool blocks3 = c->T.blk != nullptr && c->T.blk_span_ok && !blocks_kernel_off && c->T.n_w < 32768 && c->T.n_phi < 32768;
-        if (blocks3) { B.list_c_count = lc.list + 2; B.list_c = lc.list + 16 + (1 + XSW_LIST_B_SHARE) * lc.list_cap; B.list_c_cap = (unsigned)std::min<size_t>(XSW_LIST_C_SHARE * lc.list_cap, 0xfffffff0u); }
+        if (blocks3) { B.list_c_count = wl.count(WorkLists::C); B.list_c = wl.entries(WorkLists::C); B.list_c_cap = wl.cap(WorkLists::C); }
         B.long_run = long_run_env;
-        static const int area_max_env = getenv("XSW_B2_AREA") ? std::max(1, atoi(getenv("XSW_B2_AREA"))) : XSW_B2_AREA;
+        static const int area_max_env = (int)env_int("XSW_B2_AREA", XSW_B2_AREA, 1);
         B.area_max = c->T.blk ? area_max_env : 0x7fffffff;  // (without the block tables the general kernel has nothing better to offer)
-        static const int crowd_env = getenv("XSW_B2_CROWD") ? std::max(1, atoi(getenv("XSW_B2_CROWD"))) : XSW_B2_CROWD;
+        static const int crowd_env = (int)env_int("XSW_B2_CROWD", XSW_B2_CROWD, 1);
         B.b2_crowd = crowd_env;  // (65: never)
         B.area_crowd_max = 1 << 20;
-        static const int wide_env = getenv("XSW_B2_WIDE") ? std::max(0, atoi(getenv("XSW_B2_WIDE"))) : XSW_B2_WIDE;
+        static const int wide_env = (int)env_int("XSW_B2_WIDE", XSW_B2_WIDE, 0);
         B.wide_min = wide_env > 0 ? wide_env : 0x7fffffff;
-        static const int arc_min_env = getenv("XSW_ARC_MIN") ? atoi(getenv("XSW_ARC_MIN")) : XSW_ARC_MIN;
-        static const int arc_crowd_env = getenv("XSW_ARC_CROWD") ? std::max(1, atoi(getenv("XSW_ARC_CROWD"))) : XSW_ARC_CROWD;
+        static const int arc_min_env = (int)env_int("XSW_ARC_MIN", XSW_ARC_MIN);
+        static const int arc_crowd_env = (int)env_int("XSW_ARC_CROWD", XSW_ARC_CROWD, 1);
         B.arc_min = (arc_min_env > 0 && c->T.csphi32) ? arc_min_env : 0x7fffffff;
         B.arc_crowd = arc_crowd_env;
-        static const int refine_min_env = getenv("XSW_B2_REFINE_MIN") ? std::max(0, atoi(getenv("XSW_B2_REFINE_MIN"))) : XSW_B2_REFINE_MIN;
+        static const int refine_min_env = (int)env_int("XSW_B2_REFINE_MIN", XSW_B2_REFINE_MIN, 0);
         B.b2_refine_min = refine_min_env;
-        static const int b2_rows_env = getenv("XSW_B2_ROWS_MAX") ? std::max(1, atoi(getenv("XSW_B2_ROWS_MAX"))) : XSW_B2_ROWS_MAX;
+        static const int b2_rows_env = (int)env_int("XSW_B2_ROWS_MAX", XSW_B2_ROWS_MAX, 1);
         B.b2_rows_max = b2_rows_env;
-        static const int tail_max_env = getenv("XSW_TAIL_SWEEP") ? std::min(std::max(0, atoi(getenv("XSW_TAIL_SWEEP"))), 30000) : XSW_TAIL_SWEEP;
+        static const int tail_max_env = (int)env_int("XSW_TAIL_SWEEP", XSW_TAIL_SWEEP, 0, 30000);
         B.tail_max = (band2 && c->T.tail_min) ? tail_max_env : 0;  // (the tail rows are k_invert_band2's to sweep)
         // strip masks: what the consumers walk when a list overflows (only the marked pixels instead of the whole raster)
-        static const bool masks_off = getenv("XSW_NO_STRIP_MASKS") != nullptr;  // A/B measurements and the tests of the old route
+        static const bool masks_off = env_flag("XSW_NO_STRIP_MASKS");  // A/B measurements and the tests of the old route
         const size_t nstrips = (size_t)(strips_per_line * A.lines);
-        if (lc.masks && nstrips <= lc.mask_strips && !masks_off) {
-            B.mask_g = lc.masks; B.mask_b = lc.masks + nstrips;  // side by side: one reset (0.25 B per pixel)
-            if (hipMemsetAsync(lc.masks, 0, 2 * nstrips * sizeof(unsigned long long), lc.stream) != hipSuccess) return seterr(err, XSW_EHIP, "strip-mask reset failed");
+        if (nstrips <= wl.mask_strips && !masks_off) {
+            B.mask_g = wl.masks(); B.mask_b = wl.masks() + nstrips;  // side by side: one reset (0.25 B per pixel)
+            if (hipMemsetAsync(wl.masks(), 0, 2 * nstrips * sizeof(unsigned long long), lc.stream) != hipSuccess) return seterr(err, XSW_EHIP, "strip-mask reset failed");
         }
-        if (hipMemsetAsync(lc.list, 0, 3 * sizeof(unsigned), lc.stream) != hipSuccess) return seterr(err, XSW_EHIP, "work-list reset failed");
+        if (hipMemsetAsync(wl.count(WorkLists::G), 0, 3 * sizeof(unsigned), lc.stream) != hipSuccess) return seterr(err, XSW_EHIP, "work-list reset failed");
         const unsigned list_blocks = (unsigned)std::min<long long>(nblocks, 256 * 8);  // 8 waves per SIMD
         // k_invert_band: x = XCD lane + 8 * line group, y = tile column inside the XCD's range (see the kernel)
         const long long cols_per_xcd = (strips_per_line + 7) / 8;

@@ -1,26 +1,13 @@
-// Host side of the raster entry points outside xsw.hip (xsw_gradients.hip, xsw_streaks.hip): the error text, the argument
-// checks and launch grids they share, and one call's buffers on the XSW_MEM_HOST and XSW_MEM_DEVICE routes.
+// Host side of the raster entry points outside xsw.hip (xsw_gradients.hip, xsw_streaks.hip): the argument checks they
+// share (their launch grid, strip_grid, is xsw_plan.hpp's), and one call's buffers on the XSW_MEM_HOST and XSW_MEM_DEVICE routes.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 
 #include "xsw_host.hpp"
 
 namespace {
-
-static int gfail(xsw_ctx *c, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    c->err = buf;
-    return code;
-}
 
 // Host buffers of one call: uploaded to temporaries, the launch runs on the context's stream, outputs come back, all before
 // the call returns.  Device buffers: the launch alone, asynchronous on the context's stream.
@@ -34,30 +21,30 @@ struct Buf {
 template <size_t N, typename Launch>
 static int run(xsw_ctx *c, int32_t mem, Buf (&b)[N], Launch &&launch, const char *what)
 {
-    if (hipSetDevice(c->device) != hipSuccess) return gfail(c, XSW_EHIP, "%s: hipSetDevice failed", what);
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, XSW_EHIP, "%s: hipSetDevice failed", what);
     if (mem == XSW_MEM_DEVICE) {
         for (auto &x : b) x.dev = x.host_out ? x.host_out : (void *)x.host_in;
         launch(b);
         const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? XSW_OK : gfail(c, XSW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
+        return e == hipSuccess ? XSW_OK : fail(c, XSW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
     }
     int rc = XSW_OK;
     hipError_t e = hipSuccess;
     for (auto &x : b)
         if (e == hipSuccess && x.bytes) e = hipMalloc(&x.dev, x.bytes);
-    if (e != hipSuccess) rc = gfail(c, XSW_ENOMEM, "%s: hipMalloc failed (%s)", what, hipGetErrorString(e));
+    if (e != hipSuccess) rc = fail(c, XSW_ENOMEM, "%s: hipMalloc failed (%s)", what, hipGetErrorString(e));
     for (auto &x : b)
         if (!rc && x.host_in && x.bytes && (e = hipMemcpyAsync(x.dev, x.host_in, x.bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
-            rc = gfail(c, XSW_EHIP, "%s: upload failed (%s)", what, hipGetErrorString(e));
+            rc = fail(c, XSW_EHIP, "%s: upload failed (%s)", what, hipGetErrorString(e));
     if (!rc) {
         launch(b);
-        if ((e = hipGetLastError()) != hipSuccess) rc = gfail(c, XSW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
+        if ((e = hipGetLastError()) != hipSuccess) rc = fail(c, XSW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
     }
     for (auto &x : b)
         if (!rc && x.host_out && x.bytes && (e = hipMemcpyAsync(x.host_out, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
-            rc = gfail(c, XSW_EHIP, "%s: download failed (%s)", what, hipGetErrorString(e));
+            rc = fail(c, XSW_EHIP, "%s: download failed (%s)", what, hipGetErrorString(e));
     e = hipStreamSynchronize(c->stream);  // also before freeing after a failure: queued work may still use the temporaries
-    if (!rc && e != hipSuccess) rc = gfail(c, XSW_EHIP, "%s: %s", what, hipGetErrorString(e));
+    if (!rc && e != hipSuccess) rc = fail(c, XSW_EHIP, "%s: %s", what, hipGetErrorString(e));
     for (auto &x : b)
         if (x.dev) (void)hipFree(x.dev);
     return rc;
@@ -71,28 +58,13 @@ static bool fits_int(int64_t a, int64_t b = 0) { return a <= 0x7fffffffLL && b <
 // XSW_OK, or XSW_EINVAL with "<what>: raster too large" for a raster whose axes do not fit int.
 static int check_dims(xsw_ctx *c, const char *what, int64_t lines, int64_t samples)
 {
-    return fits_int(lines, samples) ? XSW_OK : gfail(c, XSW_EINVAL, "%s: raster too large", what);
+    return fits_int(lines, samples) ? XSW_OK : fail(c, XSW_EINVAL, "%s: raster too large", what);
 }
 
 // XSW_OK, or XSW_EINVAL when a 2-D grid of tiles has more rows than one launch takes.
 static int check_grid(xsw_ctx *c, const char *what, const dim3 &grid)
 {
-    return grid.y <= 65535 ? XSW_OK : gfail(c, XSW_EINVAL, "%s: raster too large for one launch", what);
-}
-
-// The grid of k_detrend for a rows x cols raster: about 16 workgroups per CU, each a 256-column strip of a block of rows.
-struct Strips {
-    long long gx, gy, rows_per_block;
-};
-static Strips strip_grid(long long rows, long long cols)
-{
-    Strips s;
-    s.gx = (cols + 255) / 256;
-    s.gy = (256LL * 16 + s.gx - 1) / s.gx;
-    s.gy = std::max<long long>(1, std::min<long long>(std::min<long long>(s.gy, rows), 65535));
-    s.rows_per_block = (rows + s.gy - 1) / s.gy;
-    s.gy = (rows + s.rows_per_block - 1) / s.rows_per_block;
-    return s;
+    return grid.y <= 65535 ? XSW_OK : fail(c, XSW_EINVAL, "%s: raster too large for one launch", what);
 }
 
 }  // namespace

@@ -198,11 +198,11 @@ extern "C" int xsw_streaks_peak(xsw_ctx *c, int64_t n_lead, int64_t n_windows, i
 {
     if (!c) return XSW_EINVAL;
     if (!weight || !used_ratio || !index || !weight_out || !used_ratio_out || n_lead < 1 || n_windows < 1)
-        return gfail(c, XSW_EINVAL, "streaks_peak: bad argument");
+        return fail(c, XSW_EINVAL, "streaks_peak: bad argument");
     if (n_angles < PEAK_MIN_ANGLES || n_angles > PEAK_MAX_ANGLES)
-        return gfail(c, XSW_EINVAL, "streaks_peak: n_angles must be %d .. %d, not %d", PEAK_MIN_ANGLES, PEAK_MAX_ANGLES, (int)n_angles);
-    if (!fits_int(n_windows, n_lead)) return gfail(c, XSW_EINVAL, "streaks_peak: too many windows");
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+        return fail(c, XSW_EINVAL, "streaks_peak: n_angles must be %d .. %d, not %d", PEAK_MIN_ANGLES, PEAK_MAX_ANGLES, (int)n_angles);
+    if (!fits_int(n_windows, n_lead)) return fail(c, XSW_EINVAL, "streaks_peak: too many windows");
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
     const size_t nw = (size_t)n_windows, C = (size_t)n_lead;
     Buf b[5] = {{weight, nullptr, C * nw * n_angles * 8}, {used_ratio, nullptr, C * nw * 8}, {nullptr, index, nw * 4}, {nullptr, weight_out, nw * 8},
                 {nullptr, used_ratio_out, nw * 8}};
@@ -218,9 +218,9 @@ extern "C" int xsw_streaks_resolve(xsw_ctx *c, int64_t n_windows, int32_t mem, c
                                    const double *ancillary, double min_weight, double min_used_ratio, double *out)
 {
     if (!c) return XSW_EINVAL;
-    if (!dirs || !weight || !used_ratio || !ancillary || !out || n_windows < 1) return gfail(c, XSW_EINVAL, "streaks_resolve: bad argument");
-    if (!fits_int(n_windows)) return gfail(c, XSW_EINVAL, "streaks_resolve: too many windows");
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    if (!dirs || !weight || !used_ratio || !ancillary || !out || n_windows < 1) return fail(c, XSW_EINVAL, "streaks_resolve: bad argument");
+    if (!fits_int(n_windows)) return fail(c, XSW_EINVAL, "streaks_resolve: too many windows");
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
     const size_t nw = (size_t)n_windows;
     Buf b[5] = {{dirs, nullptr, nw * 16}, {weight, nullptr, nw * 8}, {used_ratio, nullptr, nw * 8}, {ancillary, nullptr, nw * 16}, {nullptr, out, nw * 16}};
     return run(c, mem, b, [&](Buf (&x)[5]) {
@@ -236,9 +236,9 @@ extern "C" int xsw_streaks_ancillary(xsw_ctx *c, int64_t lines, int64_t samples,
 {
     if (!c) return XSW_EINVAL;
     if (!ancillary || !dirs || !line_first || !line_t || !sample_first || !sample_t || !out || lines < 1 || samples < 1 || n_rows < 1 || n_cols < 1)
-        return gfail(c, XSW_EINVAL, "streaks_ancillary: bad argument");
+        return fail(c, XSW_EINVAL, "streaks_ancillary: bad argument");
     if (int rc = check_dims(c, "streaks_ancillary", lines, samples)) return rc;
-    if (bad_mem(mem)) return gfail(c, XSW_EINVAL, "bad mem kind");
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
     const size_t npx = (size_t)lines * samples;
     Buf b[7] = {{ancillary, nullptr, npx * 16}, {dirs, nullptr, (size_t)n_rows * n_cols * 16}, {line_first, nullptr, (size_t)lines * 4},
                 {line_t, nullptr, (size_t)lines * 8}, {sample_first, nullptr, (size_t)samples * 4}, {sample_t, nullptr, (size_t)samples * 8},
