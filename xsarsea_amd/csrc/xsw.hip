@@ -73,10 +73,11 @@ extern "C" int xsw_ctx_create(int device, xsw_ctx **out)
     return XSW_OK;
 }
 
-static void free_all(std::vector<void *> &v)
+static void worker_release(xsw_ctx::Worker &w)
 {
-    for (void *p : v) (void)hipFree(p);
-    v.clear();
+    if (w.s) (void)hipStreamSynchronize(w.s);
+    (void)grow(w.pin, w.pin_cap, 0, nullptr, true);
+    (void)grow(w.dev, w.dev_cap, 0);
 }
 
 extern "C" int xsw_ctx_destroy(xsw_ctx *c)
@@ -87,15 +88,14 @@ extern "C" int xsw_ctx_destroy(xsw_ctx *c)
     free_all(c->co_allocs);
     free_all(c->cr_allocs);
     if (c->d_stats) (void)hipFree(c->d_stats);
-    if (c->d_ratio) (void)hipFree(c->d_ratio);
-    if (c->lists.base) (void)hipFree(c->lists.base);
-    if (c->nesz_scratch) (void)hipFree(c->nesz_scratch);
+    (void)grow(c->d_ratio, c->ratio_cap, 0);
+    (void)grow(c->lists.base, c->lists_bytes, 0);
+    (void)grow(c->nesz_scratch, c->nesz_cap, 0);
     for (hipEvent_t e : c->timing_events) (void)hipEventDestroy(e);
-    if (c->arena) (void)hipFree(c->arena);
+    (void)grow(c->arena, c->arena_cap, 0);
     for (auto &w : c->workers) {
-        if (w.s) { (void)hipStreamSynchronize(w.s); (void)hipStreamDestroy(w.s); }
-        if (w.pin) (void)hipHostFree(w.pin);
-        if (w.dev) (void)hipFree(w.dev);
+        worker_release(w);
+        if (w.s) (void)hipStreamDestroy(w.s);
     }
     for (void *p : c->host_allocs) (void)hipHostFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -129,14 +129,6 @@ extern "C" int xsw_use_own_stream(xsw_ctx *c)
 }
 
 static int host_thread_count(const xsw_ctx *c);
-static void worker_release(xsw_ctx::Worker &w)
-{
-    if (w.s) (void)hipStreamSynchronize(w.s);
-    if (w.pin) (void)hipHostFree(w.pin);
-    if (w.dev) (void)hipFree(w.dev);
-    w.pin = w.dev = nullptr;
-    w.pin_cap = w.dev_cap = 0;
-}
 
 // Staging kept between calls: each worker of the host-memory paths owns a page-locked buffer and a device buffer of one chunk
 // (float32 mono: ~40 MB each; float64 dual-pol: ~110 MB each), i.e. up to threads x chunk of pinned host memory per context.
@@ -288,45 +280,6 @@ extern "C" int xsw_stats_read_chain(xsw_ctx *c, xsw_chain_stats *out)
 }
 
 // ---------------------------------------------------------------------------------------- LUT upload
-static bool strictly_ascending(const double *a, int n)
-{
-    for (int i = 1; i < n; ++i)
-        if (!(a[i] > a[i - 1])) return false;
-    return true;
-}
-// "uniform" to the error budget the pruned kernels' screening assumes: they score with w_i = w0 + i*step (forward
-// differences) and re-score only candidates within 1e-9 (1 + |J_min| + m2) of the screening minimum with the real axis
-// values, so an axis point may be off its grid position by no more than ~1e-12 relative (dJ/dw is O(10..100)): np.linspace
-// axes are within a few ulps and pass; an axis stored in float32, or perturbed by 1e-7 of a step, takes the exact kernel.
-static bool uniform_axis(const double *a, int n)
-{
-    if (n < 2) return false;
-    const double step = (a[n - 1] - a[0]) / (n - 1);
-    if (!(step > 0) || !std::isfinite(step)) return false;
-    const double tol = 1e-12 * std::max(std::max(std::fabs(a[0]), std::fabs(a[n - 1])), step);
-    for (int i = 0; i < n; ++i)
-        if (!(std::fabs(a[i] - (a[0] + i * step)) <= tol)) return false;
-    return true;
-}
-static bool all_finite(const double *a, size_t n)
-{
-    for (size_t i = 0; i < n; ++i)
-        if (!std::isfinite(a[i])) return false;
-    return true;
-}
-
-template <typename V>
-static int upload(xsw_ctx *c, std::vector<void *> &owner, const V *host, size_t count, const V **dev)
-{
-    void *p = nullptr;
-    HIPCHK(c, hipMalloc(&p, count * sizeof(V) + 64));
-    owner.push_back(p);
-    HIPCHK(c, hipMemcpyAsync(p, host, count * sizeof(V), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *dev = (const V *)p;
-    return XSW_OK;
-}
-
 // Installs a co-pol LUT.  The dense dB table [n_inc][n_wspd][n_phi] comes from the host (l->db) or is already on the
 // device (d_dense, built by xsw_lut_build); the padded float64 copy, the float32 copy, the finiteness flag and max |dB|
 // are produced on the device either way (k_pad_co).
@@ -346,232 +299,128 @@ static int install_co(xsw_ctx *c, const xsw_lut *l, const double *d_dense)
     c->have_co = false;
     DevTables &T = c->T;
     const int nI = l->n_inc, nW = l->n_wspd, nP = l->n_phi;
-    const int ppad = (nP + 3) & ~3, wpad = (nW + 3) & ~3;
-    int rc;
-    const size_t n_dense = (size_t)nI * nW * nP;
-    const size_t n_pad = (size_t)nI * nW * ppad + (size_t)260 * ppad;  // + slack rows: kernels read 4 row groups ahead unmasked
-    void *tmp_dense = nullptr;
+    const CoGeometry g{nI, nW, nP};
+    const hipStream_t st = c->stream;
+
+    // the dense table on the device: the caller's (xsw_lut_build), or a temporary of this call
+    CallTemps tmp(st);
     if (!d_dense) {
-        HIPCHK(c, hipMalloc(&tmp_dense, n_dense * sizeof(double)));
-        hipError_t e = hipMemcpyAsync(tmp_dense, l->db, n_dense * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { (void)hipFree(tmp_dense); return fail(c, XSW_EHIP, "LUT upload failed: %s", hipGetErrorString(e)); }
-        d_dense = (const double *)tmp_dense;
+        d_dense = (const double *)tmp.alloc(g.n_dense * sizeof(double), l->db);
+        if (tmp.refused) return fail(c, tmp.code(), "LUT install failed: %s", hipGetErrorString(tmp.err));
+        if (!tmp.ok()) return fail(c, XSW_EHIP, "LUT upload failed: %s", hipGetErrorString(tmp.err));
     }
-    bool lut_finite = false;
-    {
-        double *d_co = nullptr;
-        float *d_co32 = nullptr;
-        unsigned long long *d_flags = nullptr, h_flags[2] = {0, 0};
-        hipError_t e = hipMalloc((void **)&d_co, n_pad * sizeof(double) + 64);
-        if (e == hipSuccess) { c->co_allocs.push_back(d_co); e = hipMalloc((void **)&d_co32, n_pad * sizeof(float) + 64); }
-        if (e == hipSuccess) { c->co_allocs.push_back(d_co32); e = hipMalloc((void **)&d_flags, 2 * sizeof(unsigned long long)); }
-        if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, 2 * sizeof(unsigned long long), c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_co + (size_t)nI * nW * ppad, 0, (size_t)260 * ppad * sizeof(double), c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_co32 + (size_t)nI * nW * ppad, 0, (size_t)260 * ppad * sizeof(float), c->stream);
-        if (e == hipSuccess) {
-            const long long rows = (long long)nI * nW;
-            hipLaunchKernelGGL(k_pad_co, dim3((unsigned)std::min<long long>((rows + 3) / 4, 256 * 32)), dim3(256), 0, c->stream, d_dense, d_co,
-                               d_co32, nP, ppad, rows, d_flags);
-            e = hipGetLastError();
-        }
-        int *d_mono = nullptr;
-        std::vector<int> init((size_t)nI, nW);  // read by the copy below until the stream is synchronised at the end of this block
-        if (e == hipSuccess) e = hipMalloc((void **)&d_mono, (size_t)nI * sizeof(int) + 64);
-        if (e == hipSuccess) {
-            c->co_allocs.push_back(d_mono);
-            // on the launch stream, in order with k_mono_rows (not a null-stream copy whose completion the kernel would rely on)
-            e = hipMemcpyAsync(d_mono, init.data(), (size_t)nI * sizeof(int), hipMemcpyHostToDevice, c->stream);
-        }
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_mono_rows, dim3((unsigned)(((long long)nI * nP + 255) / 256)), dim3(256), 0, c->stream, d_dense, nI, nW, nP, d_mono);
-            e = hipGetLastError();
-        }
-        T.mono_rows = d_mono;
-        T.tail_min = nullptr;
-        static const bool tail_off = env_flag("XSW_NO_TAIL_CUT");  // A/B measurements only
-        if (e == hipSuccess && !tail_off) {
-            double *d_tail = nullptr;
-            if (hipMalloc((void **)&d_tail, (size_t)nI * (XSW_TAIL_LEVELS + 1) * ppad * sizeof(double) + 64) == hipSuccess) {
-                c->co_allocs.push_back(d_tail);
-                hipLaunchKernelGGL(k_tail_min, dim3((unsigned)nI), dim3(256), 0, c->stream, d_dense, nW, nP, (int)ppad, d_mono, d_tail);
-                if (hipGetLastError() == hipSuccess) T.tail_min = d_tail;
-            } else (void)hipGetLastError();
-        }
-        // inverse of the monotone rows (co_band_pass starts its sweep from a table look-up instead of a bisection)
-        T.inv_rows = nullptr; T.inv_grid = nullptr;
-        const size_t inv_n = (size_t)nI * XSW_INV_BINS * ppad;
-        if (e == hipSuccess && nW < 65536 && nI < 65536 && inv_n * sizeof(unsigned short) < ((size_t)1 << 32)) {
-            unsigned short *d_inv = nullptr;
-            double *d_grid = nullptr;
-            e = hipMalloc((void **)&d_inv, inv_n * sizeof(unsigned short) + 64);
-            if (e == hipSuccess) { c->co_allocs.push_back(d_inv); e = hipMalloc((void **)&d_grid, (size_t)3 * nI * sizeof(double) + 64); }
-            if (e == hipSuccess) { c->co_allocs.push_back(d_grid); e = hipMemsetAsync(d_inv, 0, inv_n * sizeof(unsigned short), c->stream); }
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_inv_range, dim3((unsigned)nI), dim3(256), 0, c->stream, d_dense, nW, nP, d_mono, d_grid);
-                hipLaunchKernelGGL(k_inv_rows, dim3((unsigned)(((long long)nI * nP + 255) / 256)), dim3(256), 0, c->stream, d_dense, nI, nW, nP,
-                                   ppad, d_mono, d_grid, d_inv);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) { T.inv_rows = d_inv; T.inv_grid = d_grid; }
-        }
-        // block pyramid of the general kernel (co_block_search): min / max per block of XSW_BLK_R x XSW_BLK_C candidates and per
-        // band of blk_g block rows (6 MB at the default size).  Absent (allocation failure, XSW_NO_BLOCKS=1: A/B measurements and
-        // the tests of the old routes): the general kernel sweeps windows and falls back to the exact scan as before.
-        T.blk = nullptr; T.bandmm = nullptr; T.blk4 = nullptr; T.cellmm = nullptr;
-        T.nbr = (nW + XSW_BLK_R - 1) / XSW_BLK_R; T.nbc = (nP + XSW_BLK_C - 1) / XSW_BLK_C; T.nbc4 = (nP + XSW_BLK_C4 - 1) / XSW_BLK_C4;
-        T.ncr = (T.nbr + XSW_CELL_R - 1) / XSW_CELL_R; T.ncc = (T.nbc + XSW_CELL_C - 1) / XSW_CELL_C;
-        T.blk_g = std::max(1, 64 / T.nbc);
-        T.nbands = (T.nbr + T.blk_g - 1) / T.blk_g;
-        static const bool blocks_off = env_flag("XSW_NO_BLOCKS");
-        if (e == hipSuccess && !blocks_off && (long long)nI * T.nbr * T.nbc < (1LL << 31)) {
-            float2 *d_blk = nullptr, *d_band = nullptr;
-            const long long nblk = (long long)nI * T.nbr * T.nbc, nband = (long long)nI * T.nbands;
-            hipError_t e2 = hipMalloc((void **)&d_blk, (size_t)nblk * sizeof(float2) + 64);
-            if (e2 == hipSuccess) { c->co_allocs.push_back(d_blk); e2 = hipMalloc((void **)&d_band, (size_t)nband * sizeof(float2) + 64); }
-            if (e2 == hipSuccess) {
-                c->co_allocs.push_back(d_band);
-                hipLaunchKernelGGL(k_block_minmax, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, c->stream, d_dense, nI, nW, nP, T.nbr, T.nbc, d_blk);
-                hipLaunchKernelGGL(k_band_minmax, dim3((unsigned)((nband + 255) / 256)), dim3(256), 0, c->stream, d_blk, nI, T.nbr, T.nbc, T.blk_g, T.nbands, d_band);
-                e2 = hipGetLastError();
-            }
-            // level 1 of k_invert_blocks: cells of XSW_CELL_R x XSW_CELL_C blocks (a band over ALL directions has a sigma0 range that
-            // holds nearly any s and no sector bound: 401 blocks left to bound per outlier pixel where these cells leave 70)
-            float2 *d_cell = nullptr;
-            const long long ncell = (long long)nI * T.ncr * T.ncc;
-            if (e2 == hipSuccess) e2 = hipMalloc((void **)&d_cell, (size_t)ncell * sizeof(float2) + 64);
-            if (e2 == hipSuccess) {
-                c->co_allocs.push_back(d_cell);
-                hipLaunchKernelGGL(k_block_minmax, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, c->stream, d_dense, nI, nW, nP, T.ncr, T.ncc, d_cell,
-                                   XSW_CELL_C * XSW_BLK_C, XSW_CELL_R * XSW_BLK_R);
-                e2 = hipGetLastError();
-            }
-            if (e2 == hipSuccess) { T.blk = d_blk; T.bandmm = d_band; T.cellmm = d_cell; }
-            else (void)hipGetLastError();
-            // the same per sub-block of XSW_BLK_C4 directions (k_invert_blocks bounds the quarters of a kept block before sweeping:
-            // sigma0 varies faster with the direction than with the speed where the GMF saturates, so a block 16 directions wide
-            // nearly always straddles the contour); 23 MB at the default size.  XSW_NO_BLK4=1: not built (A/B, tests of the old sweep)
-            static const bool blk4_off = env_flag("XSW_NO_BLK4");
-            if (T.blk && !blk4_off && (long long)nI * T.nbr * T.nbc4 < (1LL << 31)) {
-                float2 *d_blk4 = nullptr;
-                const long long nblk4 = (long long)nI * T.nbr * T.nbc4;
-                hipError_t e3 = hipMalloc((void **)&d_blk4, (size_t)nblk4 * sizeof(float2) + 64);
-                if (e3 == hipSuccess) {
-                    c->co_allocs.push_back(d_blk4);
-                    hipLaunchKernelGGL(k_block_minmax, dim3((unsigned)((nblk4 + 255) / 256)), dim3(256), 0, c->stream, d_dense, nI, nW, nP, T.nbr, T.nbc4, d_blk4, XSW_BLK_C4);
-                    e3 = hipGetLastError();
-                }
-                if (e3 == hipSuccess) T.blk4 = d_blk4;
-                else (void)hipGetLastError();
-            }
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(h_flags, d_flags, sizeof h_flags, hipMemcpyDeviceToHost, c->stream);
-        hipError_t se = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = se;
-        if (d_flags) (void)hipFree(d_flags);
-        if (tmp_dense) (void)hipFree(tmp_dense);
-        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? XSW_ENOMEM : XSW_EHIP, "LUT install failed: %s", hipGetErrorString(e));
-        T.co = d_co;
-        T.co32 = d_co32;
-        lut_finite = h_flags[0] == 0;
-        memcpy(&T.co_absmax, &h_flags[1], sizeof(double));
+
+    // required tables: the padded float64 and float32 copies (with the finiteness flag and max |dB|), the monotone rows
+    DevSeq req{st, c->co_allocs};
+    double *d_co = req.table<double>(g.n_pad);
+    float *d_co32 = req.table<float>(g.n_pad);
+    unsigned long long h_flags[2] = {0, 0}, *d_flags = req.ok() ? (unsigned long long *)tmp.alloc(sizeof h_flags) : nullptr;
+    req.check(tmp.err);
+    if (req.ok()) {
+        req.zero(d_flags, sizeof h_flags);
+        req.zero(d_co + g.n_body, g.n_slack * sizeof(double));
+        req.zero(d_co32 + g.n_body, g.n_slack * sizeof(float));
     }
-    std::vector<double> wh(nW), cp(nP), sp(nP);
-    for (int i = 0; i < nW; ++i) wh[i] = 0.5 * l->wspd[i];
-    bool trig_ok = true;
-    for (int i = 0; i < nP; ++i) {
-        const double r = l->phi[i] * (M_PI / 180.0);
-        cp[i] = l->cos_phi ? l->cos_phi[i] : std::cos(r);
-        sp[i] = l->sin_phi ? l->sin_phi[i] : std::sin(r);
-        if (std::fabs(cp[i] - std::cos(r)) > 1e-12 || std::fabs(sp[i] - std::sin(r)) > 1e-12) trig_ok = false;
+    req.run([&] { hipLaunchKernelGGL(k_pad_co, dim3(g.pad_grid), dim3(256), 0, st, d_dense, d_co, d_co32, nP, g.ppad, g.rows, d_flags); });
+    std::vector<int> init((size_t)nI, nW);  // read by the copy below until the stream is synchronised (tmp.finish)
+    int *d_mono = req.table<int>((size_t)nI);
+    // on the launch stream, in order with k_mono_rows (not a null-stream copy whose completion the kernel would rely on)
+    if (req.ok()) req.check(hipMemcpyAsync(d_mono, init.data(), (size_t)nI * sizeof(int), hipMemcpyHostToDevice, st));
+    req.run([&] { hipLaunchKernelGGL(k_mono_rows, dim3(g.col_grid), dim3(256), 0, st, d_dense, nI, nW, nP, d_mono); });
+    T.mono_rows = d_mono;
+
+    // optional tables (DevSeq::usable): absent, the kernels take their older routes
+    T.tail_min = nullptr;
+    static const bool tail_off = env_flag("XSW_NO_TAIL_CUT");  // A/B measurements only
+    if (req.ok() && !tail_off) {
+        DevSeq opt{st, c->co_allocs};
+        double *d_tail = opt.table<double>(g.tail_n);
+        opt.run([&] { hipLaunchKernelGGL(k_tail_min, dim3((unsigned)nI), dim3(256), 0, st, d_dense, nW, nP, g.ppad, d_mono, d_tail); });
+        if (opt.usable()) T.tail_min = d_tail;
     }
-    if ((rc = upload(c, c->co_allocs, l->inc, nI, &T.inc))) return rc;
-    if ((rc = upload(c, c->co_allocs, l->wspd, nW, &T.w))) return rc;
-    if ((rc = upload(c, c->co_allocs, wh.data(), nW, &T.wh))) return rc;
-    {
-        std::vector<float> wh32(nW);
-        for (int i = 0; i < nW; ++i) wh32[i] = (float)wh[i];
-        if ((rc = upload(c, c->co_allocs, wh32.data(), (size_t)nW, &T.wh32))) return rc;
+    // inverse of the monotone rows (co_band_pass starts its sweep from a table look-up instead of a bisection): optional by
+    // its gate only, an error while it is built fails the install
+    T.inv_rows = nullptr; T.inv_grid = nullptr;
+    if (req.ok() && g.inv_ok) {
+        unsigned short *d_inv = req.table<unsigned short>(g.inv_n);
+        double *d_grid = req.table<double>(g.inv_grid_n);
+        req.zero(d_inv, g.inv_n * sizeof(unsigned short));
+        req.run([&] {
+            hipLaunchKernelGGL(k_inv_range, dim3((unsigned)nI), dim3(256), 0, st, d_dense, nW, nP, d_mono, d_grid);
+            hipLaunchKernelGGL(k_inv_rows, dim3(g.col_grid), dim3(256), 0, st, d_dense, nI, nW, nP, g.ppad, d_mono, d_grid, d_inv);
+        });
+        if (req.ok()) { T.inv_rows = d_inv; T.inv_grid = d_grid; }
     }
-    if ((rc = upload(c, c->co_allocs, l->phi, nP, &T.phi))) return rc;
-    if ((rc = upload(c, c->co_allocs, cp.data(), nP, &T.cphi))) return rc;
-    if ((rc = upload(c, c->co_allocs, sp.data(), nP, &T.sphi))) return rc;
-    {
-        std::vector<double> cs((size_t)2 * nP);
-        for (int i = 0; i < nP; ++i) { cs[2 * i] = cp[i]; cs[2 * i + 1] = sp[i]; }
-        if ((rc = upload(c, c->co_allocs, cs.data(), cs.size(), &T.csphi))) return rc;
-        std::vector<float> cs32(cs.begin(), cs.end());  // float32 copy: the bound arithmetic of k_invert_band2 (xsw_band2.hpp)
-        if ((rc = upload(c, c->co_allocs, cs32.data(), cs32.size(), &T.csphi32))) return rc;
+    // block pyramid of the general kernel (co_block_search): min / max per block of XSW_BLK_R x XSW_BLK_C candidates and per
+    // band of blk_g block rows (6 MB at the default size).  Absent (allocation failure, XSW_NO_BLOCKS=1: A/B measurements and
+    // the tests of the old routes): the general kernel sweeps windows and falls back to the exact scan as before.
+    T.blk = nullptr; T.bandmm = nullptr; T.blk4 = nullptr; T.cellmm = nullptr;
+    static const bool blocks_off = env_flag("XSW_NO_BLOCKS");
+    if (req.ok() && !blocks_off && g.blk_ok) {
+        DevSeq opt{st, c->co_allocs};
+        float2 *d_blk = opt.table<float2>((size_t)g.nblk), *d_band = opt.table<float2>((size_t)g.nband);
+        opt.run([&] {
+            hipLaunchKernelGGL(k_block_minmax, dim3(blocks_of_256(g.nblk)), dim3(256), 0, st, d_dense, nI, nW, nP, g.nbr, g.nbc, d_blk);
+            hipLaunchKernelGGL(k_band_minmax, dim3(blocks_of_256(g.nband)), dim3(256), 0, st, d_blk, nI, g.nbr, g.nbc, g.blk_g, g.nbands, d_band);
+        });
+        // level 1 of k_invert_blocks: cells of XSW_CELL_R x XSW_CELL_C blocks (a band over ALL directions has a sigma0 range that
+        // holds nearly any s and no sector bound: 401 blocks left to bound per outlier pixel where these cells leave 70)
+        float2 *d_cell = opt.table<float2>((size_t)g.ncell);
+        opt.run([&] {
+            hipLaunchKernelGGL(k_block_minmax, dim3(blocks_of_256(g.ncell)), dim3(256), 0, st, d_dense, nI, nW, nP, g.ncr, g.ncc, d_cell,
+                               XSW_CELL_C * XSW_BLK_C, XSW_CELL_R * XSW_BLK_R);
+        });
+        if (opt.usable()) { T.blk = d_blk; T.bandmm = d_band; T.cellmm = d_cell; }
+        // the same per sub-block of XSW_BLK_C4 directions (k_invert_blocks bounds the quarters of a kept block before sweeping:
+        // sigma0 varies faster with the direction than with the speed where the GMF saturates, so a block 16 directions wide
+        // nearly always straddles the contour); 23 MB at the default size.  XSW_NO_BLK4=1: not built (A/B, tests of the old sweep)
+        static const bool blk4_off = env_flag("XSW_NO_BLK4");
+        if (T.blk && !blk4_off && g.blk4_ok) {
+            DevSeq opt4{st, c->co_allocs};
+            float2 *d_blk4 = opt4.table<float2>((size_t)g.nblk4);
+            opt4.run([&] { hipLaunchKernelGGL(k_block_minmax, dim3(blocks_of_256(g.nblk4)), dim3(256), 0, st, d_dense, nI, nW, nP, g.nbr, g.nbc4, d_blk4, XSW_BLK_C4); });
+            if (opt4.usable()) T.blk4 = d_blk4;
+        }
     }
-    // output-side tables: caller's values, or the host libm's (see xsw.h)
-    {
-        std::vector<double> od((size_t)4 * nP), ab((size_t)nW * nP), dd((size_t)4 * nW * nP);
-        for (int k = 0; k < 2; ++k)
-            for (int i = 0; i < nP; ++i) {
-                const double r = (k ? -l->phi[i] : l->phi[i]) * (M_PI / 180.0);
-                od[((size_t)k * nP + i) * 2 + 0] = l->out_dir ? l->out_dir[((size_t)k * nP + i) * 2 + 0] : std::cos(r);
-                od[((size_t)k * nP + i) * 2 + 1] = l->out_dir ? l->out_dir[((size_t)k * nP + i) * 2 + 1] : std::sin(r);
-            }
-        for (int iw = 0; iw < nW; ++iw)
-            for (int i = 0; i < nP; ++i) {
-                const double w = l->wspd[iw];
-                for (int k = 0; k < 2; ++k) {
-                    const double er = od[((size_t)k * nP + i) * 2], ei = od[((size_t)k * nP + i) * 2 + 1];
-                    const double re = w * er, im = w * ei + 0.0 * er;
-                    const size_t o = (((size_t)k * nW + iw) * nP + i) * 2;
-                    if (l->dual_dir) { dd[o] = l->dual_dir[o]; dd[o + 1] = l->dual_dir[o + 1]; }
-                    else { const double ph = std::atan2(im, re); dd[o] = std::cos(ph); dd[o + 1] = std::sin(ph); }
-                    if (k == 0) ab[(size_t)iw * nP + i] = l->abs_co ? l->abs_co[(size_t)iw * nP + i] : std::hypot(re, im);
-                }
-            }
-        if ((rc = upload(c, c->co_allocs, od.data(), od.size(), &T.out_dir))) return rc;
-        if ((rc = upload(c, c->co_allocs, ab.data(), ab.size(), &T.abs_co))) return rc;
-        if ((rc = upload(c, c->co_allocs, dd.data(), dd.size(), &T.dual_dir))) return rc;
-        // the co-pol winds themselves, by the store's own operations (store_pixel: w * e.x, w * e.y + 0.0 * e.x): what a grid
-        // code expands to, on the device (k_expand) and on the host (expand_host)
-        std::vector<double> sol((size_t)4 * nW * nP);
-        for (int k = 0; k < 2; ++k)
-            for (int iw = 0; iw < nW; ++iw)
-                for (int i = 0; i < nP; ++i) {
-                    const double w = l->wspd[iw], ex = od[((size_t)k * nP + i) * 2], ey = od[((size_t)k * nP + i) * 2 + 1];
-                    const size_t o = (((size_t)k * nW + iw) * nP + i) * 2;
-                    sol[o] = w * ex;
-                    sol[o + 1] = w * ey + 0.0 * ex;
-                }
-        if ((rc = upload(c, c->co_allocs, sol.data(), sol.size(), &T.sol))) return rc;
-        c->h_sol32.resize(sol.size());
-        for (size_t k = 0; k < sol.size(); ++k) c->h_sol32[k] = (float)sol[k];
-        c->h_sol.swap(sol);
-        c->h_dual.swap(dd);
-    }
-    T.n_inc = nI; T.n_w = nW; T.n_phi = nP; T.phi_pad = ppad; T.w_pad = wpad;
-    T.phi_180 = (180.0 - (l->phi[nP - 1] - l->phi[0])) < 2.0 ? 1 : 0;  // windspeed.py:152-156
-    T.w0 = l->wspd[0];
-    T.phi0 = l->phi[0];
-    T.phi_last = l->phi[nP - 1];
-    T.inv_wstep = nW > 1 ? (nW - 1) / (l->wspd[nW - 1] - l->wspd[0]) : 0.0;
-    T.inv_dphi = nP > 1 ? (nP - 1) / (l->phi[nP - 1] - l->phi[0]) : 0.0;
-    T.wstep_half = 0.5 / T.inv_wstep;  // the kernels' (w/2)-per-row step: same IEEE quotient they used to form per wave
-    T.inv_nphi = 1.0 / (double)nP;
-    T.inc_uniform = uniform_axis(l->inc, nI) && nI >= 2 ? 1 : 0;
-    T.inc0 = l->inc[0];
-    T.inv_incstep = nI > 1 ? (nI - 1) / (l->inc[nI - 1] - l->inc[0]) : 0.0;
-    T.prunable = (nW >= 2 && nP >= 2 && nW < 32768 && nP < 65536 && (int64_t)nW * ppad < ((int64_t)1 << 30) && uniform_axis(l->wspd, nW) && uniform_axis(l->phi, nP) && trig_ok &&
-                  (l->phi[nP - 1] - l->phi[0]) <= 360.0 + 1e-9 && lut_finite)
-                     ? 1 : 0;
-    T.co_off32 = ((uint64_t)nI * nW + 260) * (uint64_t)ppad * 8u < ((uint64_t)1 << 32) ? 1 : 0;
-    T.band_mul24 = ((uint64_t)nI * nW <= 0xFFFFFFu && (uint64_t)(nI + 1) * XSW_INV_BINS <= 0xFFFFFFu && (uint64_t)ppad * 8u <= 0xFFFFFFu &&
-                    (uint64_t)(nI + 1) * nP <= 0xFFFFFFu && (uint64_t)wpad * 8u <= 0xFFFFFFu && (uint64_t)nI * nP * wpad * 8u < ((uint64_t)1 << 32)) ? 1 : 0;
-    T.blk_span_ok = (nP > 1 && (XSW_BLK_C - 1) * (l->phi[nP - 1] - l->phi[0]) / (nP - 1) < 170.0) ? 1 : 0;
-    T.cell_span_ok = (nP > 1 && (XSW_CELL_C * XSW_BLK_C - 1) * (l->phi[nP - 1] - l->phi[0]) / (nP - 1) < 170.0) ? 1 : 0;
+
+    // the flags come back; the temporaries (and `init`) are done with once the stream is
+    if (req.ok()) req.check(hipMemcpyAsync(h_flags, d_flags, sizeof h_flags, hipMemcpyDeviceToHost, st));
+    req.check(tmp.finish());
+    if (!req.ok()) return fail(c, req.code(), "LUT install failed: %s", hipGetErrorString(req.err));
+    T.co = d_co;
+    T.co32 = d_co32;
+    const bool lut_finite = h_flags[0] == 0;
+    memcpy(&T.co_absmax, &h_flags[1], sizeof(double));
+
+    // host-built tables: the axes as they are; the output-side tables are the caller's values, or the host libm's (see xsw.h)
+    CoHostTables H(l);
+    DevSeq up{st, c->co_allocs};
+    T.inc = up.table((size_t)nI, l->inc);
+    T.w = up.table((size_t)nW, l->wspd);
+    T.wh = up.table(H.wh);
+    T.wh32 = up.table(H.wh32);
+    T.phi = up.table((size_t)nP, l->phi);
+    T.cphi = up.table(H.cphi);
+    T.sphi = up.table(H.sphi);
+    T.csphi = up.table(H.csphi);
+    T.csphi32 = up.table(H.csphi32);
+    T.out_dir = up.table(H.out_dir);
+    T.abs_co = up.table(H.abs_co);
+    T.dual_dir = up.table(H.dual_dir);
+    T.sol = up.table(H.sol);
+    if (!up.ok()) return fail(c, up.code(), "LUT install failed: %s", hipGetErrorString(up.err));
+    c->h_sol32.swap(H.sol32);
+    c->h_sol.swap(H.sol);
+    c->h_dual.swap(H.dual_dir);
+
+    co_scalars(T, l, g, lut_finite, H.trig_ok);
+
     // transposed slices for the ray scan
-    double *dT = nullptr;
-    HIPCHK(c, hipMalloc((void **)&dT, (size_t)nI * nP * wpad * sizeof(double) + 512 * sizeof(double)));
-    c->co_allocs.push_back(dT);
-    HIPCHK(c, hipMemsetAsync(dT, 0, (size_t)nI * nP * wpad * sizeof(double) + 512 * sizeof(double), c->stream));
-    dim3 grid((nP + 31) / 32, (nW + 31) / 32, nI);
-    hipLaunchKernelGGL(k_transpose_slices, grid, dim3(256), 0, c->stream, T.co, dT, nW, nP, ppad, wpad);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double *dT = (double *)up.alloc(g.coT_n * sizeof(double));
+    up.zero(dT, g.coT_n * sizeof(double));
+    up.run([&] { hipLaunchKernelGGL(k_transpose_slices, dim3((nP + 31) / 32, (nW + 31) / 32, nI), dim3(256), 0, st, T.co, dT, nW, nP, g.ppad, g.wpad); });
+    if (up.ok()) up.check(hipStreamSynchronize(st));
+    if (!up.ok()) return fail(c, up.code(), "LUT install failed: %s", hipGetErrorString(up.err));
     T.coT = dT;
     c->have_co = true;
     return XSW_OK;
@@ -587,44 +436,17 @@ static int upload_cr(xsw_ctx *c, const xsw_lut *l)
     free_all(c->cr_allocs);
     c->have_cr = false;
     DevTables &T = c->T;
-    const int nI = l->n_inc, nW = l->n_wspd, wpad = (nW + 3) & ~3;
-    std::vector<double> pad((size_t)nI * wpad, 0.0), wh(nW);
-    for (int r = 0; r < nI; ++r) memcpy(&pad[(size_t)r * wpad], l->db + (size_t)r * nW, nW * sizeof(double));
-    for (int i = 0; i < nW; ++i) wh[i] = 0.5 * l->wspd[i];
-    int rc;
-    if ((rc = upload(c, c->cr_allocs, pad.data(), pad.size(), &T.cr))) return rc;
-    if ((rc = upload(c, c->cr_allocs, l->inc, nI, &T.inc_cr))) return rc;
-    if ((rc = upload(c, c->cr_allocs, l->wspd, nW, &T.wcr))) return rc;
-    if ((rc = upload(c, c->cr_allocs, wh.data(), nW, &T.wcrh))) return rc;
-    T.n_inc_cr = nI; T.n_wcr = nW; T.wcr_pad = wpad;
-    c->h_wcr.assign(l->wspd, l->wspd + nW);
-    T.cr_finite = all_finite(l->db, (size_t)nI * nW) ? 1 : 0;
-    bool mono = T.cr_finite && nW >= 2 && uniform_axis(l->wspd, nW);
-    for (int r = 0; r < nI && mono; ++r)
-        for (int k = 1; k < nW; ++k)
-            if (l->db[(size_t)r * nW + k] < l->db[(size_t)r * nW + k - 1]) { mono = false; break; }
-    T.cr_monotone = mono ? 1 : 0;
-    T.wcr0 = l->wspd[0];
-    T.inv_wcrstep = nW > 1 ? (nW - 1) / (l->wspd[nW - 1] - l->wspd[0]) : 0.0;
-    T.wcrstep_half = 0.5 / T.inv_wcrstep;
-    T.inv_cr = nullptr; T.inv_cr_grid = nullptr;
-    if (mono && nW < 65536) {  // inverse of the monotone rows (search_cr_scan): first k with row[k] >= t0 + b * width
-        std::vector<unsigned short> inv((size_t)nI * XSW_INV_BINS);
-        std::vector<double> grid((size_t)3 * nI);
-        for (int r = 0; r < nI; ++r) {
-            const double *row = l->db + (size_t)r * nW;
-            const double t0 = row[0], width = (row[nW - 1] - row[0]) / (double)XSW_INV_BINS;
-            const bool ok = width > 0.0 && width < 1e300;
-            grid[3 * r] = ok ? t0 : 0.0; grid[3 * r + 1] = ok ? width : 0.0; grid[3 * r + 2] = ok ? 1.0 / width : 0.0;
-            for (int b = 0; b < XSW_INV_BINS; ++b)
-                inv[(size_t)r * XSW_INV_BINS + b] = (unsigned short)(b == 0 || !ok ? 0 : std::lower_bound(row, row + nW, std::fma((double)b, width, t0)) - row);
-        }
-        if ((rc = upload(c, c->cr_allocs, inv.data(), inv.size(), &T.inv_cr))) return rc;
-        if ((rc = upload(c, c->cr_allocs, grid.data(), grid.size(), &T.inv_cr_grid))) return rc;
-    }
-    T.inc_cr_uniform = uniform_axis(l->inc, nI) && nI >= 2 ? 1 : 0;
-    T.inc_cr0 = l->inc[0];
-    T.inv_inccrstep = nI > 1 ? (nI - 1) / (l->inc[nI - 1] - l->inc[0]) : 0.0;
+    const CrPlan p(l);
+    DevSeq up{c->stream, c->cr_allocs};
+    T.cr = up.table(p.pad);
+    T.inc_cr = up.table((size_t)l->n_inc, l->inc);
+    T.wcr = up.table((size_t)l->n_wspd, l->wspd);
+    T.wcrh = up.table(p.wh);
+    T.inv_cr = p.inv.empty() ? nullptr : up.table(p.inv);
+    T.inv_cr_grid = p.inv.empty() ? nullptr : up.table(p.grid);
+    if (!up.ok()) return fail(c, up.code(), "LUT install failed: %s", hipGetErrorString(up.err));
+    c->h_wcr.assign(l->wspd, l->wspd + l->n_wspd);
+    cr_scalars(T, l, p);
     c->have_cr = true;
     return XSW_OK;
 }
@@ -671,12 +493,10 @@ static void ensure_list(xsw_ctx *c, long long n, long long lines)
     const size_t want = context_list_cap(n, test_cap), want_strips = strips_for(n, lines);
     if (want <= c->lists.list_cap && want_strips <= c->lists.mask_strips) return;
     (void)hipStreamSynchronize(c->stream);  // the old lists may still be in use
-    if (c->lists.base) (void)hipFree(c->lists.base);
-    c->lists = WorkLists{};
     static const bool no_list = env_flag("XSW_FAIL_LIST_ALLOC");  // tests: the allocation-failure route
-    WorkLists w{nullptr, want, want_strips};
-    if (!no_list && hipMalloc((void **)&w.base, w.bytes()) == hipSuccess) c->lists = w;
-    else (void)hipGetLastError();
+    c->lists.list_cap = c->lists.mask_strips = 0;  // (no lists: the one-kernel path)
+    if (grow(c->lists.base, c->lists_bytes, no_list ? 0 : WorkLists{nullptr, want, want_strips}.bytes()) != hipSuccess) (void)hipGetLastError();
+    if (c->lists.base) { c->lists.list_cap = want; c->lists.mask_strips = want_strips; }
 }
 
 // ---- grid codes -> complex winds (xsw.h: xsw_expand_codes)
@@ -835,18 +655,8 @@ static int host_thread_count(const xsw_ctx *c)
 static int worker_reserve(xsw_ctx::Worker &w, size_t pin_bytes, size_t dev_bytes, std::string &err)
 {
     if (!w.s && hipStreamCreateWithFlags(&w.s, hipStreamNonBlocking) != hipSuccess) return seterr(err, XSW_EHIP, "stream create failed");
-    if (pin_bytes > w.pin_cap) {
-        if (w.pin) (void)hipHostFree(w.pin);
-        w.pin = nullptr; w.pin_cap = 0;
-        if (hipHostMalloc((void **)&w.pin, pin_bytes, hipHostMallocDefault) != hipSuccess) return seterr(err, XSW_ENOMEM, "hipHostMalloc(%zu) failed", pin_bytes);
-        w.pin_cap = pin_bytes;
-    }
-    if (dev_bytes > w.dev_cap) {
-        if (w.dev) (void)hipFree(w.dev);
-        w.dev = nullptr; w.dev_cap = 0;
-        if (hipMalloc((void **)&w.dev, dev_bytes) != hipSuccess) return seterr(err, XSW_ENOMEM, "hipMalloc(%zu) failed", dev_bytes);
-        w.dev_cap = dev_bytes;
-    }
+    if (pin_bytes > w.pin_cap && grow(w.pin, w.pin_cap, pin_bytes, nullptr, true) != hipSuccess) return seterr(err, XSW_ENOMEM, "hipHostMalloc(%zu) failed", pin_bytes);
+    if (dev_bytes > w.dev_cap && grow(w.dev, w.dev_cap, dev_bytes) != hipSuccess) return seterr(err, XSW_ENOMEM, "hipMalloc(%zu) failed", dev_bytes);
     return XSW_OK;
 }
 
@@ -1063,26 +873,17 @@ extern "C" int xsw_invert(xsw_ctx *c, const xsw_invert_args *a)
 }
 
 // ---------------------------------------------------------------------------------------- LUT interpolation
-static bool left_neighbours(const double *x_old, int n_old, const double *x_new, int n_new, std::vector<int> &lo)
+// what a failed temporary is to the caller of the interpolation or the build; `nomem` may name the bytes asked for (%zu)
+static int temps_rc(xsw_ctx *c, const CallTemps &tmp, const char *nomem, const char *h2d)
 {
-    // scipy interp1d: searchsorted(x_old, x_new) (side='left'), clip(1, n-1), minus one; bounds_error=True
-    lo.resize(n_new);
-    for (int i = 0; i < n_new; ++i) {
-        const double x = x_new[i];
-        if (!(x >= x_old[0] && x <= x_old[n_old - 1])) return false;
-        int a = 0, b = n_old;
-        while (a < b) { int m = (a + b) >> 1; if (x_old[m] < x) a = m + 1; else b = m; }
-        int hi = a < 1 ? 1 : (a > n_old - 1 ? n_old - 1 : a);
-        lo[i] = hi - 1;
-    }
-    return true;
+    return tmp.ok() ? XSW_OK : tmp.refused ? fail(c, XSW_ENOMEM, nomem, tmp.refused - 8) : fail(c, XSW_EHIP, "%s", h2d);
 }
 
 // Interpolation with device-resident raw table and output (d_raw -> d_out); axes are host arrays.  Asynchronous on the
-// context's stream except for the small uploads; temporaries are appended to `tmp` (freed by the caller after a sync).
+// context's stream except for the small uploads; the temporaries are `tmp`'s (the caller's: freed when its call ends).
 static int interp_device(xsw_ctx *c, const double *d_raw, const double *inc_raw, const double *wspd_raw, const double *phi_raw,
                          int32_t n_inc_raw, int32_t n_wspd_raw, int32_t n_phi_raw, const double *inc, const double *wspd,
-                         const double *phi, int32_t n_inc, int32_t n_wspd, int32_t n_phi, double *d_out, std::vector<void *> &tmp)
+                         const double *phi, int32_t n_inc, int32_t n_wspd, int32_t n_phi, double *d_out, CallTemps &tmp)
 {
     if (!inc_raw || !wspd_raw || !inc || !wspd || n_inc_raw < 2 || n_wspd_raw < 2 || n_inc < 1 || n_wspd < 1)
         return fail(c, XSW_EINVAL, "lut_interp: null pointer or axis shorter than 2");
@@ -1096,27 +897,19 @@ static int interp_device(xsw_ctx *c, const double *d_raw, const double *inc_raw,
         (has_phi && !left_neighbours(phi_raw, n_phi_raw, phi, n_phi, lop)))
         return fail(c, XSW_EINVAL, "A value in x_new is outside the interpolation range.");
     InterpArgs a{};
-    int rc = XSW_OK;
-    auto up = [&](const void *h, size_t bytes, const void **d) {
-        void *p = nullptr;
-        if (rc) return;
-        if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess) { rc = fail(c, XSW_ENOMEM, "lut_interp: hipMalloc failed"); return; }
-        tmp.push_back(p);
-        if (bytes && hipMemcpyAsync(p, h, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(c, XSW_EHIP, "lut_interp: H2D failed");
-        *d = p;
-    };
     a.raw = d_raw;
-    up(inc_raw, (size_t)n_inc_raw * 8, (const void **)&a.xi_raw);
-    up(wspd_raw, (size_t)n_wspd_raw * 8, (const void **)&a.xw_raw);
-    up(inc, (size_t)n_inc * 8, (const void **)&a.xi);
-    up(wspd, (size_t)n_wspd * 8, (const void **)&a.xw);
-    up(loi.data(), loi.size() * 4, (const void **)&a.loi);
-    up(low.data(), low.size() * 4, (const void **)&a.low);
+    a.xi_raw = (const double *)tmp.alloc((size_t)n_inc_raw * 8, inc_raw);
+    a.xw_raw = (const double *)tmp.alloc((size_t)n_wspd_raw * 8, wspd_raw);
+    a.xi = (const double *)tmp.alloc((size_t)n_inc * 8, inc);
+    a.xw = (const double *)tmp.alloc((size_t)n_wspd * 8, wspd);
+    a.loi = (const int *)tmp.alloc(loi.size() * 4, loi.data());
+    a.low = (const int *)tmp.alloc(low.size() * 4, low.data());
     if (has_phi) {
-        up(phi_raw, (size_t)n_phi_raw * 8, (const void **)&a.xp_raw);
-        up(phi, (size_t)n_phi * 8, (const void **)&a.xp);
-        up(lop.data(), lop.size() * 4, (const void **)&a.lop);
+        a.xp_raw = (const double *)tmp.alloc((size_t)n_phi_raw * 8, phi_raw);
+        a.xp = (const double *)tmp.alloc((size_t)n_phi * 8, phi);
+        a.lop = (const int *)tmp.alloc(lop.size() * 4, lop.data());
     }
+    int rc = temps_rc(c, tmp, "lut_interp: hipMalloc failed", "lut_interp: H2D failed");
     a.out = d_out;
     a.ni_raw = n_inc_raw; a.nw_raw = n_wspd_raw; a.np_raw = has_phi ? n_phi_raw : 0;
     a.ni = n_inc; a.nw = n_wspd; a.np = has_phi ? n_phi : 0;
@@ -1142,35 +935,22 @@ extern "C" int xsw_lut_interp(xsw_ctx *c, const double *raw, const double *inc_r
     if (!raw || !out) return fail(c, XSW_EINVAL, "lut_interp: null pointer or axis shorter than 2");
     HIPCHK(c, hipSetDevice(c->device));
     const bool has_phi = n_phi_raw > 0;
-    std::vector<void *> tmp;
+    CallTemps tmp(c->stream);
     const size_t n_raw = (size_t)std::max(n_inc_raw, 0) * std::max(n_wspd_raw, 0) * (has_phi ? n_phi_raw : 1);
     const size_t n_out = (size_t)std::max(n_inc, 0) * std::max(n_wspd, 0) * (has_phi ? std::max(n_phi, 0) : 1);
-    void *d_raw = nullptr, *d_out = nullptr;
-    int rc = XSW_OK;
-    if (hipMalloc(&d_raw, n_raw * 8 + 8) != hipSuccess || hipMalloc(&d_out, n_out * 8 + 8) != hipSuccess)
-        rc = fail(c, XSW_ENOMEM, "lut_interp: hipMalloc failed");
-    if (d_raw) tmp.push_back(d_raw);
-    if (d_out) tmp.push_back(d_out);
-    if (!rc && hipMemcpyAsync(d_raw, raw, n_raw * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(c, XSW_EHIP, "lut_interp: H2D failed");
+    const void *d_raw = tmp.alloc(n_raw * 8, raw, 8);
+    void *d_out = tmp.alloc(n_out * 8, nullptr, 8);
+    int rc = temps_rc(c, tmp, "lut_interp: hipMalloc failed", "lut_interp: H2D failed");
     if (!rc) rc = interp_device(c, (const double *)d_raw, inc_raw, wspd_raw, phi_raw, n_inc_raw, n_wspd_raw, n_phi_raw, inc, wspd, phi,
                                 n_inc, n_wspd, n_phi, (double *)d_out, tmp);
     if (!rc && hipMemcpyAsync(out, d_out, n_out * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
         rc = fail(c, XSW_EHIP, "lut_interp: D2H failed");
-    hipError_t se = hipStreamSynchronize(c->stream);
+    const hipError_t se = tmp.finish();
     if (!rc && se != hipSuccess) rc = fail(c, XSW_EHIP, "lut_interp: %s", hipGetErrorString(se));
-    for (void *p : tmp) (void)hipFree(p);
     return rc;
 }
 
 // ---------------------------------------------------------------------------------------- device-side LUT build
-static bool same_axis(const double *a, int na, const double *b, int nb)
-{
-    if (na != nb) return false;
-    for (int i = 0; i < na; ++i)
-        if (a[i] != b[i]) return false;
-    return true;
-}
-
 extern "C" int xsw_lut_build(xsw_ctx *c, int32_t gmf_id, const double *inc_raw, int32_t n_inc_raw, const double *wspd_raw,
                              int32_t n_wspd_raw, const double *phi_raw, int32_t n_phi_raw, const xsw_lut *target)
 {
@@ -1185,20 +965,12 @@ extern "C" int xsw_lut_build(xsw_ctx *c, int32_t gmf_id, const double *inc_raw, 
     HIPCHK(c, hipSetDevice(c->device));
     const int npr = copol ? n_phi_raw : 1, npt = copol ? target->n_phi : 1;
     const size_t n_raw = (size_t)n_inc_raw * n_wspd_raw * npr, n_out = (size_t)target->n_inc * target->n_wspd * npt;
-    std::vector<void *> tmp;
-    int rc = XSW_OK;
-    auto dev = [&](const void *h, size_t bytes) -> void * {
-        void *p = nullptr;
-        if (rc) return nullptr;
-        if (hipMalloc(&p, bytes + 8) != hipSuccess) { rc = fail(c, XSW_ENOMEM, "lut_build: hipMalloc(%zu) failed", bytes); return nullptr; }
-        tmp.push_back(p);
-        // on the launch stream, in order with the kernels that read it (the stream is synchronised before this function returns)
-        if (h && hipMemcpyAsync(p, h, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(c, XSW_EHIP, "lut_build: H2D failed");
-        return p;
-    };
-    const double *d_i = (const double *)dev(inc_raw, (size_t)n_inc_raw * 8), *d_w = (const double *)dev(wspd_raw, (size_t)n_wspd_raw * 8);
-    const double *d_p = copol ? (const double *)dev(phi_raw, (size_t)n_phi_raw * 8) : nullptr;
-    double *d_raw = (double *)dev(nullptr, n_raw * 8);
+    // the uploads are queued on the launch stream, in order with the kernels that read them (synchronised before this function returns)
+    CallTemps tmp(c->stream);
+    const double *d_i = (const double *)tmp.alloc((size_t)n_inc_raw * 8, inc_raw, 8), *d_w = (const double *)tmp.alloc((size_t)n_wspd_raw * 8, wspd_raw, 8);
+    const double *d_p = copol ? (const double *)tmp.alloc((size_t)n_phi_raw * 8, phi_raw, 8) : nullptr;
+    double *d_raw = (double *)tmp.alloc(n_raw * 8, nullptr, 8);
+    int rc = temps_rc(c, tmp, "lut_build: hipMalloc(%zu) failed", "lut_build: H2D failed");
     if (!rc) {
         XSW_GMF_DISPATCH(gmf_id, hipLaunchKernelGGL((k_gmf_grid<M>), dim3((unsigned)std::min<size_t>((n_raw + 255) / 256, 256 * 16)), dim3(256), 0, c->stream,
                                                     (int)gmf_id, d_i, d_w, d_p, n_inc_raw, n_wspd_raw, copol ? n_phi_raw : 0, d_raw));
@@ -1209,8 +981,8 @@ extern "C" int xsw_lut_build(xsw_ctx *c, int32_t gmf_id, const double *inc_raw, 
                       (!copol || same_axis(phi_raw, n_phi_raw, target->phi, target->n_phi));
     double *d_dense = d_raw;
     if (!rc && !same) {
-        d_dense = (double *)dev(nullptr, n_out * 8);
-        if (!rc) rc = interp_device(c, d_raw, inc_raw, wspd_raw, phi_raw, n_inc_raw, n_wspd_raw, copol ? n_phi_raw : 0, target->inc,
+        d_dense = (double *)tmp.alloc(n_out * 8, nullptr, 8);
+        if (!(rc = temps_rc(c, tmp, "lut_build: hipMalloc(%zu) failed", "lut_build: H2D failed"))) rc = interp_device(c, d_raw, inc_raw, wspd_raw, phi_raw, n_inc_raw, n_wspd_raw, copol ? n_phi_raw : 0, target->inc,
                                     target->wspd, target->phi, target->n_inc, target->n_wspd, copol ? target->n_phi : 0, d_dense, tmp);
     }
     if (!rc) {
@@ -1229,9 +1001,8 @@ extern "C" int xsw_lut_build(xsw_ctx *c, int32_t gmf_id, const double *inc_raw, 
             rc = upload_cr(c, &t);
         }
     }
-    hipError_t se = hipStreamSynchronize(c->stream);
+    const hipError_t se = tmp.finish();
     if (!rc && se != hipSuccess) rc = fail(c, XSW_EHIP, "lut_build: %s", hipGetErrorString(se));
-    for (void *p : tmp) (void)hipFree(p);
     return rc;
 }
 
@@ -1245,35 +1016,25 @@ extern "C" int xsw_gmf_eval(xsw_ctx *c, int32_t gmf_id, int64_t n, int32_t mem, 
     if (gmf_id <= GMF_CMODIFR2 && !phi) return fail(c, XSW_EINVAL, "gmf_eval: this GMF needs phi");
     if (n == 0) return XSW_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    const double *d_inc = inc, *d_w = wspd, *d_phi = phi;
-    double *d_out = out;
-    std::vector<void *> tmp;
-    hipError_t e = hipSuccess;
-    if (mem == XSW_MEM_HOST) {
-        auto stage = [&](const double *h, const double **d) {
-            if (e != hipSuccess || !h) return;
-            void *p = nullptr;
-            e = hipMalloc(&p, (size_t)n * 8);
-            if (e != hipSuccess) return;
-            tmp.push_back(p);
-            e = hipMemcpyAsync(p, h, (size_t)n * 8, hipMemcpyHostToDevice, c->stream);
-            *d = (const double *)p;
-        };
-        stage(inc, &d_inc); stage(wspd, &d_w); stage(phi, &d_phi);
-        if (e == hipSuccess) { void *p = nullptr; e = hipMalloc(&p, (size_t)n * 8); if (e == hipSuccess) { tmp.push_back(p); d_out = (double *)p; } }
-    }
-    if (e == hipSuccess) {
+    auto launch = [&](const double *d_inc, const double *d_w, const double *d_phi, double *d_out) {
         long long blocks = (n + 255) / 256;
         if (blocks > 256 * 16) blocks = 256 * 16;
         XSW_GMF_DISPATCH(gmf_id, hipLaunchKernelGGL((k_gmf_eval<M>), dim3((unsigned)blocks), dim3(256), 0, c->stream, (int)gmf_id, (long long)n, d_inc, d_w, d_phi, d_out));
-        e = hipGetLastError();
-    }
+        return hipGetLastError();
+    };
+    hipError_t e;
     if (mem == XSW_MEM_HOST) {
-        if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream);
-        hipError_t se = hipStreamSynchronize(c->stream);
+        CallTemps tmp(c->stream);
+        const size_t bytes = (size_t)n * 8;
+        const double *d_inc = (const double *)tmp.alloc(bytes, inc), *d_w = (const double *)tmp.alloc(bytes, wspd);
+        const double *d_phi = phi ? (const double *)tmp.alloc(bytes, phi) : nullptr;
+        double *d_out = (double *)tmp.alloc(bytes);
+        e = tmp.err;
+        if (e == hipSuccess) e = launch(d_inc, d_w, d_phi, d_out);
+        if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t se = tmp.finish();
         if (e == hipSuccess) e = se;
-        for (void *p : tmp) (void)hipFree(p);
-    }
+    } else e = launch(inc, wspd, phi, out);
     if (e != hipSuccess) return fail(c, XSW_EHIP, "gmf_eval failed: %s", hipGetErrorString(e));
     return XSW_OK;
 }
@@ -1305,26 +1066,11 @@ extern "C" int xsw_detrend(xsw_ctx *c, int64_t lines, int64_t samples, int32_t d
     HIPCHK(c, hipSetDevice(c->device));
     const size_t es = dtype == XSW_F32 ? 4 : 8, os = out_dtype == XSW_F32 ? 4 : 8;
     // the ratio row lives in a context-owned buffer (grown on demand): no allocation on the steady-state path
-    if ((size_t)samples > c->ratio_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));  // a previous asynchronous call may still read the old row
-        if (c->d_ratio) (void)hipFree(c->d_ratio);
-        c->d_ratio = nullptr;
-        c->ratio_cap = 0;
-        HIPCHK(c, hipMalloc((void **)&c->d_ratio, 2 * (size_t)samples * sizeof(double) + 64));
-        c->ratio_cap = (size_t)samples;
-    }
-    // [ratio | RN(1/ratio)]; the fused-multiply quotient is exact only for "ordinary" divisors: check them all
-    std::vector<double> both(2 * (size_t)samples);
-    bool fast = true;
-    for (int64_t k = 0; k < samples; ++k) {
-        const double r = ratio_row[k];
-        both[(size_t)k] = r;
-        both[(size_t)samples + k] = 1.0 / r;
-        uint64_t bits;
-        memcpy(&bits, &r, 8);
-        const double ar = std::fabs(r);
-        if (!(ar > 0x1p-500 && ar < 0x1p500) || (bits & 0xFFFFFFFFFFFFFull) == 0xFFFFFFFFFFFFFull) fast = false;
-    }
+    const size_t row_bytes = 2 * (size_t)samples * sizeof(double) + 64;
+    if (row_bytes > c->ratio_cap)  // (synchronised first: a previous asynchronous call may still read the old row)
+        HIPCHK(c, grow(c->d_ratio, c->ratio_cap, row_bytes, &c->stream));
+    std::vector<double> both;
+    const bool fast = detrend_row(ratio_row, (size_t)samples, both);
     double *d_rinv = c->d_ratio + samples;
     hipError_t e = hipMemcpyAsync(c->d_ratio, both.data(), 2 * (size_t)samples * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // `both` is a local
@@ -1424,25 +1170,13 @@ extern "C" int xsw_nesz_flatten(xsw_ctx *c, int64_t lines, int64_t samples, int3
     if (n == 0) return XSW_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t es = dtype == XSW_F32 ? 4 : 8;
-    // line blocks of the column pass: enough workgroups to fill the chip (~16 per CU), at least 8 lines each
-    const long long gx = (samples + 255) / 256;
-    long long nb = (256LL * 16 + gx - 1) / gx;
-    nb = std::max<long long>(1, std::min<long long>(std::min<long long>(nb, (lines + 7) / 8), 65535));
-    const long long lpb = (lines + nb - 1) / nb;
-    nb = (lines + lpb - 1) / lpb;
+    const NeszBlocks nbk = nesz_blocks(lines, samples, sizeof(NeszPartial));
     // context-owned scratch (column partials, means, centring abscissa), grown on demand: no allocation on the steady-state path
-    const size_t scratch_bytes = (size_t)nb * samples * sizeof(NeszPartial) + (2 * (size_t)samples + 8 + 2 * (size_t)lines) * sizeof(double);
-    if (scratch_bytes > c->nesz_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));  // a previous call may still be using the old scratch
-        if (c->nesz_scratch) (void)hipFree(c->nesz_scratch);
-        c->nesz_scratch = nullptr;
-        c->nesz_cap = 0;
-        HIPCHK(c, hipMalloc(&c->nesz_scratch, scratch_bytes));
-        c->nesz_cap = scratch_bytes;
-    }
+    if (nbk.scratch_bytes > c->nesz_cap)  // (synchronised first: a previous call may still be using the old scratch)
+        HIPCHK(c, grow(c->nesz_scratch, c->nesz_cap, nbk.scratch_bytes, &c->stream));
     auto launch = [&](const void *dn, const void *di, double *dout) {
-        return dtype == XSW_F32 ? launch_nesz<float>(c->stream, dn, di, c->nesz_scratch, dout, lines, samples, (int)nb, lpb)
-                                : launch_nesz<double>(c->stream, dn, di, c->nesz_scratch, dout, lines, samples, (int)nb, lpb);
+        return dtype == XSW_F32 ? launch_nesz<float>(c->stream, dn, di, c->nesz_scratch, dout, lines, samples, (int)nbk.nb, nbk.lpb)
+                                : launch_nesz<double>(c->stream, dn, di, c->nesz_scratch, dout, lines, samples, (int)nbk.nb, nbk.lpb);
     };
     if (mem == XSW_MEM_DEVICE) {  // asynchronous on the context's stream, like xsw_invert / xsw_detrend
         const hipError_t e = launch(noise, inc, out);
@@ -1452,13 +1186,7 @@ extern "C" int xsw_nesz_flatten(xsw_ctx *c, int64_t lines, int64_t samples, int3
     // host rasters: the column means need the whole raster before the per-line pass, so the rasters are uploaded whole (through
     // the workers' page-locked staging), the four kernels run, and the result comes back the same way
     const size_t in_b = ((size_t)n * es + 255) & ~(size_t)255, need = 2 * in_b + (size_t)n * 8;
-    if (need > c->arena_cap) {
-        if (c->arena) (void)hipFree(c->arena);
-        c->arena = nullptr;
-        c->arena_cap = 0;
-        if (hipMalloc((void **)&c->arena, need) != hipSuccess) return fail(c, XSW_ENOMEM, "hipMalloc(%zu) failed", need);
-        c->arena_cap = need;
-    }
+    if (need > c->arena_cap && grow(c->arena, c->arena_cap, need) != hipSuccess) return fail(c, XSW_ENOMEM, "hipMalloc(%zu) failed", need);
     const bool pinned = mem == XSW_MEM_HOST_PINNED;
     char *d_noise = c->arena, *d_inc = c->arena + in_b;
     double *d_out = (double *)(c->arena + 2 * in_b);
@@ -1471,10 +1199,6 @@ extern "C" int xsw_nesz_flatten(xsw_ctx *c, int64_t lines, int64_t samples, int3
     }
     if (!rc) rc = move_through_workers(c, out, d_out, (size_t)n * 8, false, pinned);
     trim_staging(c);
-    if (c->arena_cap > XSW_ARENA_KEEP) {  // do not sit on a huge staging area
-        (void)hipFree(c->arena);
-        c->arena = nullptr;
-        c->arena_cap = 0;
-    }
+    if (c->arena_cap > XSW_ARENA_KEEP) (void)grow(c->arena, c->arena_cap, 0);  // do not sit on a huge staging area
     return rc;
 }

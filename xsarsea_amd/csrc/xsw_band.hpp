@@ -236,9 +236,9 @@ __device__ __forceinline__ void co_band_pass(const DevTables &L, double inv_dsig
     const unsigned rowB = (unsigned)L.phi_pad * 8u;
     const int i_inc = B.inc_bin & 0xffff;
     // (24-bit multiplies: full rate, where v_mul_lo_u32 takes four issue slots -- four of them per lane and pass; the operands fit:
-    // the band kernels run only when n_inc * n_w and n_inc * XSW_INV_BINS stay below 2^24, xsw.hip: band_mul24)
+    // the band kernels run only when n_inc * n_w and n_inc * XSW_INV_BINS stay below 2^24, xsw_lutplan.hpp: band_mul24)
     const unsigned slice0 = mul24_sv(rowB, mul24_sv((unsigned)L.n_w, (unsigned)i_inc));
-    // rows of the inverse table (2-byte entries, one per direction, < 4 GB: xsw.hip): the largest threshold <= s - d gives a
+    // rows of the inverse table (2-byte entries, one per direction, < 4 GB: xsw_lutplan.hpp): the largest threshold <= s - d gives a
     // row at or below the band's first, the smallest threshold > s + d one past a row at or above its last
     const unsigned short *__restrict__ inv_tab = L.inv_rows;
     const unsigned inv_rowB = (unsigned)L.phi_pad * 2u;
@@ -287,7 +287,7 @@ __device__ __forceinline__ void co_band_pass(const DevTables &L, double inv_dsig
             for (int j = 0; j < K; ++j) {
                 if (left[j] == 0ULL) continue;  // wave-uniform: the j-th directions of this pass have no rows left (often the upper half)
                 // (a lane past its run -- masked below -- may read past the window, up to XSW_BAND_MAX rows: the table is padded by
-                // 260 rows, xsw.hip; r[j] <= n_w)
+                // 260 rows, xsw_lutplan.hpp; r[j] <= n_w)
                 const int rc = min(r[j] + t, w_hi);  // (unclamped -- the table is padded -- measured slower: masked lanes then touch new cache lines)
                 const double v = ld_co(base, off0[j], rc, rowB);
                 // the end rows may lie just outside the band: candidates of the window all the same, so scoring them is harmless

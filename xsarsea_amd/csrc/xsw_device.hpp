@@ -23,11 +23,9 @@
 
 #include <type_traits>
 
-namespace xsw {
+#include "xsw_lutplan.hpp"  // the table shapes (XSW_INV_BINS, XSW_TAIL_LEVELS, XSW_BLK_*, XSW_CELL_*)
 
-#ifndef XSW_INV_BINS
-#define XSW_INV_BINS 2048  // thresholds per slice of the inverse-row table (DevTables::inv_rows)
-#endif
+namespace xsw {
 
 struct DevTables {
     // co-pol LUT, dB
@@ -68,7 +66,7 @@ struct DevTables {
     double w0, inv_wstep, phi0, phi_last, inv_dphi;
     double wstep_half;  // 0.5 / inv_wstep (host: one IEEE division instead of one per wave and pass)
     double inv_nphi;    // 1 / n_phi: flat index -> (row, direction) without an integer division
-    int inc_uniform;    // incidence axis uniform (xsw.hip uniform_axis): nearest_index starts from the computed bin
+    int inc_uniform;    // incidence axis uniform (xsw_lutplan.hpp uniform_axis): nearest_index starts from the computed bin
     double inc0, inv_incstep;
     // cross-pol LUT, dB
     const double *cr;    // [n_inc_cr][wcr_pad]
@@ -83,9 +81,6 @@ struct DevTables {
     double inc_cr0, inv_inccrstep;
 };
 
-#ifndef XSW_TAIL_LEVELS
-#define XSW_TAIL_LEVELS 7  // levels of the sparse table of tail minima (DevTables::tail_min): windows of up to 2^7 - 1 directions
-#endif
 struct KArgs {
     const void *inc, *s_co, *s_cr, *dsig_cr, *anc;
     void *out_co, *out_cr;
@@ -732,19 +727,6 @@ __device__ __forceinline__ int co_box_search(const DevTables &L, int i_inc, doub
 // strictly above an examined one in the reference's arithmetic: it can neither be the argmin nor tie with it.  Settle as
 // everywhere: a unique candidate within eps of the screening minimum is the argmin; otherwise the kept blocks are swept once
 // more and every candidate within eps is re-scored in the reference's operation order (lowest flat index wins ties).
-#ifndef XSW_BLK_R
-#define XSW_BLK_R 4
-#endif
-#ifndef XSW_BLK_C
-#define XSW_BLK_C 16
-#endif
-#ifndef XSW_CELL_R
-#define XSW_CELL_R 8  // block rows ...
-#endif
-#ifndef XSW_CELL_C
-#define XSW_CELL_C 2  // ... x block columns of a level-1 cell of k_invert_blocks (32 speed rows x 32 directions: 16 blocks, one bounding step)
-#endif
-#define XSW_BLK_C4 4  // directions of a sub-block (k_invert_blocks: a kept block is bounded once more per quarter before it is swept)
 static_assert(XSW_BLK_R * XSW_BLK_C == 64, "one candidate of a block per lane");
 static_assert(XSW_BLK_C == 4 * XSW_BLK_C4, "four sub-blocks per block");
 __device__ __forceinline__ int co_block_search(const DevTables &L, int i_inc, double s, double a, double b, double jub_in, int w_lo, int w_hi,
@@ -1028,7 +1010,7 @@ __device__ __forceinline__ bool search_cr_interval(const DevTables &L, bool need
     jub = jub * (1.0 + 1e-9) + 1e-300;
     const double d = fabs(fast ? dsig : 1.0) * sqrt(jub) * (1.0 + 1e-9) + 1e-12 * (1.0 + fabs(sq));
     // the wind term is >= 0 too: ((w - |co|)/2)^2 <= J_ub, i.e. |w - |co|| <= 2 sqrt(J_ub): the index window [a0, a1] (with a
-    // margin; uniform axis to 1e-12: csrc/xsw.hip uniform_axis).  The sigma0 interval is then looked for inside it only
+    // margin; uniform axis to 1e-12: csrc/xsw_lutplan.hpp uniform_axis).  The sigma0 interval is then looked for inside it only
     // (shorter bisections); the three seed candidates satisfy both bounds.
     int a0 = 0, a1 = n - 1;
     if (fast && have_co) {

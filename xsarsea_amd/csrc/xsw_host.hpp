@@ -14,6 +14,7 @@
 #include "xsw.h"
 #include "xsw_device.hpp"
 #include "xsw_plan.hpp"
+#include "xsw_lutplan.hpp"
 
 #ifndef XSW_ARENA_KEEP
 #define XSW_ARENA_KEEP ((size_t)24 << 30)
@@ -30,9 +31,10 @@ struct xsw_ctx {
     bool stats_chain = false;               // xsw_stats_enable(ctx, 2): the production chain keeps running, its kernels count what they score
     bool timing_on = false;                 // xsw_timing_enable: HIP events around the kernels of every device-memory inversion
     std::vector<hipEvent_t> timing_events;  // quintuples (start, after k_invert_band, k_invert_band2, k_invert_blocks, k_invert_list) on the launch stream
+    size_t lists_bytes = 0;
     WorkLists lists;  // of the device-raster path (context-owned, grown on demand: list G an eighth of the largest raster seen)
     double *d_ratio = nullptr;  // detrend ratio row (context-owned, grown on demand)
-    size_t ratio_cap = 0;
+    size_t ratio_cap = 0;       // its bytes
     void *nesz_scratch = nullptr;  // xsw_nesz_flatten: column partials + means (context-owned, grown on demand)
     size_t nesz_cap = 0;
     // host-memory paths: worker w owns a stream, a page-locked staging buffer and a device staging buffer, all kept between calls
@@ -95,6 +97,82 @@ static inline long long env_int(const char *name, long long dflt, long long lo =
     return v ? std::min(std::max(atoll(v), lo), hi) : dflt;
 }
 static inline bool env_flag(const char *name) { return getenv(name) != nullptr; }
+
+// ---- device memory.  Two patterns, each spelled once: a sequence of allocations and stream operations whose first error
+// sticks (DevSeq; CallTemps is one that owns what it allocates), and a buffer that is kept and replaced by a larger one (grow).
+static inline void free_all(std::vector<void *> &v)
+{
+    for (void *p : v) (void)hipFree(p);
+    v.clear();
+}
+
+// Allocations recorded in `owner` and operations queued on `stream`, in order; after the first error every later call is a
+// no-op that returns nullptr, so a caller writes its steps as a list and asks once.
+struct DevSeq {
+    hipStream_t stream;
+    std::vector<void *> &owner;
+    hipError_t err = hipSuccess;
+    size_t refused = 0;  // bytes (slack included) of the allocation that failed: the callers' XSW_ENOMEM; 0: any other error
+
+    bool ok() const { return err == hipSuccess; }
+    void check(hipError_t e) { if (ok()) err = e; }
+    void zero(void *p, size_t bytes) { if (ok()) err = hipMemsetAsync(p, 0, bytes, stream); }
+    template <typename F> void run(F &&launches) { if (ok()) { launches(); err = hipGetLastError(); } }  // kernel launches on `stream`
+    void *alloc(size_t bytes, const void *host = nullptr, size_t slack = 0)  // host: uploaded, asynchronously
+    {
+        void *p = nullptr;
+        if (!ok()) return nullptr;
+        if ((err = hipMalloc(&p, bytes + slack)) != hipSuccess) { refused = bytes + slack; return nullptr; }
+        owner.push_back(p);
+        if (host && bytes) err = hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, stream);
+        return p;
+    }
+    // a table of a LUT install: count elements and XSW_OWNED_SLACK; one uploaded from `host` is synchronised at once (the
+    // host vector may be a temporary of the caller's)
+    template <typename V> V *table(size_t count, const V *host = nullptr)
+    {
+        V *p = (V *)alloc(count * sizeof(V), host, XSW_OWNED_SLACK);
+        if (p && host) check(hipStreamSynchronize(stream));
+        return p;
+    }
+    template <typename V> V *table(const std::vector<V> &host) { return table(host.size(), host.data()); }
+    // for a table an install can do without: true when every step since the construction succeeded; otherwise the runtime's
+    // sticky error is cleared, the caller leaves the table's pointer null and goes on
+    bool usable() const { if (!ok()) (void)hipGetLastError(); return ok(); }
+    int code() const { return err == hipErrorOutOfMemory ? XSW_ENOMEM : XSW_EHIP; }
+};
+
+// Temporaries of one call on one stream: freed after ONE stream synchronisation -- finish(), for a caller that wants its
+// result, or scope exit on a path that did not get there (work queued before a failure may still use them).
+struct CallTemps : DevSeq {
+    std::vector<void *> bufs;
+    explicit CallTemps(hipStream_t s) : DevSeq{s, bufs} {}
+    ~CallTemps() { if (!bufs.empty()) (void)finish(); }
+    hipError_t finish()
+    {
+        const hipError_t e = hipStreamSynchronize(stream);
+        free_all(bufs);
+        return e;
+    }
+};
+
+// A buffer kept between calls (device memory, or page-locked host memory) is replaced here and nowhere else: free, null,
+// cap = 0, then `need` bytes (0: release only) and cap = need.  wait_for: work queued on that stream may still use the old
+// buffer and is waited for first (nullptr: no wait; a null stream handle is the default stream, hence the pointer); when
+// the wait fails the buffer is left as it is.
+template <typename P>
+static inline hipError_t grow(P *&ptr, size_t &cap, size_t need, const hipStream_t *wait_for = nullptr, bool pinned = false)
+{
+    hipError_t e = wait_for ? hipStreamSynchronize(*wait_for) : hipSuccess;
+    if (e != hipSuccess) return e;
+    if (ptr) (void)(pinned ? hipHostFree(ptr) : hipFree(ptr));
+    ptr = nullptr;
+    cap = 0;
+    if (!need) return hipSuccess;
+    e = pinned ? hipHostMalloc((void **)&ptr, need, hipHostMallocDefault) : hipMalloc((void **)&ptr, need);
+    if (e == hipSuccess) cap = need;
+    return e;
+}
 
 // Where an inversion launches: its stream and the work lists that hand pixels from k_invert_band to the other kernels (device
 // rasters: the context's; host rasters: the worker's own, so that the chunks of different workers run side by side).

@@ -28,14 +28,12 @@ static int run(xsw_ctx *c, int32_t mem, Buf (&b)[N], Launch &&launch, const char
         const hipError_t e = hipGetLastError();
         return e == hipSuccess ? XSW_OK : fail(c, XSW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
     }
-    int rc = XSW_OK;
-    hipError_t e = hipSuccess;
+    CallTemps tmp(c->stream);
     for (auto &x : b)
-        if (e == hipSuccess && x.bytes) e = hipMalloc(&x.dev, x.bytes);
-    if (e != hipSuccess) rc = fail(c, XSW_ENOMEM, "%s: hipMalloc failed (%s)", what, hipGetErrorString(e));
-    for (auto &x : b)
-        if (!rc && x.host_in && x.bytes && (e = hipMemcpyAsync(x.dev, x.host_in, x.bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
-            rc = fail(c, XSW_EHIP, "%s: upload failed (%s)", what, hipGetErrorString(e));
+        if (x.bytes) x.dev = tmp.alloc(x.bytes, x.host_in);
+    int rc = tmp.ok() ? XSW_OK : tmp.refused ? fail(c, XSW_ENOMEM, "%s: hipMalloc failed (%s)", what, hipGetErrorString(tmp.err))
+                                             : fail(c, XSW_EHIP, "%s: upload failed (%s)", what, hipGetErrorString(tmp.err));
+    hipError_t e;
     if (!rc) {
         launch(b);
         if ((e = hipGetLastError()) != hipSuccess) rc = fail(c, XSW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
@@ -43,10 +41,8 @@ static int run(xsw_ctx *c, int32_t mem, Buf (&b)[N], Launch &&launch, const char
     for (auto &x : b)
         if (!rc && x.host_out && x.bytes && (e = hipMemcpyAsync(x.host_out, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
             rc = fail(c, XSW_EHIP, "%s: download failed (%s)", what, hipGetErrorString(e));
-    e = hipStreamSynchronize(c->stream);  // also before freeing after a failure: queued work may still use the temporaries
+    e = tmp.finish();  // the one synchronisation, also before freeing after a failure: queued work may still use the temporaries
     if (!rc && e != hipSuccess) rc = fail(c, XSW_EHIP, "%s: %s", what, hipGetErrorString(e));
-    for (auto &x : b)
-        if (x.dev) (void)hipFree(x.dev);
     return rc;
 }
 
