@@ -56,8 +56,9 @@ def test_empty_touched_shape_dtype():
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_in_place_piecewise_db_equals_the_one_shot_expression(dtype):
-    """The staging callback of `_engine.invert_numpy` converts sigma0 -> dB piece by piece, in place, into a foreign buffer
-    at arbitrary offsets (add, log10, multiply with out=): the bits must be those of `10 * np.log10(x + 1e-15)` on the whole
+    """The staging step (`_engine.stage_db`, behind the callbacks of `invert_numpy` and `invert_coded`) converts sigma0 -> dB
+    piece by piece, in place, into a foreign buffer at arbitrary offsets (add, log10, multiply with out=): the bits must be
+    those of `10 * np.log10(x + 1e-15)` on the whole
     raster whatever the piece boundaries and alignments (numpy's float32 log10 is a SIMD routine with masked tails)."""
     rng = np.random.default_rng(8)
     n = 300_007
@@ -72,12 +73,13 @@ def test_in_place_piecewise_db_equals_the_one_shot_expression(dtype):
         got = buf[shift:shift + n]
         edges = [0, 1, 17, 4096, 4099, 65536 + 5, 200_001, n]
         for a, b in zip(edges[:-1], edges[1:]):
-            out = got[a:b]
-            with np.errstate(all="ignore"):
-                np.add(x[a:b], 1e-15, out=out)
-                np.log10(out, out=out)
-                np.multiply(out, 10, out=out)
+            _engine.stage_db(x[a:b], got[a:b].ctypes.data, dtype)
         assert np.array_equal(ref.view(u), got.view(u)), (dtype, shift)
+        # the other dtype pairing (a float32 sigma0 among float64 rasters, say): the one-shot expression, cast on assignment
+        wide = np.empty(n, np.float64)
+        for a, b in zip(edges[:-1], edges[1:]):
+            _engine.stage_db(x[a:b], wide[a:b].ctypes.data, np.float64)
+        assert np.array_equal(ref.astype(np.float64).view(np.uint64), wide.view(np.uint64)), dtype
 
 
 def test_ensure_luts_never_leaves_a_stale_key():

@@ -102,6 +102,44 @@ class on_current_stream:
         return False
 
 
+def meta(t):
+    """(shape, numpy dtype) of a tensor, None for an absent one: what `windspeed._plan.CallPlan` is made from."""
+    return None if t is None else (tuple(t.shape), np.dtype(dict(_dtype_pairs()).get(t.dtype, np.void)))  # (void: none of the four)
+
+
+def _dtype_pairs():
+    import torch
+    return ((torch.float32, np.float32), (torch.float64, np.float64), (torch.complex64, np.complex64), (torch.complex128, np.complex128))
+
+
+def torch_dtype(dt):
+    return {np.dtype(n): t for t, n in _dtype_pairs()}[np.dtype(dt)]
+
+
+def prep(t, dtype, shape):
+    """The raster a kernel reads: `dtype`, broadcast to the call's shape, contiguous."""
+    return None if t is None else t.to(torch_dtype(dtype)).expand(shape).contiguous()
+
+
+def to_db(t):
+    """10*log10(t + 1e-15) in t's own dtype (windspeed.py:126-130)."""
+    import torch
+    return None if t is None else 10 * torch.log10(t + 1e-15)
+
+
+def keep_alive(tensors, device):
+    """The inputs of an asynchronous launch must outlive it: tie them to the stream they are read on."""
+    import torch
+    for t in tensors:
+        if t is not None:
+            t.record_stream(torch.cuda.current_stream(device))
+
+
+def at(t, off=0, size=0):
+    """Address of element `off` of a tensor of `size`-byte items, of its first element by default (None for an absent tensor)."""
+    return None if t is None else t.data_ptr() + off * size
+
+
 def xsw_dtype(t):
     import torch
     if t.dtype in (torch.float32, torch.complex64):

@@ -16,6 +16,20 @@ ALGO_AUTO, ALGO_PRUNED, ALGO_EXHAUSTIVE, ALGO_EXACT, ALGO_EXHAUSTIVE_F64 = 0, 1,
 ALGOS = {"auto": ALGO_AUTO, "pruned": ALGO_PRUNED, "exhaustive": ALGO_EXHAUSTIVE, "exact": ALGO_EXACT,
          "exhaustive_f64": ALGO_EXHAUSTIVE_F64}
 
+
+def lines_samples(shape):
+    """The (lines, samples) view of a raster: samples = the last axis, (1, 1) for a 0-d raster, (0, 0) for an empty one."""
+    n = int(np.prod(shape, dtype=np.int64))
+    if not n:
+        return 0, 0
+    return (n // shape[-1], shape[-1]) if len(shape) else (1, 1)
+
+
+def algo_code(algo):
+    """XSW_ALGO_* of an `options.algo` name (a code passes through)."""
+    return ALGOS.get(algo, algo)
+
+
 GMF_IDS = {"gmf_cmod5": 0, "gmf_cmod5n": 1, "gmf_cmod5n_pr_zhangA": 2, "gmf_cmod5n_pr_mouche1": 3, "gmf_cmodifr2": 4,
            "gmf_rs2_v2": 5, "gmf_s1_v2": 6, "gmf_rcm_noaa": 7, "gmf_s1_v3_ew_rec": 8, "gmf_rs2_v3": 9, "gmf_rcm_v3": 10,
            "gmf_rcm_v4": 11, "gmf_rs2_v4": 12}
@@ -491,9 +505,7 @@ class Context:
                                       if a is not None))
         inc = np.ascontiguousarray(np.broadcast_to(inc, shape))
         n = inc.size
-        lines, samples = (int(np.prod(shape[:-1])), shape[-1]) if inc.ndim >= 1 and n else (0, 0)
-        if inc.ndim == 0:
-            lines, samples = 1, 1
+        lines, samples = lines_samples(shape)
 
         def prep(a, t):
             if a is None:
@@ -529,7 +541,7 @@ class Context:
             self.invert_raw(lines, samples, XSW_F32 if dt == np.float32 else XSW_F64,
                             XSW_F32 if out_dtype == np.complex64 else XSW_F64, MEM_HOST_PINNED if pinned else MEM_HOST,
                             _ptr(inc), _ptr(s_co), _ptr(s_cr), _ptr(dsig_arr), _ptr(anc_), _ptr(out_co), _ptr(out_cr),
-                            _ptr(idx), dsig_co, dsig_scalar, sigma0_is_db, ALGOS.get(algo, algo), dual_select,
+                            _ptr(idx), dsig_co, dsig_scalar, sigma0_is_db, algo_code(algo), dual_select,
                             _ptr(codes[0]), _ptr(codes[1]), stage)
         if want_codes:
             return out_co, out_cr, idx, codes

@@ -34,25 +34,7 @@ def gather_chunk_async(tile, lines, k, n_chunks, dst=0, group=None, out=None, se
     Any dtype: complex winds, or the 4-byte grid codes of xsw_invert (`out_code_*`: a quarter / half of the bytes, expanded
     on `dst` by xsw_expand_codes).  self_copy=False: `dst` produced its own rows directly in `out` (nothing to copy)."""
     world = dist.get_world_size(group)
-    rank = dist.get_rank(group)
-    ops = []
-    if rank == dst:
-        for r in range(world):
-            t0, t1 = tile_bounds(lines, world, r)
-            c0, c1 = chunk_bounds(t1 - t0, n_chunks, k)
-            if c1 <= c0:
-                continue
-            if r == dst:
-                if self_copy:
-                    out[t0 + c0:t0 + c1].copy_(tile[c0:c1], non_blocking=True)
-            else:
-                ops.append(dist.P2POp(dist.irecv, out[t0 + c0:t0 + c1], r, group))
-    else:
-        t0, t1 = tile_bounds(lines, world, rank)
-        c0, c1 = chunk_bounds(t1 - t0, n_chunks, k)
-        if c1 > c0:
-            ops.append(dist.P2POp(dist.isend, tile[c0:c1], dst, group))
-    return dist.batch_isend_irecv(ops) if ops else []
+    return _gather_chunk_bounds(tile, lambda r: tile_bounds(lines, world, r), k, n_chunks, dst, group, out, self_copy)
 
 
 def gather_bytes_into(lines, samples, world, dst, bytes_per_pixel):
@@ -250,24 +232,53 @@ def _group_up():
     return dist.is_available() and dist.is_initialized()
 
 
-def _gather_chunk_bounds(tile, bounds, k, n_chunks, dst, group, out):
-    """`gather_chunk_async` for any row ownership `bounds(rank) -> (g0, g1)`; `dst` produced its own rows in place."""
+def _gather_chunk_bounds(tile, bounds, k, n_chunks, dst, group, out, self_copy=False):
+    """The loop of `gather_chunk_async`, for any row ownership `bounds(rank) -> (g0, g1)`: `dst` receives every peer's chunk
+    into its rows of `out` (and copies its own there with self_copy; else it produced them in place), a peer sends its own."""
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     ops = []
-    if rank == dst:
-        for r in range(world):
-            if r == dst:
-                continue
-            t0, t1 = bounds(r)
-            c0, c1 = chunk_bounds(t1 - t0, n_chunks, k)
-            if c1 > c0:
-                ops.append(dist.P2POp(dist.irecv, out[t0 + c0:t0 + c1], r, group))
-    else:
-        t0, t1 = bounds(rank)
+    for r in (range(world) if rank == dst else (rank,)):
+        t0, t1 = bounds(r)
         c0, c1 = chunk_bounds(t1 - t0, n_chunks, k)
-        if c1 > c0:
+        if c1 <= c0:
+            continue
+        if rank != dst:
             ops.append(dist.P2POp(dist.isend, tile[c0:c1], dst, group))
+        elif r != dst:
+            ops.append(dist.P2POp(dist.irecv, out[t0 + c0:t0 + c1], r, group))
+        elif self_copy:
+            out[t0 + c0:t0 + c1].copy_(tile[c0:c1], non_blocking=True)
     return dist.batch_isend_irecv(ops) if ops else []
+
+
+def chunk_calls(ctx, pipe, rasters, dt, odt, mem, scalars, flat=False, sigma0=None, second=True):
+    """The two callables `TiledPipeline.run` takes, over a tile resident in device memory.  rasters: (inc, sigma0_co, sigma0_cr,
+    dsig_cr, anc) contiguous tensors or None, reals of dtype code `dt`; complex winds of code `odt`; scalars: (dsig_co,
+    dsig_cr_scalar, sigma0_is_db, algo, dual_select) of `invert_raw`.  flat: a 1-D raster (a chunk is one line).
+    sigma0(off, npx, lines) -> (mem, sigma0_co, sigma0_cr, stage, held): a chunk's sigma0 addresses when they are not the
+    tensors'; `held`: tensors made for this chunk alone, kept alive across its launch and then tied to the launch stream.
+    second=False: the pipeline's second code raster is not this call's (`invert_tiled_device` without a cross-pol sigma0)."""
+    from . import _device, _lib
+    at = _device.at
+    inc, co, cr, dsig, anc = rasters
+    item, oitem = 4 if dt == _lib.XSW_F32 else 8, 8 if odt == _lib.XSW_F32 else 16
+    S = pipe.samples
+    codes_dual, full_codes_dual, full_dual = (pipe.codes_dual, pipe.full_codes_dual, pipe.full_dual) if second else (None, None, None)
+
+    def invert_chunk(k, r0, r1):
+        off, npx = r0 * S, (r1 - r0) * S
+        lines, samples = (1, npx) if flat else (r1 - r0, S)
+        m, p_co, p_cr, stage, held = (mem, at(co, off, item), at(cr, off, item), None, ()) if sigma0 is None else sigma0(off, npx, lines)
+        ctx.invert_raw(lines, samples, dt, odt, m, at(inc, off, item), p_co, p_cr, at(dsig, off, item), at(anc, off, 2 * item), None, None,
+                       None, *scalars, out_code_co=at(pipe.codes, off, 4), out_code_cr=at(codes_dual, off, 4), stage=stage)
+        _device.keep_alive(held, pipe.device)  # (`held` is referenced until here: freed after the launch, in stream order)
+
+    def expand_rows(g0, g1, stream):
+        off = g0 * S
+        ctx.expand_codes_on_stream(stream.cuda_stream, (g1 - g0) * S, odt, at(pipe.full_codes, off, 4), at(full_codes_dual, off, 4),
+                                   at(pipe.full, off, oitem), at(full_dual, off, oitem))
+
+    return invert_chunk, expand_rows
 
 
 def invert_tiled_device(ctx, inc, sigma0_co, anc, total_lines, *, sigma0_cr=None, dsig_cr=None, dst=0, group=None, n_chunks=8,
@@ -290,25 +301,11 @@ def invert_tiled_device(ctx, inc, sigma0_co, anc, total_lines, *, sigma0_cr=None
     if pipe.rows != lines or pipe.samples != samples or pipe.dual != dual:
         raise ValueError("the pipeline was built for another tile geometry")
     dt = _device.xsw_dtype(sigma0_co)
-    item = 4 if dt == _lib.XSW_F32 else 8
     odt = _lib.XSW_F32 if (pipe.full.dtype if pipe.full is not None else (out_dtype or torch.complex64)) == torch.complex64 else _lib.XSW_F64
-    oitem = 8 if odt == _lib.XSW_F32 else 16
-    algo = _lib.ALGO_AUTO if algo is None else _lib.ALGOS.get(algo, algo)
+    algo = _lib.ALGO_AUTO if algo is None else _lib.algo_code(algo)
     ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    at = lambda t, off, size: None if t is None else t.data_ptr() + off * size
-
-    def invert_chunk(k, r0, r1):
-        off = r0 * samples
-        ctx.invert_raw(r1 - r0, samples, dt, odt, _lib.MEM_DEVICE, at(inc, off, item), at(sigma0_co, off, item), at(sigma0_cr, off, item),
-                       at(dsig_cr, off, item), at(anc, off, 2 * item), None, None, None, dsig_co, dsig_cr_scalar, sigma0_is_db, algo,
-                       dual_select and dual, out_code_co=at(pipe.codes, off, 4), out_code_cr=at(pipe.codes_dual, off, 4) if dual else None)
-
-    def expand_rows(g0, g1, stream):
-        off = g0 * samples
-        ctx.expand_codes_on_stream(stream.cuda_stream, (g1 - g0) * samples, odt, at(pipe.full_codes, off, 4),
-                                   at(pipe.full_codes_dual, off, 4) if dual else None, at(pipe.full, off, oitem),
-                                   at(pipe.full_dual, off, oitem) if dual else None)
-
+    invert_chunk, expand_rows = chunk_calls(ctx, pipe, (inc, sigma0_co, sigma0_cr, dsig_cr, anc), dt, odt, _lib.MEM_DEVICE,
+                                            (dsig_co, dsig_cr_scalar, sigma0_is_db, algo, dual_select and dual), second=dual)
     pipe.run(invert_chunk, expand_rows)
     if not wait:
         return pipe

@@ -5,6 +5,7 @@ import ctypes
 import numpy as np
 
 from .. import _host, _lib, options
+from . import _plan
 
 
 def host_tables(wspd, phi):
@@ -209,6 +210,52 @@ def tile_rows(lines, parts):
     return [(k * base, lines if k == parts - 1 else (k + 1) * base) for k in range(parts)]
 
 
+def _staged(dst, npx, dt):
+    return np.frombuffer((ctypes.c_char * (npx * np.dtype(dt).itemsize)).from_address(dst), dtype=dt)
+
+
+def stage_db(x, dst, dt):
+    """The dB of the linear sigma0 slice `x` (1-D), as `dt` at address `dst`: numpy's own log10 in the raster's dtype is the
+    reference's arithmetic (windspeed.py:126-130) and, for float32, the only way to its bits (a platform-specific few-ulp SIMD
+    routine).  Same dtype: the three ufunc loops of `10 * np.log10(x + 1e-15)` write in place; else the one-shot expression."""
+    out = _staged(dst, x.size, dt)
+    with np.errstate(all="ignore"):
+        if x.dtype == dt:
+            np.add(x, 1e-15, out=out)
+            np.log10(out, out=out)
+            np.multiply(out, 10, out=out)
+        else:
+            out[...] = 10 * np.log10(x + 1e-15)
+
+
+def dsig_raster(sigma0_cr, dsig_cr):
+    """A scalar dsig_cr broadcast from the LINEAR sigma0_cr, in its dtype (windspeed.py:122-123; numpy array or torch tensor) --
+    finite where sigma0 is; formed from the dB value it would be NaN wherever sigma0_cr + 1e-15 == 0, i.e. -inf dB."""
+    with np.errstate(all="ignore"):
+        return sigma0_cr * 0 + dsig_cr
+
+
+def stage_fill(x, dsig_cr, dst, dt):
+    """`dsig_raster` of the linear cross-pol slice `x`, cast to `dt` on assignment at address `dst`."""
+    _staged(dst, x.size, dt)[...] = dsig_raster(x, dsig_cr)
+
+
+def _stager(src, dt, base=0, fill=None):
+    """The staging step of xsw_invert's host pipeline (xsw_invert_args.stage) over the flat linear rasters `src` {STAGE_*: array}:
+    the worker thread that is about to upload a piece calls back, numpy converts that piece straight into the page-locked
+    staging buffer -- no pass of its own, no dB raster in host memory.  Pixel offsets count from `base`; fill: a scalar dsig_cr."""
+    def stage(which, px0, npx, dst):
+        px0 += base
+        if which == _lib.STAGE_DSIG_CR and fill is not None:
+            stage_fill(src[_lib.STAGE_SIGMA0_CR][px0:px0 + npx], fill, dst, dt)
+        elif which in src:
+            stage_db(src[which][px0:px0 + npx], dst, dt)
+        else:
+            return 0  # (not a raster this call stages)
+        return 1
+    return stage
+
+
 def invert_numpy(lut_co, lut_cr, inc, sigma0_co, sigma0_cr, dsig_cr, anc, dsig_co=0.1, codes=False):
     """(ws_co, ws_cr) complex128 for numpy rasters (None for a search that was not requested); any of
     sigma0_co / sigma0_cr / anc may be None.  codes=True: the uint32 grid codes instead (include/xsw.h: out_code_*; what
@@ -223,107 +270,49 @@ def invert_numpy(lut_co, lut_cr, inc, sigma0_co, sigma0_cr, dsig_cr, anc, dsig_c
     written in place into the one output raster (pixels are independent: no exchange).
     """
     inc = np.asarray(inc)
-    rasters = [a for a in (inc, sigma0_co, sigma0_cr, None if np.isscalar(dsig_cr) else dsig_cr) if a is not None]
-    # the gufunc "(n),(n),(n),(n),(n)->(n),(n)" broadcasts its loop dimensions over ALL inputs (windspeed.py:307-322):
-    # e.g. a 1-D incidence row with 2-D sigma0 gives (line, sample) outputs
-    shape = np.broadcast_shapes(*(np.shape(a) for a in rasters + ([] if anc is None else [anc])))
-    all_f32 = all(np.asarray(a).dtype == np.float32 for a in rasters) and (
-        anc is None or np.asarray(anc).dtype == np.complex64)
-    on_dev = options.db_on_device
-    if on_dev == "auto":
-        on_dev = not any(np.asarray(a).dtype == np.float32 for a in (sigma0_co, sigma0_cr) if a is not None)
-    is_db = not on_dev
-    dt = np.float32 if all_f32 else np.float64
-    cast = lambda a, t: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a), shape), dtype=t)
-    cdt = np.complex64 if dt == np.float32 else np.complex128
-    want_co, want_cr = sigma0_co is not None, sigma0_cr is not None
-    lin = {}  # host dB: the linear sigma0 rasters in their OWN dtype; converted piece by piece inside the library's pipeline
-    if is_db:
-        # numpy's own log10 in the raster's dtype is the reference's arithmetic (windspeed.py:126-130) and, for float32, the
-        # only way to its bits (a platform-specific few-ulp SIMD routine).  It runs as the STAGING step of xsw_invert's host
-        # pipeline (xsw_invert_args.stage): the worker thread that is about to upload a piece calls back, numpy converts that
-        # piece straight into the page-locked staging buffer -- no pass of its own, no dB raster in host memory.
-        as_src = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a), shape))
-        if want_co:
-            lin[_lib.STAGE_SIGMA0_CO] = as_src(sigma0_co)
-        if want_cr:
-            lin[_lib.STAGE_SIGMA0_CR] = as_src(sigma0_cr)
-    dsig_fill = None
-    if want_cr and np.isscalar(dsig_cr):
-        if is_db:  # the kernel derives the broadcast from linear sigma0; with dB rasters it is formed as the reference does
-            dsig_fill = dsig_cr  # sigma0_cr * 0 + dsig_cr  (windspeed.py:122-123), piece by piece in the staging callback
-        elif dt == np.float32:
-            dsig_cr = float(np.float32(dsig_cr))
-    full = dict(inc=cast(inc, dt), anc=cast(anc, cdt))
-    # rasters the staging callback fills are never read through their pointer: the incidence raster stands in (right size)
-    full["sigma0_co"] = None if not want_co else (full["inc"] if is_db else cast(sigma0_co, dt))
-    full["sigma0_cr"] = None if not want_cr else (full["inc"] if is_db else cast(sigma0_cr, dt))
-    if dsig_fill is not None:
-        full["dsig_cr"] = full["inc"]
-    else:
-        full["dsig_cr"] = dsig_cr if (dsig_cr is None or np.isscalar(dsig_cr)) else cast(dsig_cr, dt)
-
-    def stage_for(rows):
-        """The staging callback of one row tile (pixel offsets are tile-local)."""
-        if not lin:
-            return None
-        sl = (lambda a: a) if rows is None else (lambda a: a[rows[0]:rows[1]])
-        src = {k: sl(v).reshape(-1) for k, v in lin.items()}
-        item = np.dtype(dt).itemsize
-
-        def stage(which, px0, npx, dst):
-            if which == _lib.STAGE_DSIG_CR and dsig_fill is not None:
-                x = src[_lib.STAGE_SIGMA0_CR][px0:px0 + npx]
-            elif which in src:
-                x = src[which][px0:px0 + npx]
-            else:
-                return 0
-            out = np.frombuffer((ctypes.c_char * (npx * item)).from_address(dst), dtype=dt)
-            with np.errstate(all="ignore"):
-                if which == _lib.STAGE_DSIG_CR:
-                    out[...] = x * 0 + dsig_fill
-                elif x.dtype == dt:  # 10 * np.log10(x + 1e-15), the three ufunc loops writing in place
-                    np.add(x, 1e-15, out=out)
-                    np.log10(out, out=out)
-                    np.multiply(out, 10, out=out)
-                else:
-                    out[...] = 10 * np.log10(x + 1e-15)
-            return 1
-        return stage
+    plan = _plan.CallPlan(_plan.meta(inc), _plan.meta(sigma0_co), _plan.meta(sigma0_cr),
+                          dsig_cr if np.isscalar(dsig_cr) else _plan.meta(dsig_cr), _plan.meta(anc), device=False)
+    shape, dt, want_co, want_cr = plan.shape, plan.dtype, plan.want_co, plan.want_cr
+    cast = lambda a, t=dt: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a), shape), dtype=t)
+    full_inc = cast(inc)
+    # host dB: the linear sigma0 rasters stay in their OWN dtype and are converted piece by piece by the staging callback; they
+    # (and a scalar dsig_cr's raster) are never read through their pointer: the incidence raster stands in (right size)
+    lin = {w: cast(a, None) for w, a in ((_lib.STAGE_SIGMA0_CO, sigma0_co), (_lib.STAGE_SIGMA0_CR, sigma0_cr)) if plan.is_db and a is not None}
+    full = dict(sigma0_co=full_inc if lin else cast(sigma0_co), sigma0_cr=full_inc if lin else cast(sigma0_cr), anc=cast(anc, plan.cdtype),
+                dsig_cr=full_inc if plan.dsig == _plan.DSIG_FILL else (cast(dsig_cr) if plan.dsig == _plan.DSIG_RASTER else plan.dsig_scalar))
+    if not want_co:
+        full["sigma0_co"] = None
+    if not want_cr:
+        full["sigma0_cr"] = None
 
     def run(ctx, rows, out_co, out_cr):
-        """One context inverts rows [l0, l1) of the (lines, samples) view of every raster, into the same rows of the outputs."""
-        sl = (lambda a: a) if rows is None else (lambda a: a[rows[0]:rows[1]])
+        """One context inverts rows [l0, l1) of the (lines, samples) view of every raster, into the same rows of the outputs
+        (pixel offsets of the staging callback are tile-local)."""
+        cut = lambda a: a if (rows is None or a is None or np.isscalar(a)) else a[rows[0]:rows[1]]
+        stage = _stager({w: cut(a).reshape(-1) for w, a in lin.items()}, dt, fill=plan.dsig_fill) if lin else None
         with ctx.lock:  # LUT upload + inversion as one step: another thread may want other LUTs on the same context
             ensure_luts(ctx, lut_co if want_co else None, lut_cr if want_cr else None)
             if options.host_threads:
                 ctx.set_host_threads(options.host_threads)
-            res = ctx.invert_host(sl(full["inc"]), sigma0_co=None if not want_co else sl(full["sigma0_co"]),
-                                   sigma0_cr=None if not want_cr else sl(full["sigma0_cr"]),
-                                   dsig_cr=full["dsig_cr"] if (full["dsig_cr"] is None or np.isscalar(full["dsig_cr"])) else sl(full["dsig_cr"]),
-                                   anc=None if full["anc"] is None else sl(full["anc"]), dsig_co=dsig_co, sigma0_is_db=is_db,
-                                   algo=options.algo, out_dtype=np.complex128, out_co=None if out_co is None else sl(out_co),
-                                   out_cr=None if out_cr is None else sl(out_cr), stage=stage_for(rows), want_codes=codes,
-                                   want_complex=not codes)
+            res = ctx.invert_host(cut(full_inc), **{k: cut(a) for k, a in full.items()}, dsig_co=dsig_co, sigma0_is_db=plan.is_db,
+                                  algo=plan.algo, out_dtype=plan.out_dtype, out_co=cut(out_co), out_cr=cut(out_cr), stage=stage,
+                                  want_codes=codes, want_complex=not codes)
             return (res[3][0], res[3][1], None) if codes else res
 
     devs = _device_list()
-    n = int(np.prod(shape, dtype=np.int64)) if len(shape) else 1
-    if codes or devs is None or len(devs) == 1 or len(shape) < 2 or n < options.devices_min_pixels or shape[0] < 4 * len(devs):
+    if codes or devs is None or len(devs) == 1 or len(shape) < 2 or plan.n < options.devices_min_pixels or shape[0] < 4 * len(devs):
         # one device: `options.device`, or the one entry of `options.devices` (a one-entry list names THE device, whatever the
         # raster's size); several entries with a raster too small to tile: the first of them
         one = options.device if devs is None else devs[0]
         out_co, out_cr, _ = run(_lib.default_context(one), None, None, None)
         return out_co, out_cr  # None where that search did not run (the caller never reads it)
     # several GPUs: contiguous row tiles of the leading axis, one host thread and one context per GPU, results in place
-    lines = shape[0]
-    out_co = np.empty(shape, np.complex128) if want_co else None
-    out_cr = np.empty(shape, np.complex128) if want_cr else None
+    out_co = np.empty(shape, plan.out_dtype) if want_co else None
+    out_cr = np.empty(shape, plan.out_dtype) if want_cr else None
     ctxs = _lib.contexts_for(devs)
-    tiles = tile_rows(lines, len(ctxs))
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max_workers=len(ctxs)) as ex:
-        futs = [ex.submit(run, c, t, out_co, out_cr) for c, t in zip(ctxs, tiles) if t[1] > t[0]]
+        futs = [ex.submit(run, c, t, out_co, out_cr) for c, t in zip(ctxs, tile_rows(shape[0], len(ctxs))) if t[1] > t[0]]
         for f in futs:
             f.result()  # re-raises a tile's error here
     return out_co, out_cr
@@ -337,6 +326,25 @@ def expand_codes(lut_co, lut_cr, codes_co, codes_cr):
         return ctx.expand_codes_host(codes_co, codes_cr)
 
 
+def _device_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc, dual_select, broadcast=None):
+    """(plan, device, [inc, sigma0_co, sigma0_cr, dsig_cr, anc] as the kernel reads them) for rasters resident in HBM (host
+    arrays among them are uploaded).  Mixed dtypes (float32 sigma0 next to a float64 incidence, say): torch converts sigma0 to
+    dB in sigma0's OWN dtype before anything is widened, after a scalar dsig_cr was broadcast from the LINEAR sigma0_cr.
+    broadcast: the caller's own shape check (`invert_device`: torch's, whose error a shape mismatch has always raised there)."""
+    from .. import _device
+    args = (inc, sigma0_co, sigma0_cr, None if np.isscalar(dsig_cr) else dsig_cr, anc)
+    dev = _device.device_of(*(a for a in args if a is not None))
+    t = [None if a is None else _device.as_tensor(a, dev) for a in args]
+    if broadcast is not None:
+        broadcast(*(x.shape for x in t if x is not None))
+    plan = _plan.CallPlan(*(dsig_cr if (k == 3 and x is None) else _device.meta(x) for k, x in enumerate(t)), device=True, dual_select=dual_select)
+    if plan.dsig == _plan.DSIG_FILL:
+        t[3] = dsig_raster(t[2], dsig_cr)
+    if plan.db_by == _plan.DB_TORCH:
+        t[1], t[2] = _device.to_db(t[1]), _device.to_db(t[2])
+    return plan, dev, [_device.prep(x, plan.cdtype if k == 4 else plan.dtype, plan.shape) for k, x in enumerate(t)]
+
+
 def invert_device(lut_co, lut_cr, inc, sigma0_co, sigma0_cr, dsig_cr, anc, dsig_co=0.1, dual_select=False):
     """(ws_co, ws_cr) torch complex tensors for rasters resident in HBM (torch CUDA tensors / `__cuda_array_interface__`
     objects; host arrays among them are uploaded): the drop-in call without PCIe.  sigma0 -> dB is fused into the kernel
@@ -345,51 +353,39 @@ def invert_device(lut_co, lut_cr, inc, sigma0_co, sigma0_cr, dsig_cr, anc, dsig_
     bit).  Asynchronous on torch's current stream.  dual_select: ws_cr receives the fused where(|co|<5 | |dual|<5, co, dual)."""
     import torch
     from .. import _device
-    arrays = [a for a in (inc, sigma0_co, sigma0_cr, None if np.isscalar(dsig_cr) else dsig_cr, anc) if a is not None]
-    dev = _device.device_of(*arrays)
+    plan, dev, t = _device_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc, dual_select, broadcast=torch.broadcast_shapes)
     ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
-    t_inc = _device.as_tensor(inc, dev)
-    t_co = None if sigma0_co is None else _device.as_tensor(sigma0_co, dev)
-    t_cr = None if sigma0_cr is None else _device.as_tensor(sigma0_cr, dev)
-    t_dsig = None if (dsig_cr is None or np.isscalar(dsig_cr)) else _device.as_tensor(dsig_cr, dev)
-    t_anc = None if anc is None else _device.as_tensor(anc, dev)
-    rasters = [t for t in (t_inc, t_co, t_cr, t_dsig) if t is not None]
-    shape = torch.broadcast_shapes(*(t.shape for t in rasters + ([] if t_anc is None else [t_anc])))
-    all_f32 = all(t.dtype == torch.float32 for t in rasters) and (t_anc is None or t_anc.dtype == torch.complex64)
-    rt, ct = (torch.float32, torch.complex64) if all_f32 else (torch.float64, torch.complex128)
-    is_db = False
-    if not all_f32 and any(t is not None and t.dtype == torch.float32 for t in (t_co, t_cr)):
-        # mixed dtypes (float32 sigma0 next to a float64 incidence, say): the reference converts sigma0 to dB in sigma0's OWN dtype
-        # (windspeed.py:126-130) before anything is widened -- do that here, then hand dB rasters to the kernel
-        to_db = lambda t: None if t is None else (10 * torch.log10(t + 1e-15))
-        # a scalar dsig_cr is broadcast from the LINEAR sigma0_cr, in its dtype (windspeed.py:122-123: sigma0_cr * 0 + dsig_cr --
-        # finite where sigma0 is; formed from the dB value it would be NaN wherever sigma0_cr + 1e-15 == 0, i.e. -inf dB)
-        if t_cr is not None and t_dsig is None and dsig_cr is not None:
-            t_dsig = t_cr * 0 + dsig_cr
-        t_co, t_cr, is_db = to_db(t_co), to_db(t_cr), True
-    prep = lambda t, d: None if t is None else t.to(d).expand(shape).contiguous()
-    t_inc, t_co, t_cr, t_dsig, t_anc = prep(t_inc, rt), prep(t_co, rt), prep(t_cr, rt), prep(t_dsig, rt), prep(t_anc, ct)
-    dsig_scalar = 0.1
-    if t_cr is not None and t_dsig is None and dsig_cr is not None:
-        dsig_scalar = float(np.float32(dsig_cr)) if all_f32 else float(dsig_cr)
-    odt = torch.complex64 if options.device_out_dtype == "complex64" else torch.complex128
-    out_co = torch.empty(shape, dtype=odt, device=dev) if t_co is not None else None
-    out_cr = torch.empty(shape, dtype=odt, device=dev) if t_cr is not None else None
-    n = int(np.prod(shape, dtype=np.int64)) if len(shape) else 1
-    lines, samples = (n // shape[-1], shape[-1]) if len(shape) and n else (1 if n else 0, 1 if n else 0)
-    p = lambda t: None if t is None else t.data_ptr()
-    if n:
+    odt = _device.torch_dtype(plan.out_dtype)
+    out_co = torch.empty(plan.shape, dtype=odt, device=dev) if plan.want_co else None
+    out_cr = torch.empty(plan.shape, dtype=odt, device=dev) if plan.want_cr else None
+    p = _device.at
+    if plan.n:
         with _device.on_current_stream(ctx, dev):
-            ensure_luts(ctx, lut_co if t_co is not None else None, lut_cr if t_cr is not None else None)
-            ctx.invert_raw(lines, samples, _lib.XSW_F32 if all_f32 else _lib.XSW_F64,
-                           _lib.XSW_F32 if odt == torch.complex64 else _lib.XSW_F64, _lib.MEM_DEVICE, p(t_inc), p(t_co), p(t_cr),
-                           p(t_dsig), p(t_anc), p(out_co), p(out_cr), None, dsig_co, dsig_scalar, is_db,
-                           _lib.ALGOS.get(options.algo, options.algo), dual_select and out_cr is not None and out_co is not None)
-            # the inputs must outlive the asynchronous launch: tie them to the stream they are read on
-            for t in (t_inc, t_co, t_cr, t_dsig, t_anc):
-                if t is not None:
-                    t.record_stream(torch.cuda.current_stream(dev))
+            ensure_luts(ctx, lut_co if plan.want_co else None, lut_cr if plan.want_cr else None)
+            ctx.invert_raw(plan.lines, plan.samples, plan.code, plan.out_code, _lib.MEM_DEVICE, *(p(x) for x in t), p(out_co), p(out_cr),
+                           None, dsig_co, plan.dsig_scalar, plan.is_db, plan.algo, plan.fused_select)
+            _device.keep_alive(t, dev)
     return out_co, out_cr
+
+
+def _uploaded_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc):
+    """`_device_rasters` for a tile of numpy rasters, which follow `invert_numpy`'s arithmetic: (plan, device, tensors, src).
+    With host dB the linear sigma0 stays on the host -- `src` {STAGE_*: flat raster}, converted piece by piece on its way up,
+    its tensors None -- and a scalar dsig_cr's raster is formed whole, in sigma0's own dtype, and uploaded."""
+    import torch
+    from .. import _device
+    h = [None if a is None or np.isscalar(a) else np.asarray(a) for a in (inc, sigma0_co, sigma0_cr, dsig_cr, anc)]
+    plan = _plan.CallPlan(*(dsig_cr if (k == 3 and x is None) else _plan.meta(x) for k, x in enumerate(h)), device=False, coded=True)
+    dev = torch.device("cuda", int(options.device))
+    if plan.dsig == _plan.DSIG_FILL:
+        h[3] = dsig_raster(h[2], dsig_cr)
+    src = {}
+    if plan.is_db:
+        src = {w: np.ascontiguousarray(np.broadcast_to(h[k], plan.shape)).reshape(-1)
+               for k, w in ((1, _lib.STAGE_SIGMA0_CO), (2, _lib.STAGE_SIGMA0_CR)) if h[k] is not None}
+        h[1] = h[2] = None
+    t = [None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in h]
+    return plan, dev, [_device.prep(x, plan.cdtype if k == 4 else plan.dtype, plan.shape) for k, x in enumerate(t)], src
 
 
 def invert_coded(lut_co, lut_cr, inc, sigma0_co, sigma0_cr, dsig_cr, anc, dsig_co, sink, dual_select=False):
@@ -406,113 +402,36 @@ def invert_coded(lut_co, lut_cr, inc, sigma0_co, sigma0_cr, dsig_cr, anc, dsig_c
     are already resident (XSW_MEM_DEVICE_SIGMA0_HOST) -- and a scalar `dsig_cr` is broadcast from the LINEAR sigma0
     (windspeed.py:122-123).  Device rasters follow `invert_device` (sigma0 -> dB fused, the dual-pol select fused)."""
     import torch
-    from .. import _device
-    given = [a for a in (inc, sigma0_co, sigma0_cr, None if np.isscalar(dsig_cr) else dsig_cr, anc) if a is not None]
-    on_device = _device.any_device_array(*given)
-    dev = _device.device_of(*given) if on_device else torch.device("cuda", int(options.device))
-    ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
-    want_co, want_cr = sigma0_co is not None, sigma0_cr is not None
-    shape = tuple(np.broadcast_shapes(*(tuple(np.shape(a)) for a in given)))
-    n = int(np.prod(shape, dtype=np.int64)) if len(shape) else 1
-    host_lin, is_db = {}, False
-    if on_device:
-        t = {k: (None if v is None or np.isscalar(v) else _device.as_tensor(v, dev)) for k, v in
-             (("inc", inc), ("co", sigma0_co), ("cr", sigma0_cr), ("dsig", dsig_cr), ("anc", anc))}
-        rasters = [t[k] for k in ("inc", "co", "cr", "dsig") if t[k] is not None]
-        all_f32 = all(x.dtype == torch.float32 for x in rasters) and (t["anc"] is None or t["anc"].dtype == torch.complex64)
-        if not all_f32 and any(t[k] is not None and t[k].dtype == torch.float32 for k in ("co", "cr")):
-            if want_cr and t["dsig"] is None and dsig_cr is not None:  # scalar dsig_cr: broadcast from the LINEAR sigma0, in its dtype
-                t["dsig"] = t["cr"] * 0 + dsig_cr
-            to_db = lambda x: None if x is None else (10 * torch.log10(x + 1e-15))
-            t["co"], t["cr"], is_db = to_db(t["co"]), to_db(t["cr"]), True
+    from .. import _device, multi_gpu
+    if _device.any_device_array(inc, sigma0_co, sigma0_cr, dsig_cr, anc):
+        (plan, dev, t), src = _device_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc, dual_select), {}
     else:
-        arr = lambda a: None if a is None or np.isscalar(a) else np.asarray(a)
-        h = dict(inc=arr(inc), co=arr(sigma0_co), cr=arr(sigma0_cr), dsig=arr(dsig_cr), anc=arr(anc))
-        rasters = [h[k] for k in ("inc", "co", "cr", "dsig") if h[k] is not None]
-        all_f32 = all(x.dtype == np.float32 for x in rasters) and (h["anc"] is None or h["anc"].dtype == np.complex64)
-        on_dev = options.db_on_device
-        if on_dev == "auto":
-            on_dev = not any(h[k] is not None and h[k].dtype == np.float32 for k in ("co", "cr"))
-        is_db = not on_dev
-        if is_db and want_cr and h["dsig"] is None and dsig_cr is not None:
-            with np.errstate(all="ignore"):
-                h["dsig"] = h["cr"] * 0 + dsig_cr  # windspeed.py:122-123, from the linear sigma0 in its own dtype
-        if is_db:  # sigma0 stays on the host: converted piece by piece on its way up
-            host_lin = {k: np.ascontiguousarray(np.broadcast_to(h[k], shape)) for k in ("co", "cr") if h[k] is not None}
-        t = {k: (None if v is None or (is_db and k in ("co", "cr")) else torch.from_numpy(np.ascontiguousarray(v)).to(dev)) for k, v in h.items()}
-    rt, ct = (torch.float32, torch.complex64) if all_f32 else (torch.float64, torch.complex128)
-    npdt = np.float32 if all_f32 else np.float64
-    prep = lambda x, d: None if x is None else x.to(d).expand(shape).contiguous()
-    t_inc, t_co, t_cr, t_dsig, t_anc = prep(t["inc"], rt), prep(t["co"], rt), prep(t["cr"], rt), prep(t["dsig"], rt), prep(t["anc"], ct)
-    dsig_scalar = 0.1
-    if want_cr and t_dsig is None and dsig_cr is not None:
-        dsig_scalar = float(np.float32(dsig_cr)) if all_f32 else float(dsig_cr)
-    numpy_out = not on_device
-    odt = torch.complex128 if (numpy_out or options.device_out_dtype != "complex64") else torch.complex64
-    sink.begin(shape, want_co, want_cr, dev, odt)
-    pipe = sink.pipe
-    S = pipe.samples
-    item, oitem = (4 if all_f32 else 8), (8 if odt == torch.complex64 else 16)
-    xdt, xodt = (_lib.XSW_F32 if all_f32 else _lib.XSW_F64), (_lib.XSW_F32 if odt == torch.complex64 else _lib.XSW_F64)
-    algo = _lib.ALGOS.get(options.algo, options.algo)
-    fused_select = bool(dual_select and want_co and want_cr and on_device)
+        plan, dev, t, src = _uploaded_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc)
+    ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    sink.begin(plan.shape, plan.want_co, plan.want_cr, dev, _device.torch_dtype(plan.out_dtype))
     with ctx.lock:
-        ensure_luts(ctx, lut_co if want_co else None, lut_cr if want_cr else None)  # (also on a rank whose tile is empty: it may expand)
-    at = lambda x, off, size: None if x is None else x.data_ptr() + off * size
-    src = {k: v.reshape(-1) for k, v in host_lin.items()}
+        ensure_luts(ctx, lut_co if plan.want_co else None, lut_cr if plan.want_cr else None)  # (also on a rank whose tile is empty: it may expand)
 
-    def stage_for(px_base):
-        def stage(which, px0, npx, dst):
-            key = "co" if which == _lib.STAGE_SIGMA0_CO else ("cr" if which == _lib.STAGE_SIGMA0_CR else None)
-            if key not in src:
-                return 0
-            x = src[key][px_base + px0:px_base + px0 + npx]
-            out = np.frombuffer((ctypes.c_char * (npx * item)).from_address(dst), dtype=npdt)
-            with np.errstate(all="ignore"):
-                if x.dtype == npdt:
-                    np.add(x, 1e-15, out=out)
-                    np.log10(out, out=out)
-                    np.multiply(out, 10, out=out)
-                else:
-                    out[...] = 10 * np.log10(x + 1e-15)
-            return 1
-        return stage
+    def host_sigma0(off, npx, lines):
+        """sigma0 of one chunk of host-dB rasters: through the staging ring (the host addresses are never read: the callback
+        fills every piece), or -- a chunk too thin for the ring -- numpy's dB of these rows, uploaded (the tensors go back with
+        their addresses: the chunk's launch holds them)."""
+        if lines >= 4:
+            return (_lib.MEM_DEVICE_SIGMA0_HOST,) + tuple(None if w not in src else src[w].ctypes.data + off * src[w].itemsize
+                                                           for w in (_lib.STAGE_SIGMA0_CO, _lib.STAGE_SIGMA0_CR)) + (_stager(src, plan.dtype, off), ())
+        up = {w: np.empty(npx, plan.dtype) for w in src}
+        for w, buf in up.items():
+            stage_db(src[w][off:off + npx], buf.ctypes.data, plan.dtype)
+        up = {w: torch.from_numpy(buf).to(dev) for w, buf in up.items()}  # (held by the chunk's launch: `chunk_calls`)
+        return _lib.MEM_DEVICE, _device.at(up.get(_lib.STAGE_SIGMA0_CO)), _device.at(up.get(_lib.STAGE_SIGMA0_CR)), None, list(up.values())
 
-    def invert_chunk(k, r0, r1):
-        off, npx = r0 * S, (r1 - r0) * S
-        lines, samples = ((r1 - r0), S) if len(shape) >= 2 else (1, npx)
-        p_co = at(t_co, off, item) if t_co is not None else (at(t_inc, off, item) if "co" in src else None)
-        p_cr = at(t_cr, off, item) if t_cr is not None else (at(t_inc, off, item) if "cr" in src else None)
-        host_route = bool(src) and lines >= 4
-        if src and not host_route:  # a chunk too thin for the staging ring: numpy's dB of these rows, uploaded
-            with np.errstate(all="ignore"):
-                up = {key: torch.from_numpy(np.ascontiguousarray(10 * np.log10(v[off:off + npx] + 1e-15)).astype(npdt, copy=False)).to(dev) for key, v in src.items()}
-            p_co = up["co"].data_ptr() if "co" in up else p_co
-            p_cr = up["cr"].data_ptr() if "cr" in up else p_cr
-            for x in up.values():
-                x.record_stream(torch.cuda.current_stream(dev))
-        if host_route:
-            # (pointers of the host rasters are never read: the staging callback fills every piece)
-            ctx.invert_raw(lines, samples, xdt, xodt, _lib.MEM_DEVICE_SIGMA0_HOST, at(t_inc, off, item),
-                           src["co"].ctypes.data + off * src["co"].itemsize if "co" in src else None,
-                           src["cr"].ctypes.data + off * src["cr"].itemsize if "cr" in src else None,
-                           at(t_dsig, off, item), at(t_anc, off, 2 * item), None, None, None, dsig_co, dsig_scalar, True, algo, False,
-                           out_code_co=at(pipe.codes, off, 4), out_code_cr=at(pipe.codes_dual, off, 4), stage=stage_for(off))
-        else:
-            ctx.invert_raw(lines, samples, xdt, xodt, _lib.MEM_DEVICE, at(t_inc, off, item), p_co, p_cr, at(t_dsig, off, item),
-                           at(t_anc, off, 2 * item), None, None, None, dsig_co, dsig_scalar, is_db, algo, fused_select,
-                           out_code_co=at(pipe.codes, off, 4), out_code_cr=at(pipe.codes_dual, off, 4))
-
-    def expand_rows(g0, g1, stream):
-        off = g0 * S
-        ctx.expand_codes_on_stream(stream.cuda_stream, (g1 - g0) * S, xodt, at(pipe.full_codes, off, 4), at(pipe.full_codes_dual, off, 4),
-                                   at(pipe.full, off, oitem), at(pipe.full_dual, off, oitem))
+    invert_chunk, expand_rows = multi_gpu.chunk_calls(
+        ctx, sink.pipe, t, plan.code, plan.out_code, _lib.MEM_DEVICE,
+        (dsig_co, plan.dsig_scalar, plan.is_db, plan.algo, plan.fused_select), flat=len(plan.shape) < 2, sigma0=host_sigma0 if src else None)
 
     def launch():
         with _device.on_current_stream(ctx, dev):
-            pipe.run(invert_chunk, expand_rows)
-            for x in (t_inc, t_co, t_cr, t_dsig, t_anc):
-                if x is not None:
-                    x.record_stream(torch.cuda.current_stream(dev))
+            sink.pipe.run(invert_chunk, expand_rows)
+            _device.keep_alive(t, dev)
 
     return launch
