@@ -211,6 +211,27 @@ int xsw_expand_codes(xsw_ctx *ctx, int64_t n, int32_t mem, int32_t out_dtype, co
 int xsw_expand_codes_on_stream(xsw_ctx *ctx, void *stream, int64_t n, int32_t out_dtype, const uint32_t *code_co,
                                const uint32_t *code_cr, void *out_co, void *out_cr);
 
+/* Additive to XSW_VERSION 4.  The cross-pol step of a dual-pol inversion from STORED co-pol codes: replaces windspeed.py:252-278
+ * (cross-pol cost Jsig_cr [+ Jwind_cr], argmin, wind_dual = wspd_dual * exp(1j * angle(wind_co))) and, with dual_select, the
+ * select :426-428, for a co-pol answer that is already there as xsw_invert's out_code_co.  The code holds all the cross-pol
+ * step needs of the co-pol search -- whether it ran, whether the pixel was an early NaN (:198-207), |wind_co| and its direction
+ * (tables of the context's co-pol LUT) -- so another cross-pol GMF or another dsig_cr costs ONE pass of 16-20 B per pixel, not
+ * the co-pol search again.  out_code_cr / out_cr receive, bit for bit, what one dual-pol xsw_invert of the same rasters writes
+ * to out_code_cr / out_cr (either may be NULL, not both).
+ *   code_co      the co-pol codes of these pixels from the context's CURRENT co-pol LUT; NULL: every pixel XSW_CODE_NAN, i.e. the
+ *                cross-pol-only inversion (J_cr = Jsig_cr, wind_dual = wspd_dual + 0j).  A value that is no code of that LUT
+ *                (bit 31 set and neither NaN code, or an index at or beyond n_wspd * n_phi) reads no table: the pixel is
+ *                handled as XSW_CODE_NAN_RE.  The ancillary wind is no input: its effect is in the code.
+ *   sigma0_cr    `dtype` raster, converted to dB as xsw_invert does (sigma0_is_db as there); dsig_cr a `dtype` raster, or NULL:
+ *                dsig_cr_scalar broadcast as sigma0_cr * 0 + dsig_cr in `dtype` (:122-123).
+ *   out_dtype    XSW_F32 -> complex64 out_cr, XSW_F64 -> complex128.
+ * XSW_ENOLUT without a cross-pol LUT, or with code_co and no co-pol LUT; XSW_EINVAL for both outputs NULL, a NULL inc or
+ * sigma0_cr, a bad dtype or mem.  XSW_MEM_DEVICE: one kernel (k_cross_from_codes), asynchronous on the context's stream;
+ * XSW_MEM_HOST: upload, kernel, download, returns with the outputs filled. */
+int xsw_cross_from_codes(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                         int32_t sigma0_is_db, int32_t dual_select, const void *inc, const uint32_t *code_co,
+                         const void *sigma0_cr, const void *dsig_cr, double dsig_cr_scalar, uint32_t *out_code_cr, void *out_cr);
+
 /* Page-locked host memory for rasters a caller fills itself (XSW_MEM_HOST_PINNED); freed by xsw_host_free or with the context. */
 int xsw_host_alloc(xsw_ctx *ctx, size_t bytes, void **out);
 int xsw_host_free(xsw_ctx *ctx, void *p);

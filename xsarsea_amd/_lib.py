@@ -42,6 +42,7 @@ EXPORTS = (
     "xsw_grad_r2_sqrt", "xsw_grad_local_sqrt", "xsw_grad_smooth", "xsw_grad_mean", "xsw_grad_filter",
     "xsw_grad_hist_masked", "xsw_grad_keep_f64", "xsw_grad_keep_u8",
     "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary",
+    "xsw_cross_from_codes",
 )
 
 
@@ -201,6 +202,8 @@ def load():
         lib.xsw_timing_read.argtypes = [ctypes.c_void_p, ctypes.POINTER(Timing)]
         lib.xsw_expand_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 4
         lib.xsw_expand_codes_on_stream.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 4
+        lib.xsw_cross_from_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 5 + [ctypes.c_void_p] * 4 + \
+            [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
         lib.xsw_host_alloc.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
         lib.xsw_host_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         lib.xsw_set_host_threads.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -430,6 +433,15 @@ class Context:
     def expand_codes_raw(self, n, mem, out_dtype, code_co, code_cr, out_co, out_cr):
         """Thin call of xsw_expand_codes (pointers are ints or None): grid codes -> the complex winds xsw_invert stores."""
         self._check(self._lib.xsw_expand_codes(self._h, int(n), mem, out_dtype, code_co, code_cr, out_co, out_cr), "xsw_expand_codes")
+
+    @_locked
+    def cross_from_codes_raw(self, lines, samples, dtype, out_dtype, mem, inc, code_co, sigma0_cr, dsig_cr, out_code_cr, out_cr,
+                             dsig_cr_scalar=0.1, sigma0_is_db=False, dual_select=False):
+        """Thin call of xsw_cross_from_codes (pointers are ints or None): the cross-pol step of a dual-pol inversion from the
+        co-pol grid codes `code_co` (None: cross-pol only) -> the cross-pol codes and / or winds the fused xsw_invert stores."""
+        self._check(self._lib.xsw_cross_from_codes(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(sigma0_is_db)),
+                                                   int(bool(dual_select)), inc, code_co, sigma0_cr, dsig_cr, float(dsig_cr_scalar),
+                                                   out_code_cr, out_cr), "xsw_cross_from_codes")
 
     def expand_codes_on_stream(self, stream, n, out_dtype, code_co, code_cr, out_co, out_cr):
         """xsw_expand_codes_on_stream: device codes -> device winds on `stream` (a HIP stream handle as an int), the context's

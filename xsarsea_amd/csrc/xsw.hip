@@ -642,6 +642,63 @@ static int expand_codes_on(xsw_ctx *c, hipStream_t stream, int64_t n, int32_t me
     return XSW_OK;
 }
 
+// ---- the cross-pol step from stored co-pol codes (xsw.h: xsw_cross_from_codes; kernel: xsw_cross.hpp)
+extern "C" int xsw_cross_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                                    int32_t sigma0_is_db, int32_t dual_select, const void *inc, const uint32_t *code_co,
+                                    const void *sigma0_cr, const void *dsig_cr, double dsig_cr_scalar, uint32_t *out_code_cr, void *out_cr)
+{
+    if (!c) return XSW_EINVAL;
+    if (lines < 0 || samples < 0) return fail(c, XSW_EINVAL, "negative raster shape");
+    if ((dtype != XSW_F32 && dtype != XSW_F64) || (out_dtype != XSW_F32 && out_dtype != XSW_F64))
+        return fail(c, XSW_EINVAL, "dtype/out_dtype must be XSW_F32 or XSW_F64");
+    if (mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE) return fail(c, XSW_EINVAL, "bad mem kind");
+    if (!inc || !sigma0_cr) return fail(c, XSW_EINVAL, "cross_from_codes: inc or sigma0_cr is NULL");
+    if (!out_code_cr && !out_cr) return fail(c, XSW_EINVAL, "cross_from_codes: neither out_code_cr nor out_cr given");
+    if (!c->have_cr) return fail(c, XSW_ENOLUT, "cross_from_codes: no cross-pol LUT uploaded");
+    if (code_co && !c->have_co) return fail(c, XSW_ENOLUT, "co-pol codes given but no co-pol LUT on this context");
+    if (lines && samples > (int64_t)(0x7fffffffLL * 256) / lines)  // (no overflow of lines * samples; one launch of 256-pixel blocks)
+        return fail(c, XSW_EINVAL, "cross_from_codes: raster too large for one launch");
+    const long long n = (long long)lines * samples;
+    if (n == 0) return XSW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    CrossArgs A{};
+    A.n = n;
+    A.dsig_cr_scalar = dsig_cr_scalar;
+    A.is_db = sigma0_is_db;
+    A.dual_select = dual_select;
+    std::string err;
+    auto launch = [&]() {
+        if (dtype == XSW_F32 && out_dtype == XSW_F32) return xsw_launch_cross_ff(c, A, c->stream, err);
+        if (dtype == XSW_F32) return xsw_launch_cross_fd(c, A, c->stream, err);
+        if (out_dtype == XSW_F32) return xsw_launch_cross_df(c, A, c->stream, err);
+        return xsw_launch_cross_dd(c, A, c->stream, err);
+    };
+    if (mem == XSW_MEM_DEVICE) {  // asynchronous on the context's stream
+        A.inc = inc; A.s_cr = sigma0_cr; A.dsig_cr = dsig_cr; A.code_co = code_co; A.code_cr = out_code_cr; A.out_cr = out_cr;
+        const int rc = launch();
+        return rc ? fail(c, rc, "%s", err.c_str()) : XSW_OK;
+    }
+    // host rasters (synchronous): upload, one kernel, download
+    CallTemps tmp(c->stream);
+    const size_t es = dtype == XSW_F32 ? 4 : 8, os = out_dtype == XSW_F32 ? 8 : 16, px = (size_t)n;
+    A.inc = tmp.alloc(px * es, inc);
+    A.s_cr = tmp.alloc(px * es, sigma0_cr);
+    if (dsig_cr) A.dsig_cr = tmp.alloc(px * es, dsig_cr);
+    if (code_co) A.code_co = (const unsigned *)tmp.alloc(px * 4, code_co);
+    if (out_code_cr) A.code_cr = (unsigned *)tmp.alloc(px * 4);
+    if (out_cr) A.out_cr = tmp.alloc(px * os);
+    if (!tmp.ok()) return tmp.refused ? fail(c, XSW_ENOMEM, "hipMalloc(%zu) failed", tmp.refused) : fail(c, XSW_EHIP, "cross_from_codes: upload failed: %s", hipGetErrorString(tmp.err));
+    int rc = launch();
+    hipError_t e = hipSuccess;
+    if (!rc && out_code_cr) e = hipMemcpyAsync(out_code_cr, A.code_cr, px * 4, hipMemcpyDeviceToHost, c->stream);
+    if (!rc && e == hipSuccess && out_cr) e = hipMemcpyAsync(out_cr, A.out_cr, px * os, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t se = tmp.finish();
+    if (rc) return fail(c, rc, "%s", err.c_str());
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) return fail(c, XSW_EHIP, "cross_from_codes failed: %s", hipGetErrorString(e));
+    return XSW_OK;
+}
+
 // ---- host-memory paths: chunks through a ring of workers (thread + stream + page-locked staging + device staging each)
 static int host_thread_count(const xsw_ctx *c)
 {

@@ -203,3 +203,21 @@ int xsw_launch_invert_ff(xsw_ctx *c, const xsw::KArgs &A, int algo, const Launch
 int xsw_launch_invert_fd(xsw_ctx *c, const xsw::KArgs &A, int algo, const LaunchCtl &lc, std::string &err);
 int xsw_launch_invert_df(xsw_ctx *c, const xsw::KArgs &A, int algo, const LaunchCtl &lc, std::string &err);
 int xsw_launch_invert_dd(xsw_ctx *c, const xsw::KArgs &A, int algo, const LaunchCtl &lc, std::string &err);
+
+// The arguments of k_cross_from_codes (xsw_cross.hpp; xsw.h: xsw_cross_from_codes) and its launches, one dtype pair per
+// translation unit next to that pair's inversion kernels.
+namespace xsw {
+struct CrossArgs {
+    const void *inc, *s_cr, *dsig_cr;  // dsig_cr nullable: dsig_cr_scalar broadcast as in load_pixel
+    const unsigned *code_co;           // nullable: every pixel XSW_CODE_NAN (cross-pol only)
+    unsigned *code_cr;                 // nullable
+    void *out_cr;                      // nullable: complex of the output dtype
+    long long n;
+    double dsig_cr_scalar;
+    int is_db, dual_select;
+};
+}  // namespace xsw
+int xsw_launch_cross_ff(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream, std::string &err);
+int xsw_launch_cross_fd(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream, std::string &err);
+int xsw_launch_cross_df(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream, std::string &err);
+int xsw_launch_cross_dd(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream, std::string &err);

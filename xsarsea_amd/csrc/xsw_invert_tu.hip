@@ -10,6 +10,7 @@
 #include "xsw_band2.hpp"
 #include "xsw_blocks.hpp"
 #include "xsw_exhaustive.hpp"
+#include "xsw_cross.hpp"
 
 using namespace xsw;
 
@@ -164,10 +165,14 @@ static int launch_invert(xsw_ctx *c, const KArgs &A_in, int algo, const LaunchCt
 #endif
 #if XSW_PAIR == 0
 int xsw_launch_invert_ff(xsw_ctx *c, const KArgs &A, int algo, const LaunchCtl &lc, std::string &err) { return launch_invert<float, float>(c, A, algo, lc, err); }
+int xsw_launch_cross_ff(xsw_ctx *c, const CrossArgs &A, hipStream_t stream, std::string &err) { return launch_cross<float, float>(c, A, stream, err); }
 #elif XSW_PAIR == 1
 int xsw_launch_invert_fd(xsw_ctx *c, const KArgs &A, int algo, const LaunchCtl &lc, std::string &err) { return launch_invert<float, double>(c, A, algo, lc, err); }
+int xsw_launch_cross_fd(xsw_ctx *c, const CrossArgs &A, hipStream_t stream, std::string &err) { return launch_cross<float, double>(c, A, stream, err); }
 #elif XSW_PAIR == 2
 int xsw_launch_invert_df(xsw_ctx *c, const KArgs &A, int algo, const LaunchCtl &lc, std::string &err) { return launch_invert<double, float>(c, A, algo, lc, err); }
+int xsw_launch_cross_df(xsw_ctx *c, const CrossArgs &A, hipStream_t stream, std::string &err) { return launch_cross<double, float>(c, A, stream, err); }
 #else
 int xsw_launch_invert_dd(xsw_ctx *c, const KArgs &A, int algo, const LaunchCtl &lc, std::string &err) { return launch_invert<double, double>(c, A, algo, lc, err); }
+int xsw_launch_cross_dd(xsw_ctx *c, const CrossArgs &A, hipStream_t stream, std::string &err) { return launch_cross<double, double>(c, A, stream, err); }
 #endif

@@ -345,27 +345,122 @@ def _device_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc, dual_select, broadc
     return plan, dev, [_device.prep(x, plan.cdtype if k == 4 else plan.dtype, plan.shape) for k, x in enumerate(t)]
 
 
-def invert_device(lut_co, lut_cr, inc, sigma0_co, sigma0_cr, dsig_cr, anc, dsig_co=0.1, dual_select=False):
+def invert_device(lut_co, lut_cr, inc, sigma0_co, sigma0_cr, dsig_cr, anc, dsig_co=0.1, dual_select=False, codes=False):
     """(ws_co, ws_cr) torch complex tensors for rasters resident in HBM (torch CUDA tensors / `__cuda_array_interface__`
     objects; host arrays among them are uploaded): the drop-in call without PCIe.  sigma0 -> dB is fused into the kernel
     (float32 rasters: float32 arithmetic like the reference, the log10 correctly rounded -- numpy's float32 log10 is a few-ulp
     SIMD routine, so ~2e-5 of the pixels of a float32 raster land one grid step from a numpy run; float64 rasters agree bit for
-    bit).  Asynchronous on torch's current stream.  dual_select: ws_cr receives the fused where(|co|<5 | |dual|<5, co, dual)."""
+    bit).  Asynchronous on torch's current stream.  dual_select: ws_cr receives the fused where(|co|<5 | |dual|<5, co, dual).
+    codes=True: the grid codes (int32 tensors holding the uint32 bit patterns) instead of the winds."""
     import torch
     from .. import _device
     plan, dev, t = _device_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc, dual_select, broadcast=torch.broadcast_shapes)
     ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
-    odt = _device.torch_dtype(plan.out_dtype)
+    odt = torch.int32 if codes else _device.torch_dtype(plan.out_dtype)
     out_co = torch.empty(plan.shape, dtype=odt, device=dev) if plan.want_co else None
     out_cr = torch.empty(plan.shape, dtype=odt, device=dev) if plan.want_cr else None
     p = _device.at
     if plan.n:
         with _device.on_current_stream(ctx, dev):
             ensure_luts(ctx, lut_co if plan.want_co else None, lut_cr if plan.want_cr else None)
-            ctx.invert_raw(plan.lines, plan.samples, plan.code, plan.out_code, _lib.MEM_DEVICE, *(p(x) for x in t), p(out_co), p(out_cr),
-                           None, dsig_co, plan.dsig_scalar, plan.is_db, plan.algo, plan.fused_select)
+            outs = (None, None, None) if codes else (p(out_co), p(out_cr), None)
+            ctx.invert_raw(plan.lines, plan.samples, plan.code, plan.out_code, _lib.MEM_DEVICE, *(p(x) for x in t), *outs,
+                           dsig_co, plan.dsig_scalar, plan.is_db, plan.algo, plan.fused_select,
+                           out_code_co=p(out_co) if codes else None, out_code_cr=p(out_cr) if codes else None)
             _device.keep_alive(t, dev)
     return out_co, out_cr
+
+
+def _code_tensor(codes):
+    """Grid codes in device memory as a torch tensor (zero copy): an int32 / uint32 tensor or any `__cuda_array_interface__` array."""
+    import torch
+    from .. import _device
+    t = _device.as_tensor(codes, _device.device_of(codes))
+    if t.dtype not in (torch.int32, torch.uint32):
+        raise TypeError(f"grid codes must be int32 or uint32, not {t.dtype}")
+    return t
+
+
+def expand_device(lut_co, codes_co):
+    """Co-pol grid codes in device memory (int32 tensor) -> the complex winds `invert_device` stores, on torch's current stream."""
+    import torch
+    from .. import _device
+    codes_co = _code_tensor(codes_co)
+    dev = codes_co.device
+    ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    out_dtype = np.complex64 if options.device_out_dtype == "complex64" else np.complex128
+    out = torch.empty(codes_co.shape, dtype=_device.torch_dtype(out_dtype), device=dev)
+    if codes_co.numel():
+        with _device.on_current_stream(ctx, dev):
+            ensure_luts(ctx, lut_co, None)
+            ctx.expand_codes_raw(codes_co.numel(), _lib.MEM_DEVICE, _lib.XSW_F32 if out_dtype == np.complex64 else _lib.XSW_F64,
+                                 codes_co.data_ptr(), None, out.data_ptr(), None)
+            _device.keep_alive([codes_co], dev)
+    return out
+
+
+def cross_plan(shape, inc, sigma0_co, anc, sigma0_cr, dsig_cr, *, device, dual_select=False):
+    """The `CallPlan` of the dual-pol call whose cross-pol step runs on its own: inc, sigma0_co, anc are the (shape, dtype) the
+    co-pol call saw, sigma0_cr / dsig_cr those of this one -- so dtype, dB route and dsig_cr handling are the fused call's.
+    ValueError when the cross-pol rasters do not broadcast to the co-pol codes' `shape`."""
+    try:
+        plan = _plan.CallPlan(inc, sigma0_co, sigma0_cr, dsig_cr, anc, device=device, dual_select=dual_select)
+    except ValueError as exc:
+        raise ValueError(f"cross-pol rasters do not broadcast against the co-pol codes of shape {tuple(shape)}: {exc}") from None
+    if plan.shape != tuple(shape):
+        raise ValueError(f"cross-pol rasters broadcast to {plan.shape}, the co-pol codes have shape {tuple(shape)}")
+    return plan
+
+
+def cross_numpy(lut_co, lut_cr, plan, codes_co, inc, sigma0_cr, dsig_cr, dual_select=False):
+    """The cross-pol grid codes (uint32) of numpy rasters from the co-pol codes `codes_co`: `invert_numpy`'s arithmetic for the
+    cross-pol inputs (a float32 sigma0 converted to dB by numpy's own log10, a scalar dsig_cr broadcast from the LINEAR
+    sigma0), then xsw_cross_from_codes on host memory."""
+    shape, dt = plan.shape, plan.dtype
+    cast = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a), shape), dtype=dt)
+    sigma0_cr = np.asarray(sigma0_cr)
+    dsig = None
+    if plan.dsig == _plan.DSIG_FILL:
+        dsig = cast(dsig_raster(sigma0_cr, plan.dsig_fill))
+    elif plan.dsig == _plan.DSIG_RASTER:
+        dsig = cast(dsig_cr)
+    s_cr = cast(_to_db(sigma0_cr) if plan.is_db else sigma0_cr)
+    full_inc, cc = cast(inc), np.ascontiguousarray(codes_co, dtype=np.uint32)
+    out = np.empty(shape, np.uint32)
+    ctx = _lib.default_context(options.device)
+    if plan.n:
+        with ctx.lock:
+            ensure_luts(ctx, lut_co, lut_cr)
+            ctx.cross_from_codes_raw(plan.lines, plan.samples, plan.code, _lib.XSW_F64, _lib.MEM_HOST, full_inc.ctypes.data, cc.ctypes.data,
+                                     s_cr.ctypes.data, None if dsig is None else dsig.ctypes.data, out.ctypes.data, None,
+                                     dsig_cr_scalar=plan.dsig_scalar, sigma0_is_db=plan.is_db, dual_select=dual_select)
+    return out
+
+
+def cross_device(lut_co, lut_cr, plan, codes_co, inc, sigma0_cr, dsig_cr, dual_select=False, codes=False):
+    """`cross_numpy` for rasters resident in HBM, following `invert_device`: the cross-pol winds (select fused with dual_select)
+    or, codes=True, the cross-pol codes as an int32 tensor; asynchronous on torch's current stream."""
+    import torch
+    from .. import _device
+    codes_co = _code_tensor(codes_co)
+    dev = codes_co.device
+    t = [_device.as_tensor(inc, dev), _device.as_tensor(sigma0_cr, dev), None if np.isscalar(dsig_cr) else _device.as_tensor(dsig_cr, dev)]
+    if plan.dsig == _plan.DSIG_FILL:
+        t[2] = dsig_raster(t[1], plan.dsig_fill)
+    if plan.db_by == _plan.DB_TORCH:
+        t[1] = _device.to_db(t[1])
+    t = [_device.prep(x, plan.dtype, plan.shape) for x in t] + [codes_co.contiguous()]
+    ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    out = torch.empty(plan.shape, dtype=torch.int32 if codes else _device.torch_dtype(plan.out_dtype), device=dev)
+    p = _device.at
+    if plan.n:
+        with _device.on_current_stream(ctx, dev):
+            ensure_luts(ctx, lut_co, lut_cr)
+            ctx.cross_from_codes_raw(plan.lines, plan.samples, plan.code, plan.out_code, _lib.MEM_DEVICE, p(t[0]), p(t[3]), p(t[1]), p(t[2]),
+                                     p(out) if codes else None, None if codes else p(out), dsig_cr_scalar=plan.dsig_scalar,
+                                     sigma0_is_db=plan.is_db, dual_select=dual_select)
+            _device.keep_alive(t, dev)
+    return out
 
 
 def _uploaded_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc):
