@@ -332,6 +332,37 @@ int xsw_detrend(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int
 int xsw_nesz_flatten(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t mem, const void *noise,
                      const void *inc, double *out);
 
+/* ---- dsig_cr from the cross-pol signal-to-noise ratio (windspeed/utils.py:47-91 get_dsig, :18-44 get_dsig_wspd).  Additive to
+ * XSW_VERSION 4.  mem is XSW_MEM_HOST or XSW_MEM_DEVICE: device calls are asynchronous on the context's stream, host calls
+ * upload, run the same kernels, download, and return with `out` filled.  XSW_EINVAL for a bad rule, dtype or mem, a NULL
+ * required pointer, or XSW_DSIG_S1_V2 without inc; an empty raster returns XSW_OK and launches nothing. */
+enum { XSW_DSIG_S1_V2 = 0,      /* gmf_s1_v2: 1 / sqrt(r ** c), c = d0 + d1 / (1 + exp(-c0 (inc - c1))) */
+       XSW_DSIG_RS2_V2 = 1,     /* gmf_rs2_v2: 1 / sqrt(r ** 8) */
+       XSW_DSIG_CMODMS1AHW = 2  /* sarwing_lut_cmodms1ahw, nc_lut_cmodms1ahw: (1.25 / r) ** 4 */ };
+enum { XSW_DSIG_WSPD_RS2_V3 = 0, XSW_DSIG_WSPD_S1_EW_REC_V3 = 1, XSW_DSIG_WSPD_RCM_V3 = 2 };
+
+/* Replaces get_dsig, elementwise: r = sigma0_cr / nesz_cr, one IEEE division in the common type of the two (`dtype`: sigma0_cr
+ * and inc; `nesz_dtype`: nesz_cr).  XSW_DSIG_S1_V2 goes on in float64 and `out` is float64; the other rules go on in the type of
+ * r, which is also `out`'s: float32 only when both rasters are.  inc is read by XSW_DSIG_S1_V2 only (NULL otherwise).  Special
+ * values as numpy's: r < 0 is NaN under S1_V2 and finite under the even powers, r == 0 gives inf, r == inf gives 0, NaN in gives
+ * NaN out.  One kernel (k_dsig). */
+int xsw_dsig(xsw_ctx *ctx, int32_t rule, int64_t lines, int64_t samples, int32_t dtype, int32_t nesz_dtype, int32_t mem,
+             const void *inc, const void *sigma0_cr, const void *nesz_cr, void *out);
+
+/* get_dsig(rule, inc, sigma0_cr, nesz_flattening(noise, inc)) without the flattened raster: the fit of xsw_nesz_flatten (same
+ * kernels, same context scratch), then one pass (k_dsig_flat) that forms each pixel's flattened noise in a register -- the bits
+ * xsw_nesz_flatten would have stored -- and applies the rule in float64.  noise, inc and sigma0_cr are `dtype` rasters, all
+ * required; out is float64 (the reference's result type) or, with out_dtype == XSW_F32, that value rounded once.  Bit-equal to
+ * xsw_nesz_flatten followed by xsw_dsig (nesz_dtype XSW_F64).  Device rasters: asynchronous on the context's stream; the scratch
+ * is context-owned, so the stream hand-over rule of xsw_nesz_flatten applies. */
+int xsw_dsig_flat(xsw_ctx *ctx, int32_t rule, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                  const void *noise, const void *inc, const void *sigma0_cr, void *out);
+
+/* Replaces get_dsig_wspd on n float64 values: clip(1 / (1 + exp(-b (U - c0 + gamma snr))) * 1 / (1 + exp((U - 30) k)), 0, 1)
+ * with the rule's (b, c0, gamma, k).  An exp that overflows gives 0 for its factor, NaN passes through the clip.  One kernel
+ * (k_dsig_wspd). */
+int xsw_dsig_wspd(xsw_ctx *ctx, int32_t rule, int64_t n, int32_t mem, const double *U, const double *snr, double *out);
+
 /* ---- wind-streak direction histograms (Koch 2004; reference: gradients.py).  Additive to XSW_VERSION 4.  Raster pointers are
  * host or device per `mem` (XSW_MEM_HOST / XSW_MEM_DEVICE); device calls are asynchronous on the context's stream, host calls
  * return with the outputs filled.  Sums are float64 in a fixed order: results are bit-identical from run to run. */

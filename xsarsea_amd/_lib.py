@@ -30,6 +30,10 @@ def algo_code(algo):
     return ALGOS.get(algo, algo)
 
 
+# get_dsig / get_dsig_wspd names -> XSW_DSIG_* / XSW_DSIG_WSPD_* (include/xsw.h)
+DSIG_RULES = {"gmf_s1_v2": 0, "gmf_rs2_v2": 1, "sarwing_lut_cmodms1ahw": 2, "nc_lut_cmodms1ahw": 2}
+DSIG_WSPD_RULES = {"dsig_wspd_rs2_v3": 0, "dsig_wspd_s1_ew_rec_v3": 1, "dsig_wspd_rcm_v3": 2}
+
 GMF_IDS = {"gmf_cmod5": 0, "gmf_cmod5n": 1, "gmf_cmod5n_pr_zhangA": 2, "gmf_cmod5n_pr_mouche1": 3, "gmf_cmodifr2": 4,
            "gmf_rs2_v2": 5, "gmf_s1_v2": 6, "gmf_rcm_noaa": 7, "gmf_s1_v3_ew_rec": 8, "gmf_rs2_v3": 9, "gmf_rcm_v3": 10,
            "gmf_rcm_v4": 11, "gmf_rs2_v4": 12}
@@ -43,6 +47,7 @@ EXPORTS = (
     "xsw_grad_hist_masked", "xsw_grad_keep_f64", "xsw_grad_keep_u8",
     "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary",
     "xsw_cross_from_codes",
+    "xsw_dsig", "xsw_dsig_flat", "xsw_dsig_wspd",
 )
 
 
@@ -204,6 +209,9 @@ def load():
         lib.xsw_expand_codes_on_stream.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 4
         lib.xsw_cross_from_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 5 + [ctypes.c_void_p] * 4 + \
             [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
+        lib.xsw_dsig.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
+        lib.xsw_dsig_flat.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
+        lib.xsw_dsig_wspd.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 3
         lib.xsw_host_alloc.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
         lib.xsw_host_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         lib.xsw_set_host_threads.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -564,6 +572,23 @@ class Context:
         """Thin call of xsw_nesz_flatten (pointers are ints: device or host addresses)."""
         self._check(self._lib.xsw_nesz_flatten(self._h, int(lines), int(samples), dtype, mem, ctypes.c_void_p(noise_ptr),
                                                ctypes.c_void_p(inc_ptr), ctypes.c_void_p(out_ptr)), "xsw_nesz_flatten")
+
+    @_locked
+    def dsig_raw(self, rule, lines, samples, dtype, nesz_dtype, mem, inc_ptr, sigma0_ptr, nesz_ptr, out_ptr):
+        """Thin call of xsw_dsig (pointers are ints: device or host addresses; inc_ptr None unless the rule is S1_V2)."""
+        self._check(self._lib.xsw_dsig(self._h, int(rule), int(lines), int(samples), dtype, nesz_dtype, mem, _ptr(inc_ptr), _ptr(sigma0_ptr),
+                                       _ptr(nesz_ptr), _ptr(out_ptr)), "xsw_dsig")
+
+    @_locked
+    def dsig_flat_raw(self, rule, lines, samples, dtype, out_dtype, mem, noise_ptr, inc_ptr, sigma0_ptr, out_ptr):
+        """Thin call of xsw_dsig_flat (pointers are ints: device or host addresses)."""
+        self._check(self._lib.xsw_dsig_flat(self._h, int(rule), int(lines), int(samples), dtype, out_dtype, mem, _ptr(noise_ptr), _ptr(inc_ptr),
+                                            _ptr(sigma0_ptr), _ptr(out_ptr)), "xsw_dsig_flat")
+
+    @_locked
+    def dsig_wspd_raw(self, rule, n, mem, u_ptr, snr_ptr, out_ptr):
+        """Thin call of xsw_dsig_wspd (float64 values; pointers are ints: device or host addresses)."""
+        self._check(self._lib.xsw_dsig_wspd(self._h, int(rule), int(n), mem, _ptr(u_ptr), _ptr(snr_ptr), _ptr(out_ptr)), "xsw_dsig_wspd")
 
     @_locked
     def nesz_flatten_host(self, noise, inc):

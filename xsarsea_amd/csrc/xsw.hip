@@ -19,6 +19,7 @@
 #include "xsw_misc.hpp"
 #include "xsw_gmf.hpp"
 #include "xsw_nesz.hpp"
+#include "xsw_dsig.hpp"
 #include "xsw_lutbuild.hpp"
 
 using namespace xsw;
@@ -1171,23 +1172,42 @@ extern "C" int xsw_detrend(xsw_ctx *c, int64_t lines, int64_t samples, int32_t d
 }
 
 // ---------------------------------------------------------------------------------------- cross-pol noise flattening
+// The context scratch of one raster: [column partials | noise_mean, inc_row | x0 (+ pad) | fit[lines][2]] (nesz_blocks sizes it)
+struct NeszScratch {
+    NeszPartial *part;
+    double *col, *x0, *fit;
+    NeszScratch(void *scratch, long long samples, int nb)
+        : part((NeszPartial *)scratch), col((double *)((char *)scratch + (size_t)nb * samples * sizeof(NeszPartial))),
+          x0(col + 2 * samples), fit(x0 + 8) {}
+};
+
+// The fit half, shared by xsw_nesz_flatten and xsw_dsig_flat: column means, centring abscissa, (slope, icpt) of every line
+template <typename T>
+static void launch_nesz_fit(hipStream_t s, const void *noise, const void *inc, const NeszScratch &k, long long lines, long long samples,
+                            int nb, long long lpb)
+{
+    const unsigned gx = (unsigned)((samples + 255) / 256);
+    hipLaunchKernelGGL((k_nesz_colsum<T, 1>), dim3(gx, (unsigned)nb), dim3(256), 0, s, (const T *)noise, (const T *)inc, k.part, lines, samples, lpb);
+    hipLaunchKernelGGL(k_nesz_colmean, dim3(gx), dim3(256), 0, s, k.part, k.col, samples, nb);
+    hipLaunchKernelGGL(k_nesz_center, dim3(1), dim3(1024), 0, s, k.col, k.x0, samples);
+    hipLaunchKernelGGL((k_nesz_fit<T>), dim3((unsigned)((lines + XSW_NESZ_LINES - 1) / XSW_NESZ_LINES)), dim3(XSW_NESZ_THREADS), 0, s, (const T *)noise, k.col,
+                       k.x0, k.fit, lines, samples);
+}
+
+// The grid of the passes that evaluate the fit (k_nesz_eval, k_dsig_flat): column groups x line blocks, ~16 workgroups per CU
+static Strips nesz_eval_grid(long long lines, long long samples)
+{
+    return strip_grid(lines, (samples + XSW_NESZ_EV - 1) / XSW_NESZ_EV);  // columns: groups of XSW_NESZ_EV samples
+}
+
 template <typename T>
 static hipError_t launch_nesz(hipStream_t s, const void *noise, const void *inc, void *scratch, double *out, long long lines,
                               long long samples, int nb, long long lpb)
 {
-    NeszPartial *part = (NeszPartial *)scratch;
-    double *col = (double *)((char *)scratch + (size_t)nb * samples * sizeof(NeszPartial));
-    double *x0 = col + 2 * samples;
-    double *fit = x0 + 8;  // [lines][2]
-    const unsigned gx = (unsigned)((samples + 255) / 256);
-    hipLaunchKernelGGL((k_nesz_colsum<T, 1>), dim3(gx, (unsigned)nb), dim3(256), 0, s, (const T *)noise, (const T *)inc, part, lines, samples, lpb);
-    hipLaunchKernelGGL(k_nesz_colmean, dim3(gx), dim3(256), 0, s, part, col, samples, nb);
-    hipLaunchKernelGGL(k_nesz_center, dim3(1), dim3(1024), 0, s, col, x0, samples);
-    hipLaunchKernelGGL((k_nesz_fit<T>), dim3((unsigned)((lines + XSW_NESZ_LINES - 1) / XSW_NESZ_LINES)), dim3(XSW_NESZ_THREADS), 0, s, (const T *)noise, col,
-                       x0, fit, lines, samples);
-    // the write pass: column groups x line blocks, ~16 workgroups per CU
-    const Strips e = strip_grid(lines, (samples + XSW_NESZ_EV - 1) / XSW_NESZ_EV);  // columns: groups of XSW_NESZ_EV samples
-    hipLaunchKernelGGL((k_nesz_eval<sizeof(T) == 4>), dim3((unsigned)e.gx, (unsigned)e.gy), dim3(256), 0, s, col, fit, out, lines, samples, e.rows_per_block);
+    const NeszScratch k(scratch, samples, nb);
+    launch_nesz_fit<T>(s, noise, inc, k, lines, samples, nb, lpb);
+    const Strips e = nesz_eval_grid(lines, samples);  // the write pass
+    hipLaunchKernelGGL((k_nesz_eval<sizeof(T) == 4>), dim3((unsigned)e.gx, (unsigned)e.gy), dim3(256), 0, s, k.col, k.fit, out, lines, samples, e.rows_per_block);
     return hipGetLastError();
 }
 
@@ -1258,4 +1278,148 @@ extern "C" int xsw_nesz_flatten(xsw_ctx *c, int64_t lines, int64_t samples, int3
     trim_staging(c);
     if (c->arena_cap > XSW_ARENA_KEEP) (void)grow(c->arena, c->arena_cap, 0);  // do not sit on a huge staging area
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------- dsig_cr
+#define XSW_DSIG_RULES(rule, CALL)                                       \
+    do {                                                                 \
+        if ((rule) == XSW_DSIG_S1_V2) { CALL(XSW_DSIG_S1_V2); }          \
+        else if ((rule) == XSW_DSIG_RS2_V2) { CALL(XSW_DSIG_RS2_V2); }   \
+        else { CALL(XSW_DSIG_CMODMS1AHW); }                              \
+    } while (0)
+
+template <typename T, typename TN>
+static hipError_t launch_dsig(hipStream_t s, int rule, const void *inc, const void *sigma0, const void *nesz, void *out, long long n)
+{
+    const unsigned blocks = (unsigned)((n + 256LL * XSW_DSIG_V - 1) / (256LL * XSW_DSIG_V));
+#define XSW_CALL(R) hipLaunchKernelGGL((k_dsig<T, TN, R>), dim3(blocks), dim3(256), 0, s, (const T *)sigma0, (const TN *)nesz, (const T *)inc, \
+                                       (typename DsigOut<T, TN, R>::type *)out, n)
+    XSW_DSIG_RULES(rule, XSW_CALL);
+#undef XSW_CALL
+    return hipGetLastError();
+}
+
+static bool dsig_dtype_ok(int32_t dt) { return dt == XSW_F32 || dt == XSW_F64; }
+static bool dsig_rule_ok(int32_t rule) { return rule >= XSW_DSIG_S1_V2 && rule <= XSW_DSIG_CMODMS1AHW; }
+
+extern "C" int xsw_dsig(xsw_ctx *c, int32_t rule, int64_t lines, int64_t samples, int32_t dtype, int32_t nesz_dtype, int32_t mem,
+                        const void *inc, const void *sigma0_cr, const void *nesz_cr, void *out)
+{
+    if (!c) return XSW_EINVAL;
+    if (!dsig_rule_ok(rule)) return fail(c, XSW_EINVAL, "dsig: unknown rule %d", (int)rule);
+    if (!dsig_dtype_ok(dtype) || !dsig_dtype_ok(nesz_dtype)) return fail(c, XSW_EINVAL, "dsig: dtype must be XSW_F32 or XSW_F64");
+    if (mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE) return fail(c, XSW_EINVAL, "dsig: bad mem kind");
+    if (lines < 0 || samples < 0 || !sigma0_cr || !nesz_cr || !out) return fail(c, XSW_EINVAL, "dsig: bad argument");
+    if (rule == XSW_DSIG_S1_V2 && !inc) return fail(c, XSW_EINVAL, "dsig: XSW_DSIG_S1_V2 needs inc");
+    if (samples && lines > (int64_t)(0x7fffffffLL * 256 * XSW_DSIG_V) / samples) return fail(c, XSW_EINVAL, "raster too large for one launch");
+    const long long n = (long long)lines * samples;
+    if (n == 0) return XSW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (rule != XSW_DSIG_S1_V2) inc = nullptr;
+    const size_t es = dtype == XSW_F32 ? 4 : 8, ns = nesz_dtype == XSW_F32 ? 4 : 8;
+    const size_t os = (rule != XSW_DSIG_S1_V2 && es == 4 && ns == 4) ? 4 : 8;
+    auto launch = [&](const void *di, const void *ds, const void *dn, void *dout) {
+        if (es == 4) return ns == 4 ? launch_dsig<float, float>(c->stream, rule, di, ds, dn, dout, n) : launch_dsig<float, double>(c->stream, rule, di, ds, dn, dout, n);
+        return ns == 4 ? launch_dsig<double, float>(c->stream, rule, di, ds, dn, dout, n) : launch_dsig<double, double>(c->stream, rule, di, ds, dn, dout, n);
+    };
+    hipError_t e;
+    if (mem == XSW_MEM_HOST) {
+        CallTemps tmp(c->stream);
+        const void *d_s = tmp.alloc((size_t)n * es, sigma0_cr), *d_n = tmp.alloc((size_t)n * ns, nesz_cr);
+        const void *d_i = inc ? tmp.alloc((size_t)n * es, inc) : nullptr;
+        void *d_out = tmp.alloc((size_t)n * os);
+        e = tmp.err;
+        if (e == hipSuccess) e = launch(d_i, d_s, d_n, d_out);
+        if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * os, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t se = tmp.finish();
+        if (e == hipSuccess) e = se;
+    } else e = launch(inc, sigma0_cr, nesz_cr, out);
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? XSW_ENOMEM : XSW_EHIP, "dsig failed: %s", hipGetErrorString(e));
+    return XSW_OK;
+}
+
+template <typename T, typename TO>
+static hipError_t launch_dsig_flat(hipStream_t s, int rule, const void *noise, const void *inc, const void *sigma0, void *scratch, void *out,
+                                   long long lines, long long samples, int nb, long long lpb)
+{
+    const NeszScratch k(scratch, samples, nb);
+    launch_nesz_fit<T>(s, noise, inc, k, lines, samples, nb, lpb);
+    const Strips e = nesz_eval_grid(lines, samples);
+#define XSW_CALL(R) hipLaunchKernelGGL((k_dsig_flat<T, TO, R>), dim3((unsigned)e.gx, (unsigned)e.gy), dim3(256), 0, s, k.col, k.fit, (const T *)sigma0, \
+                                       (const T *)inc, (TO *)out, lines, samples, e.rows_per_block)
+    XSW_DSIG_RULES(rule, XSW_CALL);
+#undef XSW_CALL
+    return hipGetLastError();
+}
+
+extern "C" int xsw_dsig_flat(xsw_ctx *c, int32_t rule, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                             const void *noise, const void *inc, const void *sigma0_cr, void *out)
+{
+    if (!c) return XSW_EINVAL;
+    if (!dsig_rule_ok(rule)) return fail(c, XSW_EINVAL, "dsig_flat: unknown rule %d", (int)rule);
+    if (!dsig_dtype_ok(dtype) || !dsig_dtype_ok(out_dtype)) return fail(c, XSW_EINVAL, "dsig_flat: dtype must be XSW_F32 or XSW_F64");
+    if (mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE) return fail(c, XSW_EINVAL, "dsig_flat: bad mem kind");
+    if (lines < 0 || samples < 0 || !noise || !inc || !sigma0_cr || !out) return fail(c, XSW_EINVAL, "dsig_flat: bad argument");
+    if (lines > 0x7fffffffLL) return fail(c, XSW_EINVAL, "raster too large for one launch");
+    const long long n = (long long)lines * samples;
+    if (n == 0) return XSW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t es = dtype == XSW_F32 ? 4 : 8, os = out_dtype == XSW_F32 ? 4 : 8;
+    const NeszBlocks nbk = nesz_blocks(lines, samples, sizeof(NeszPartial));
+    if (nbk.scratch_bytes > c->nesz_cap)  // (synchronised first: a previous call may still be using the old scratch)
+        HIPCHK(c, grow(c->nesz_scratch, c->nesz_cap, nbk.scratch_bytes, &c->stream));
+    auto launch = [&](const void *dn, const void *di, const void *ds, void *dout) {
+#define XSW_CALL(T, TO) launch_dsig_flat<T, TO>(c->stream, rule, dn, di, ds, c->nesz_scratch, dout, lines, samples, (int)nbk.nb, nbk.lpb)
+        if (es == 4) return os == 4 ? XSW_CALL(float, float) : XSW_CALL(float, double);
+        return os == 4 ? XSW_CALL(double, float) : XSW_CALL(double, double);
+#undef XSW_CALL
+    };
+    hipError_t e;
+    if (mem == XSW_MEM_HOST) {
+        CallTemps tmp(c->stream);
+        const void *d_n = tmp.alloc((size_t)n * es, noise), *d_i = tmp.alloc((size_t)n * es, inc), *d_s = tmp.alloc((size_t)n * es, sigma0_cr);
+        void *d_out = tmp.alloc((size_t)n * os);
+        e = tmp.err;
+        if (e == hipSuccess) e = launch(d_n, d_i, d_s, d_out);
+        if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * os, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t se = tmp.finish();
+        if (e == hipSuccess) e = se;
+    } else e = launch(noise, inc, sigma0_cr, out);
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? XSW_ENOMEM : XSW_EHIP, "dsig_flat failed: %s", hipGetErrorString(e));
+    return XSW_OK;
+}
+
+extern "C" int xsw_dsig_wspd(xsw_ctx *c, int32_t rule, int64_t n, int32_t mem, const double *U, const double *snr, double *out)
+{
+    // (b, c0, gamma, k) of windspeed/utils.py:27-42
+    static const DsigWspdCoef coef[3] = {
+        {-0.4908643753212401, 16.763199934792965, 1.3891445172991084, 20.616914824394343},
+        {-0.5858970325653666, 16.50039320910609, 1.1032031322520397, 7.434663633997121},
+        {-0.7920301376936547, 15.8288289109038, 0.24040294696606557, 0.2538177092195224},
+    };
+    if (!c) return XSW_EINVAL;
+    if (rule < XSW_DSIG_WSPD_RS2_V3 || rule > XSW_DSIG_WSPD_RCM_V3) return fail(c, XSW_EINVAL, "dsig_wspd: unknown rule %d", (int)rule);
+    if (mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE) return fail(c, XSW_EINVAL, "dsig_wspd: bad mem kind");
+    if (n < 0 || !U || !snr || !out) return fail(c, XSW_EINVAL, "dsig_wspd: bad argument");
+    if (n == 0) return XSW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto launch = [&](const double *d_u, const double *d_snr, double *d_out) {
+        const long long blocks = std::min<long long>((n + 255) / 256, 256 * 16);
+        hipLaunchKernelGGL(k_dsig_wspd, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_u, d_snr, d_out, (long long)n, coef[rule]);
+        return hipGetLastError();
+    };
+    hipError_t e;
+    if (mem == XSW_MEM_HOST) {
+        CallTemps tmp(c->stream);
+        const size_t bytes = (size_t)n * 8;
+        const double *d_u = (const double *)tmp.alloc(bytes, U), *d_snr = (const double *)tmp.alloc(bytes, snr);
+        double *d_out = (double *)tmp.alloc(bytes);
+        e = tmp.err;
+        if (e == hipSuccess) e = launch(d_u, d_snr, d_out);
+        if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t se = tmp.finish();
+        if (e == hipSuccess) e = se;
+    } else e = launch(U, snr, out);
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? XSW_ENOMEM : XSW_EHIP, "dsig_wspd failed: %s", hipGetErrorString(e));
+    return XSW_OK;
 }
