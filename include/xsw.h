@@ -232,6 +232,50 @@ int xsw_cross_from_codes(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t d
                          int32_t sigma0_is_db, int32_t dual_select, const void *inc, const uint32_t *code_co,
                          const void *sigma0_cr, const void *dsig_cr, double dsig_cr_scalar, uint32_t *out_code_cr, void *out_cr);
 
+/* Additive to XSW_VERSION 4.  The VALUE of the minimum the co-pol search found, from its stored codes: J_co = Jwind_co + Jsig_co
+ * of windspeed.py:216-225 at the grid point (i_wspd, i_phi) the code names -- the reference takes the arg-min of J and drops
+ * J -- with its two terms and the forward-model residual, one pass over the rasters and ONE LUT entry gathered per pixel:
+ *   out_J        Jwind + Jsig: bit for bit the minimum of the reference's dense J_co array (float64 arithmetic in its order)
+ *   out_Jsig     ((lut_db - sigma0_db) / dsig_co)^2: large where the grid point does not reproduce the observation
+ *   out_Jwind    ((w cos(phi) - Re anc) / 2)^2 + ((w sin(phi) - Im anc) / 2)^2, |Im anc| for a 0..180 LUT (:218-219): large where
+ *                the retrieval was pulled far from the a-priori wind
+ *   out_residual lut_db - sigma0_db, in dB
+ * Each output is a `lines x samples` real raster of out_dtype (XSW_F32: the float64 value rounded once) or NULL: a NULL output
+ * is not computed and never written; at least one must be given.  inc, sigma0_co (converted to dB as xsw_invert does,
+ * sigma0_is_db as there) and anc (complex of `dtype`) are the rasters the codes were computed from, dsig_co that call's.
+ * NaN in all outputs: a pixel whose code is XSW_CODE_NAN, XSW_CODE_NAN_RE or no code of the context's CURRENT co-pol LUT (bit 31
+ * set, or an index at or beyond n_wspd * n_phi: no table is read), or whose incidence is NaN.  Bit 30 (the -phi solution) does
+ * not enter the cost.  A NaN sigma0 or ancillary wind next to a grid code gives NaN by the arithmetic.
+ * Bytes per pixel, float32 rasters: 20 read (code, incidence, sigma0, ancillary wind; 12 without out_J / out_Jwind), one 8-byte
+ * LUT entry gathered, 4 or 8 written per output.
+ * XSW_EINVAL, before any launch, with a message in xsw_last_error: no output requested, no co-pol LUT installed, dsig_co NaN or
+ * 0, a NULL input, a bad dtype or mem, a raster too large for one launch (more than 0x7fffffff * 256 pixels).
+ * XSW_MEM_DEVICE: one kernel (k_cost_co), asynchronous on the context's stream; XSW_MEM_HOST: upload, kernel, download,
+ * returns with the outputs filled. */
+int xsw_cost_from_codes(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                        int32_t sigma0_is_db, const void *inc, const uint32_t *code_co, const void *sigma0_co, const void *anc,
+                        double dsig_co, void *out_J, void *out_Jsig, void *out_Jwind, void *out_residual);
+
+/* Additive to XSW_VERSION 4.  The same for the cross-pol search (windspeed.py:254-264), from the cross-pol codes xsw_invert or
+ * xsw_cross_from_codes wrote (with or without dual_select: XSW_CODE_PICK_CO is ignored, the cost is the cross-pol search's
+ * whichever wind the select returned):
+ *   out_Jsig     ((lut_cr_db - sigma0_cr_db) / dsig_cr)^2 at i_wspd_cr = the code's index; dsig_cr a `dtype` raster, or NULL:
+ *                dsig_cr_scalar broadcast as sigma0_cr * 0 + dsig_cr in `dtype` (:122-123)
+ *   out_Jwind    ((wspd_cr - |wind_co|) / 2)^2 where the co-pol code names a grid point of the context's co-pol LUT, else NaN
+ *   out_J        Jsig + Jwind, or Jsig alone without a co-pol wind (:259-264): the minimum of the reference's dense J_cr
+ *   out_residual lut_cr_db - sigma0_cr_db
+ *   code_co      the co-pol codes of these pixels, or NULL: every pixel XSW_CODE_NAN (cross-pol-only inversion)
+ * NaN in all outputs: a pixel no cross-pol search ran for (code_cr XSW_CODE_NAN_RE, index XSW_CODE_NO_INDEX, an index at or
+ * beyond n_wspd_cr: no table is read) or whose incidence is NaN.  Outputs, out_dtype and mem as in xsw_cost_from_codes.
+ * Bytes per pixel, float32 rasters: 16 read (two codes, incidence, sigma0_cr; + 4 with a dsig_cr raster), one 8-byte LUT entry
+ * gathered, 4 or 8 written per output.
+ * XSW_EINVAL, before any launch: no output requested, no cross-pol LUT installed, code_co given and no co-pol LUT installed, a
+ * NULL inc / code_cr / sigma0_cr, a bad dtype or mem, a raster too large for one launch.  One kernel (k_cost_cr). */
+int xsw_cost_cr_from_codes(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                           int32_t sigma0_is_db, const void *inc, const uint32_t *code_co, const uint32_t *code_cr,
+                           const void *sigma0_cr, const void *dsig_cr, double dsig_cr_scalar, void *out_J, void *out_Jsig,
+                           void *out_Jwind, void *out_residual);
+
 /* Page-locked host memory for rasters a caller fills itself (XSW_MEM_HOST_PINNED); freed by xsw_host_free or with the context. */
 int xsw_host_alloc(xsw_ctx *ctx, size_t bytes, void **out);
 int xsw_host_free(xsw_ctx *ctx, void *p);

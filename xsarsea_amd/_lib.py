@@ -46,7 +46,7 @@ EXPORTS = (
     "xsw_grad_r2_sqrt", "xsw_grad_local_sqrt", "xsw_grad_smooth", "xsw_grad_mean", "xsw_grad_filter",
     "xsw_grad_hist_masked", "xsw_grad_keep_f64", "xsw_grad_keep_u8",
     "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary",
-    "xsw_cross_from_codes",
+    "xsw_cross_from_codes", "xsw_cost_from_codes", "xsw_cost_cr_from_codes",
     "xsw_dsig", "xsw_dsig_flat", "xsw_dsig_wspd",
 )
 
@@ -209,6 +209,10 @@ def load():
         lib.xsw_expand_codes_on_stream.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 4
         lib.xsw_cross_from_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 5 + [ctypes.c_void_p] * 4 + \
             [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
+        lib.xsw_cost_from_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 4 + \
+            [ctypes.c_double] + [ctypes.c_void_p] * 4
+        lib.xsw_cost_cr_from_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 5 + \
+            [ctypes.c_double] + [ctypes.c_void_p] * 4
         lib.xsw_dsig.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_dsig_flat.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_dsig_wspd.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 3
@@ -450,6 +454,23 @@ class Context:
         self._check(self._lib.xsw_cross_from_codes(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(sigma0_is_db)),
                                                    int(bool(dual_select)), inc, code_co, sigma0_cr, dsig_cr, float(dsig_cr_scalar),
                                                    out_code_cr, out_cr), "xsw_cross_from_codes")
+
+    @_locked
+    def cost_from_codes_raw(self, lines, samples, dtype, out_dtype, mem, inc, code_co, sigma0_co, anc, out_J, out_Jsig=None, out_Jwind=None,
+                            out_residual=None, dsig_co=0.1, sigma0_is_db=False):
+        """Thin call of xsw_cost_from_codes (pointers are ints or None): J_co = Jwind + Jsig at the grid point of every co-pol code,
+        its two terms and lut_db - sigma0_db, each into a real raster of `out_dtype` (None: not computed)."""
+        self._check(self._lib.xsw_cost_from_codes(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(sigma0_is_db)), inc, code_co,
+                                                  sigma0_co, anc, float(dsig_co), out_J, out_Jsig, out_Jwind, out_residual), "xsw_cost_from_codes")
+
+    @_locked
+    def cost_cr_from_codes_raw(self, lines, samples, dtype, out_dtype, mem, inc, code_co, code_cr, sigma0_cr, dsig_cr, out_J, out_Jsig=None,
+                               out_Jwind=None, out_residual=None, dsig_cr_scalar=0.1, sigma0_is_db=False):
+        """Thin call of xsw_cost_cr_from_codes: the same for the cross-pol codes `code_cr` (code_co None: cross-pol only; dsig_cr
+        None: the scalar broadcast)."""
+        self._check(self._lib.xsw_cost_cr_from_codes(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(sigma0_is_db)), inc, code_co,
+                                                     code_cr, sigma0_cr, dsig_cr, float(dsig_cr_scalar), out_J, out_Jsig, out_Jwind, out_residual),
+                    "xsw_cost_cr_from_codes")
 
     def expand_codes_on_stream(self, stream, n, out_dtype, code_co, code_cr, out_co, out_cr):
         """xsw_expand_codes_on_stream: device codes -> device winds on `stream` (a HIP stream handle as an int), the context's

@@ -700,6 +700,86 @@ extern "C" int xsw_cross_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, 
     return XSW_OK;
 }
 
+// ---- inversion cost and sigma0 residual from stored codes (xsw.h: xsw_cost_from_codes, xsw_cost_cr_from_codes; kernels: xsw_cost.hpp)
+// One body for the two entries: A holds the caller's pointers (cr: the cross-pol entry); every check comes before any launch.
+static int cost_from_codes(xsw_ctx *c, const char *who, bool cr, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype,
+                           int32_t mem, CostArgs A)
+{
+    if (lines < 0 || samples < 0) return fail(c, XSW_EINVAL, "negative raster shape");
+    if ((dtype != XSW_F32 && dtype != XSW_F64) || (out_dtype != XSW_F32 && out_dtype != XSW_F64))
+        return fail(c, XSW_EINVAL, "dtype/out_dtype must be XSW_F32 or XSW_F64");
+    if (mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE) return fail(c, XSW_EINVAL, "bad mem kind");
+    if (!A.inc || !A.s || (cr ? !A.code_cr : (!A.code_co || !A.anc))) return fail(c, XSW_EINVAL, "%s: an input raster is NULL", who);
+    if (!A.out_J && !A.out_Jsig && !A.out_Jwind && !A.out_res) return fail(c, XSW_EINVAL, "%s: no output requested", who);
+    if (cr ? !c->have_cr : !c->have_co) return fail(c, XSW_EINVAL, "%s: no %s LUT installed", who, cr ? "cross-pol" : "co-pol");
+    if (cr && A.code_co && !c->have_co) return fail(c, XSW_EINVAL, "%s: co-pol codes given but no co-pol LUT installed", who);
+    if (!cr && (A.dsig_co != A.dsig_co || A.dsig_co == 0.0)) return fail(c, XSW_EINVAL, "%s: dsig_co is NaN or 0", who);
+    if (lines && samples > (int64_t)(0x7fffffffLL * 256) / lines)  // (no overflow of lines * samples; one launch of 256-pixel blocks)
+        return fail(c, XSW_EINVAL, "%s: raster too large for one launch", who);
+    A.n = (long long)lines * samples;
+    if (A.n == 0) return XSW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::string err;
+    auto launch = [&]() {
+        if (dtype == XSW_F32 && out_dtype == XSW_F32) return xsw_launch_cost_ff(c, A, cr, c->stream, err);
+        if (dtype == XSW_F32) return xsw_launch_cost_fd(c, A, cr, c->stream, err);
+        if (out_dtype == XSW_F32) return xsw_launch_cost_df(c, A, cr, c->stream, err);
+        return xsw_launch_cost_dd(c, A, cr, c->stream, err);
+    };
+    if (mem == XSW_MEM_DEVICE) {  // asynchronous on the context's stream
+        const int rc = launch();
+        return rc ? fail(c, rc, "%s", err.c_str()) : XSW_OK;
+    }
+    // host rasters (synchronous): upload, one kernel, download
+    CallTemps tmp(c->stream);
+    const size_t es = dtype == XSW_F32 ? 4 : 8, os = out_dtype == XSW_F32 ? 4 : 8, px = (size_t)A.n;
+    void *host_out[4] = {A.out_J, A.out_Jsig, A.out_Jwind, A.out_res};
+    void **dev_out[4] = {&A.out_J, &A.out_Jsig, &A.out_Jwind, &A.out_res};
+    A.inc = tmp.alloc(px * es, A.inc);
+    A.s = tmp.alloc(px * es, A.s);
+    if (A.anc) A.anc = tmp.alloc(px * es * 2, A.anc);
+    if (A.dsig_cr) A.dsig_cr = tmp.alloc(px * es, A.dsig_cr);
+    if (A.code_co) A.code_co = (const unsigned *)tmp.alloc(px * 4, A.code_co);
+    if (A.code_cr) A.code_cr = (const unsigned *)tmp.alloc(px * 4, A.code_cr);
+    for (int k = 0; k < 4; ++k)
+        if (host_out[k]) *dev_out[k] = tmp.alloc(px * os);
+    if (!tmp.ok()) return tmp.refused ? fail(c, XSW_ENOMEM, "hipMalloc(%zu) failed", tmp.refused) : fail(c, XSW_EHIP, "%s: upload failed: %s", who, hipGetErrorString(tmp.err));
+    const int rc = launch();
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 4 && !rc && e == hipSuccess; ++k)
+        if (host_out[k]) e = hipMemcpyAsync(host_out[k], *dev_out[k], px * os, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t se = tmp.finish();
+    if (rc) return fail(c, rc, "%s", err.c_str());
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) return fail(c, XSW_EHIP, "%s failed: %s", who, hipGetErrorString(e));
+    return XSW_OK;
+}
+
+extern "C" int xsw_cost_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                                   int32_t sigma0_is_db, const void *inc, const uint32_t *code_co, const void *sigma0_co, const void *anc,
+                                   double dsig_co, void *out_J, void *out_Jsig, void *out_Jwind, void *out_residual)
+{
+    if (!c) return XSW_EINVAL;
+    CostArgs A{};
+    A.inc = inc; A.s = sigma0_co; A.anc = anc; A.code_co = code_co;
+    A.out_J = out_J; A.out_Jsig = out_Jsig; A.out_Jwind = out_Jwind; A.out_res = out_residual;
+    A.dsig_co = dsig_co; A.is_db = sigma0_is_db;
+    return cost_from_codes(c, "cost_from_codes", false, lines, samples, dtype, out_dtype, mem, A);
+}
+
+extern "C" int xsw_cost_cr_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                                      int32_t sigma0_is_db, const void *inc, const uint32_t *code_co, const uint32_t *code_cr,
+                                      const void *sigma0_cr, const void *dsig_cr, double dsig_cr_scalar, void *out_J, void *out_Jsig,
+                                      void *out_Jwind, void *out_residual)
+{
+    if (!c) return XSW_EINVAL;
+    CostArgs A{};
+    A.inc = inc; A.s = sigma0_cr; A.dsig_cr = dsig_cr; A.code_co = code_co; A.code_cr = code_cr;
+    A.out_J = out_J; A.out_Jsig = out_Jsig; A.out_Jwind = out_Jwind; A.out_res = out_residual;
+    A.dsig_cr_scalar = dsig_cr_scalar; A.is_db = sigma0_is_db;
+    return cost_from_codes(c, "cost_cr_from_codes", true, lines, samples, dtype, out_dtype, mem, A);
+}
+
 // ---- host-memory paths: chunks through a ring of workers (thread + stream + page-locked staging + device staging each)
 static int host_thread_count(const xsw_ctx *c)
 {

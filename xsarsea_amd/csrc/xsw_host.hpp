@@ -221,3 +221,20 @@ int xsw_launch_cross_ff(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream,
 int xsw_launch_cross_fd(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream, std::string &err);
 int xsw_launch_cross_df(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream, std::string &err);
 int xsw_launch_cross_dd(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream, std::string &err);
+
+// The arguments of k_cost_co / k_cost_cr (xsw_cost.hpp; xsw.h: xsw_cost_from_codes, xsw_cost_cr_from_codes) and their launches,
+// next to k_cross_from_codes in each dtype pair's translation unit.
+namespace xsw {
+struct CostArgs {
+    const void *inc, *s, *anc, *dsig_cr;  // s: sigma0_co (k_cost_co, with anc) or sigma0_cr (k_cost_cr, with the nullable dsig_cr)
+    const unsigned *code_co, *code_cr;    // k_cost_cr: code_co nullable (every pixel XSW_CODE_NAN)
+    void *out_J, *out_Jsig, *out_Jwind, *out_res;  // each nullable: reals of the output dtype
+    long long n;
+    double dsig_co, dsig_cr_scalar;
+    int is_db;
+};
+}  // namespace xsw
+int xsw_launch_cost_ff(xsw_ctx *c, const xsw::CostArgs &A, bool cr, hipStream_t stream, std::string &err);
+int xsw_launch_cost_fd(xsw_ctx *c, const xsw::CostArgs &A, bool cr, hipStream_t stream, std::string &err);
+int xsw_launch_cost_df(xsw_ctx *c, const xsw::CostArgs &A, bool cr, hipStream_t stream, std::string &err);
+int xsw_launch_cost_dd(xsw_ctx *c, const xsw::CostArgs &A, bool cr, hipStream_t stream, std::string &err);

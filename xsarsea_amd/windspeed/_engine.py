@@ -463,6 +463,106 @@ def cross_device(lut_co, lut_cr, plan, codes_co, inc, sigma0_cr, dsig_cr, dual_s
     return out
 
 
+def _cost_outputs(parts, empty):
+    """[J, Jsig, Jwind, residual] rasters from `empty()`; parts=False: J alone, the others None (not computed)."""
+    return [empty() if (k == 0 or parts) else None for k in range(4)]
+
+
+def _real_code(out_dtype):
+    return _lib.XSW_F32 if np.dtype(out_dtype) == np.float32 else _lib.XSW_F64
+
+
+def cost_numpy(lut_co, plan, codes_co, inc, sigma0, anc, dsig_co=0.1, parts=True, out_dtype=np.float64):
+    """[J, Jsig, Jwind, residual_db] (numpy, `out_dtype`) of the co-pol codes `codes_co` from the rasters they were computed
+    from: `invert_numpy`'s arithmetic for them (`plan` is the co-pol call's: a float32 sigma0 goes to dB by numpy's own log10),
+    then xsw_cost_from_codes on host memory."""
+    shape, dt = plan.shape, plan.dtype
+    cast = lambda a, t=dt: np.ascontiguousarray(np.broadcast_to(np.asarray(a), shape), dtype=t)
+    sigma0 = np.asarray(sigma0)
+    s_co = cast(_to_db(sigma0) if plan.is_db else sigma0)
+    full_inc, full_anc, cc = cast(inc), cast(anc, plan.cdtype), np.ascontiguousarray(codes_co, dtype=np.uint32)
+    outs = _cost_outputs(parts, lambda: np.empty(shape, out_dtype))
+    ctx = _lib.default_context(options.device)
+    if plan.n:
+        with ctx.lock:
+            ensure_luts(ctx, lut_co, None)
+            ctx.cost_from_codes_raw(plan.lines, plan.samples, plan.code, _real_code(out_dtype), _lib.MEM_HOST, full_inc.ctypes.data, cc.ctypes.data,
+                                    s_co.ctypes.data, full_anc.ctypes.data, *(None if o is None else o.ctypes.data for o in outs),
+                                    dsig_co=dsig_co, sigma0_is_db=plan.is_db)
+    return outs
+
+
+def cost_device(lut_co, plan, codes_co, inc, sigma0, anc, dsig_co=0.1, parts=True, out_dtype=np.float64):
+    """`cost_numpy` for rasters resident in HBM, following `invert_device`: torch tensors, asynchronous on torch's current stream."""
+    import torch
+    from .. import _device
+    codes_co = _code_tensor(codes_co)
+    dev = codes_co.device
+    t = [_device.as_tensor(inc, dev), _device.as_tensor(sigma0, dev), _device.as_tensor(anc, dev)]
+    if plan.db_by == _plan.DB_TORCH:
+        t[1] = _device.to_db(t[1])
+    t = [_device.prep(x, plan.cdtype if k == 2 else plan.dtype, plan.shape) for k, x in enumerate(t)] + [codes_co.contiguous()]
+    ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    outs = _cost_outputs(parts, lambda: torch.empty(plan.shape, dtype=_device.torch_dtype(out_dtype), device=dev))
+    p = _device.at
+    if plan.n:
+        with _device.on_current_stream(ctx, dev):
+            ensure_luts(ctx, lut_co, None)
+            ctx.cost_from_codes_raw(plan.lines, plan.samples, plan.code, _real_code(out_dtype), _lib.MEM_DEVICE, p(t[0]), p(t[3]), p(t[1]), p(t[2]),
+                                    *(p(o) for o in outs), dsig_co=dsig_co, sigma0_is_db=plan.is_db)
+            _device.keep_alive(t, dev)
+    return outs
+
+
+def cost_cr_numpy(lut_co, lut_cr, plan, codes_co, codes_cr, inc, sigma0_cr, dsig_cr, parts=True, out_dtype=np.float64):
+    """[J, Jsig, Jwind, residual_db] of the cross-pol codes `codes_cr` (from `cross_numpy`, with or without the select): the
+    cross-pol inputs formed as `cross_numpy` forms them (`plan` from `cross_plan`), then xsw_cost_cr_from_codes on host memory."""
+    shape, dt = plan.shape, plan.dtype
+    cast = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a), shape), dtype=dt)
+    sigma0_cr = np.asarray(sigma0_cr)
+    dsig = None
+    if plan.dsig == _plan.DSIG_FILL:
+        dsig = cast(dsig_raster(sigma0_cr, plan.dsig_fill))
+    elif plan.dsig == _plan.DSIG_RASTER:
+        dsig = cast(dsig_cr)
+    s_cr = cast(_to_db(sigma0_cr) if plan.is_db else sigma0_cr)
+    full_inc = cast(inc)
+    cc, ccr = np.ascontiguousarray(codes_co, dtype=np.uint32), np.ascontiguousarray(codes_cr, dtype=np.uint32)
+    outs = _cost_outputs(parts, lambda: np.empty(shape, out_dtype))
+    ctx = _lib.default_context(options.device)
+    if plan.n:
+        with ctx.lock:
+            ensure_luts(ctx, lut_co, lut_cr)
+            ctx.cost_cr_from_codes_raw(plan.lines, plan.samples, plan.code, _real_code(out_dtype), _lib.MEM_HOST, full_inc.ctypes.data, cc.ctypes.data,
+                                       ccr.ctypes.data, s_cr.ctypes.data, None if dsig is None else dsig.ctypes.data,
+                                       *(None if o is None else o.ctypes.data for o in outs), dsig_cr_scalar=plan.dsig_scalar, sigma0_is_db=plan.is_db)
+    return outs
+
+
+def cost_cr_device(lut_co, lut_cr, plan, codes_co, codes_cr, inc, sigma0_cr, dsig_cr, parts=True, out_dtype=np.float64):
+    """`cost_cr_numpy` for rasters resident in HBM, following `cross_device`; asynchronous on torch's current stream."""
+    import torch
+    from .. import _device
+    codes_co, codes_cr = _code_tensor(codes_co), _code_tensor(codes_cr)
+    dev = codes_co.device
+    t = [_device.as_tensor(inc, dev), _device.as_tensor(sigma0_cr, dev), None if np.isscalar(dsig_cr) else _device.as_tensor(dsig_cr, dev)]
+    if plan.dsig == _plan.DSIG_FILL:
+        t[2] = dsig_raster(t[1], plan.dsig_fill)
+    if plan.db_by == _plan.DB_TORCH:
+        t[1] = _device.to_db(t[1])
+    t = [_device.prep(x, plan.dtype, plan.shape) for x in t] + [codes_co.contiguous(), codes_cr.contiguous()]
+    ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    outs = _cost_outputs(parts, lambda: torch.empty(plan.shape, dtype=_device.torch_dtype(out_dtype), device=dev))
+    p = _device.at
+    if plan.n:
+        with _device.on_current_stream(ctx, dev):
+            ensure_luts(ctx, lut_co, lut_cr)
+            ctx.cost_cr_from_codes_raw(plan.lines, plan.samples, plan.code, _real_code(out_dtype), _lib.MEM_DEVICE, p(t[0]), p(t[3]), p(t[4]), p(t[1]),
+                                       p(t[2]), *(p(o) for o in outs), dsig_cr_scalar=plan.dsig_scalar, sigma0_is_db=plan.is_db)
+            _device.keep_alive(t, dev)
+    return outs
+
+
 def _uploaded_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc):
     """`_device_rasters` for a tile of numpy rasters, which follow `invert_numpy`'s arithmetic: (plan, device, tensors, src).
     With host dB the linear sigma0 stays on the host -- `src` {STAGE_*: flat raster}, converted piece by piece on its way up,

@@ -39,14 +39,45 @@ def _meta(a):
     return tuple(cai["shape"]), np.dtype(cai["typestr"])
 
 
+def _codes_meta(a):
+    """`_meta` for grid codes: a torch tensor's integer dtype by its name (`_device.meta` knows the raster dtypes only)."""
+    if _device.is_device_array(a) and hasattr(a, "is_cuda"):
+        try:
+            return tuple(a.shape), np.dtype(str(a.dtype).rpartition(".")[2])
+        except TypeError:
+            return tuple(a.shape), np.dtype(np.void)
+    return _meta(a)
+
+
+class InversionCost:
+    """Result of `CopolCodes.cost` / `.cost_dual`: the value of the minimum the search found and what it is made of, one real
+    raster each (numpy arrays, or torch tensors for device rasters): J = Jsig + Jwind (cross-pol without a co-pol wind:
+    J = Jsig, Jwind NaN), Jsig = ((lut_db - sigma0_db) / dsig)^2, Jwind the distance to the a-priori wind, residual_db =
+    lut_db - sigma0_db at the solution.  NaN where no search ran.  With parts=False only J is computed: the others are None."""
+
+    def __init__(self, J, Jsig=None, Jwind=None, residual_db=None):
+        self.J, self.Jsig, self.Jwind, self.residual_db = J, Jsig, Jwind, residual_db
+
+    def __getitem__(self, name):
+        return getattr(self, name)
+
+
+def _real_dtype(out_dtype):
+    dt = np.dtype(np.float64 if out_dtype is None else out_dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError(f"out_dtype must be float32 or float64, not {dt}")
+    return dt.type
+
+
 class CopolCodes:
     """The co-pol answer of `invert_copol_codes`: `codes` (uint32 numpy array, or int32 torch tensor holding the same bits:
     include/xsw.h, out_code_co), the incidence raster and the co-pol LUT they belong to.  sigma0_meta / ancillary_meta:
     (shape, dtype) of the co-pol call's sigma0 and ancillary wind (they decide, with the cross-pol rasters, the dtype the
-    fused dual-pol call would compute in); by default those of a call whose rasters all have the incidence's dtype."""
+    fused dual-pol call would compute in); by default those of a call whose rasters all have the incidence's dtype.  dsig_co:
+    the co-pol call's, what `cost` divides by when it is given none (None: 0.1, the default of that call)."""
 
-    def __init__(self, inc, codes, lut_co, sigma0_meta=None, ancillary_meta=None):
-        self.inc, self.codes, self.lut_co = inc, codes, lut_co
+    def __init__(self, inc, codes, lut_co, sigma0_meta=None, ancillary_meta=None, dsig_co=None):
+        self.inc, self.codes, self.lut_co, self.dsig_co = inc, codes, lut_co, dsig_co
         self.on_device = _device.is_device_array(codes)
         self.shape = tuple(codes.shape)
         self.inc_meta = _meta(inc)
@@ -94,6 +125,72 @@ class CopolCodes:
         return _engine.dual_select(ws_co, ws_cr) if dual_select else ws_cr
 
 
+    def _same_kind(self, **arrays):
+        for name, v in arrays.items():
+            if v is not None and _device.is_device_array(v) != self.on_device:
+                raise ValueError(f"{name} is a {'device' if not self.on_device else 'host'} array but the co-pol codes are in "
+                                 f"{'device' if self.on_device else 'host'} memory: one container kind per CopolCodes")
+
+    def cost(self, sigma0, ancillary_wind, dsig_co=None, parts=True, out_dtype=None):
+        """The cost the co-pol search minimised, at its minimum: `InversionCost` with J = Jwind + Jsig of windspeed.py:216-225 at
+        the stored grid point (bit for bit the minimum of the reference's dense J_co), its two terms and residual_db = lut_db -
+        sigma0_db.  sigma0 / ancillary_wind: the rasters `invert_copol_codes` was given (a raster of another shape or dtype is
+        refused: the cost would not be the one the search minimised).  dsig_co=None: the co-pol call's (else 0.1).
+        parts=False: J alone.  out_dtype: float64 (default) or float32.  ValueError / TypeError before any device call."""
+        _refuse_containers("CopolCodes.cost", sigma0, ancillary_wind)
+        if sigma0 is None or ancillary_wind is None:
+            raise ValueError("sigma0 and ancillary_wind are both needed: the rasters the co-pol codes were computed from")
+        self._same_kind(sigma0=sigma0, ancillary_wind=ancillary_wind)
+        for name, v, stored in (("sigma0", sigma0, self.sigma0_meta), ("ancillary_wind", ancillary_wind, self.ancillary_meta)):
+            m = _meta(v)
+            if stored is not None and (tuple(m[0]), np.dtype(m[1])) != (tuple(stored[0]), np.dtype(stored[1])):
+                raise ValueError(f"{name} has shape {tuple(m[0])} and dtype {np.dtype(m[1]).name}, the co-pol codes were computed from shape "
+                                 f"{tuple(stored[0])} and dtype {np.dtype(stored[1]).name}: the cost would not be the one the search minimised")
+        try:
+            plan = _plan.CallPlan(self.inc_meta, _meta(sigma0), None, None, _meta(ancillary_wind), device=self.on_device)
+        except ValueError as exc:
+            raise ValueError(f"sigma0 / ancillary_wind do not broadcast against the co-pol codes of shape {self.shape}: {exc}") from None
+        if plan.shape != self.shape:
+            raise ValueError(f"sigma0 / ancillary_wind broadcast to shape {plan.shape}, the co-pol codes have shape {self.shape}")
+        if dsig_co is None:
+            dsig_co = 0.1 if self.dsig_co is None else self.dsig_co
+        if not np.isscalar(dsig_co) or not float(dsig_co) == float(dsig_co) or float(dsig_co) == 0.0:
+            raise ValueError(f"dsig_co must be a scalar other than 0 and NaN, not {dsig_co!r}")
+        run = _engine.cost_device if self.on_device else _engine.cost_numpy
+        return InversionCost(*run(self.lut_co, plan, self.codes, self.inc, sigma0, ancillary_wind, dsig_co=float(dsig_co), parts=parts,
+                                  out_dtype=_real_dtype(out_dtype)))
+
+    def cost_dual(self, sigma0_dual, codes_cr, dsig_cr=0.1, model=None, parts=True, out_dtype=None, **kwargs):
+        """The cost the cross-pol search of `.dual(sigma0_dual, dsig_cr=..., model=..., **kwargs)` minimised, at its minimum:
+        `InversionCost` with J = Jsig_cr [+ Jwind_cr] of windspeed.py:257-264 (Jwind NaN and J = Jsig where there is no co-pol
+        wind).  codes_cr: what `.dual(..., codes=True)` returned, with or without dual_select (the select does not enter the
+        cost).  The same refusals as `.dual`, before any device call."""
+        scalar = np.isscalar(dsig_cr)
+        _refuse_containers("CopolCodes.cost_dual", sigma0_dual, codes_cr, None if scalar else dsig_cr)
+        if sigma0_dual is None or codes_cr is None:
+            raise ValueError("sigma0_dual and codes_cr are both needed")
+        self._same_kind(sigma0_dual=sigma0_dual, codes_cr=codes_cr, dsig_cr=None if scalar else dsig_cr)
+        cm = _codes_meta(codes_cr)
+        if np.dtype(cm[1]) not in (np.dtype(np.uint32), np.dtype(np.int32)):
+            raise TypeError(f"codes_cr must be uint32 or int32 grid codes, not {np.dtype(cm[1]).name}")
+        if tuple(cm[0]) != self.shape:
+            raise ValueError(f"codes_cr has shape {tuple(cm[0])}, the co-pol codes have shape {self.shape}")
+        plan = _engine.cross_plan(self.shape, self.inc_meta, self.sigma0_meta, self.ancillary_meta, _meta(sigma0_dual),
+                                  dsig_cr if scalar else _meta(dsig_cr), device=self.on_device)
+        mono = _plan.CallPlan(self.inc_meta, self.sigma0_meta, None, None, self.ancillary_meta, device=self.on_device)
+        if (mono.dtype, mono.db_by) != (plan.dtype, plan.db_by):
+            raise ValueError(f"the dtypes of sigma0_dual / dsig_cr would make the fused dual-pol call compute in {np.dtype(plan.dtype).name} "
+                             f"with sigma0 in dB by {plan.db_by}, but the stored codes were computed in {np.dtype(mono.dtype).name} with dB by "
+                             f"{mono.db_by}: pass cross-pol rasters of the co-pol rasters' dtype")
+        m = get_model(model)
+        if not m.iscrosspol:
+            raise ValueError(f"model {m.name} ({m.pol}) is not a cross-pol model")
+        lut_cr = _engine.lut_source(m, kwargs)
+        run = _engine.cost_cr_device if self.on_device else _engine.cost_cr_numpy
+        return InversionCost(*run(self.lut_co, lut_cr, plan, self.codes, codes_cr, self.inc, sigma0_dual, dsig_cr, parts=parts,
+                                  out_dtype=_real_dtype(out_dtype)))
+
+
 def invert_copol_codes(inc, sigma0, /, ancillary_wind=None, dsig_co=0.1, model=None, **kwargs):
     """The co-pol inversion of `invert_from_model(inc, sigma0, ancillary_wind=..., dsig_co=..., model=...)` kept as grid codes:
     a `CopolCodes`, whose `wind()` is that call's return value and whose `dual(sigma0_dual, ...)` runs the cross-pol step of
@@ -114,4 +211,4 @@ def invert_copol_codes(inc, sigma0, /, ancillary_wind=None, dsig_co=0.1, model=N
     else:
         inc, sigma0, ancillary_wind = np.asarray(inc), np.asarray(sigma0), np.asarray(ancillary_wind)
         codes, _ = _engine.invert_numpy(lut_co, None, inc, sigma0, None, None, ancillary_wind, dsig_co=dsig_co, codes=True)
-    return CopolCodes(inc, codes, lut_co, sigma0_meta=_meta(sigma0), ancillary_meta=_meta(ancillary_wind))
+    return CopolCodes(inc, codes, lut_co, sigma0_meta=_meta(sigma0), ancillary_meta=_meta(ancillary_wind), dsig_co=dsig_co)
