@@ -222,7 +222,7 @@ def test_dsig_co_defaults_to_the_stored_value(monkeypatch):
     """dsig_co=None takes the CopolCodes' own (what invert_copol_codes was given), else 0.1; an explicit value wins."""
     from xsarsea_amd.windspeed import _engine
     seen = []
-    monkeypatch.setattr(_engine, "cost_numpy", lambda *a, **k: seen.append(k["dsig_co"]) or [None] * 4)
+    monkeypatch.setattr(_engine, "cost_from_codes", lambda *a, **k: seen.append(k["dsig_co"]) or [None] * 4)
     vv, anc = np.full((6, 10), 1e-2, np.float32), np.full((6, 10), 5 + 1j, np.complex64)
     _codes(dsig_co=0.25).cost(vv, anc)
     _codes().cost(vv, anc)

@@ -240,6 +240,11 @@ def test_host_route_equals_device_route(gpu_ctx, torch, default_luts):
     gpu_ctx.cross_from_codes_raw(531, 700, _lib.XSW_F32, _lib.XSW_F32, _lib.MEM_HOST, inc.ctypes.data, want["cc"].ctypes.data, s_vh.ctypes.data,
                                  dsig.ctypes.data, None, t.ctypes.data, dual_select=True)
     assert np.array_equal(_bits(t), _bits(want["cr"]))
+    # cross-pol only (code_co = NULL): the absent input stays absent on the host route
+    inc, _, s_vh, dsig, _ = _scene((5, 67), np.float32, 29)
+    a = _cross(gpu_ctx, torch, _lib, inc, None, s_vh, dsig, np.complex64, True)
+    b = _cross(gpu_ctx, torch, _lib, inc, None, s_vh, dsig, np.complex64, True, mem=_lib.MEM_HOST)
+    assert not np.any(b[0] == 0x12345678) and np.array_equal(a[0], b[0]) and np.array_equal(_bits(a[1]), _bits(b[1]))
 
 
 def test_error_codes(torch, default_luts):

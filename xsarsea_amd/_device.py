@@ -81,6 +81,12 @@ def device_of(*arrays):
     raise ValueError("no device array among the arguments")
 
 
+def context_of(device):
+    """The libxsw context of a torch device (one without an index: torch's current device)."""
+    import torch
+    return _lib.default_context(device.index if device.index is not None else torch.cuda.current_device())
+
+
 class on_current_stream:
     """Runs the context's launches on torch's current stream of `device` (so they are ordered with the caller's other work,
     asynchronously), then hands the context back to its own stream; both hand-overs are device-side event waits."""

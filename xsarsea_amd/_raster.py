@@ -64,7 +64,7 @@ class _Call:
             import torch
             self.torch = torch
             self.dev = _device.device_of(*[a for a in arrays if _is_tensor(a)])
-            self.ctx = _lib.default_context(self.dev.index if self.dev.index is not None else torch.cuda.current_device())
+            self.ctx = _device.context_of(self.dev)
         else:
             self.ctx = _lib.default_context(options.device)
         self.mem = _lib.MEM_DEVICE if self.device else _lib.MEM_HOST

@@ -24,7 +24,7 @@
 
 using namespace xsw;
 
-#include "xsw_host.hpp"
+#include "xsw_run.hpp"
 
 #define HIPCHK(c, expr)                                                                          \
     do {                                                                                         \
@@ -481,10 +481,7 @@ extern "C" int xsw_lut_read(xsw_ctx *c, int32_t cross, double *out_db)
 // ---------------------------------------------------------------------------------------- invert
 static int dispatch_invert(xsw_ctx *c, const KArgs &A, int dtype, int out_dtype, int algo, const LaunchCtl &lc, std::string &err)
 {
-    if (dtype == XSW_F32 && out_dtype == XSW_F32) return xsw_launch_invert_ff(c, A, algo, lc, err);
-    if (dtype == XSW_F32 && out_dtype == XSW_F64) return xsw_launch_invert_fd(c, A, algo, lc, err);
-    if (dtype == XSW_F64 && out_dtype == XSW_F32) return xsw_launch_invert_df(c, A, algo, lc, err);
-    return xsw_launch_invert_dd(c, A, algo, lc, err);
+    return pair_launch(dtype, out_dtype).invert(c, A, algo, lc, err);
 }
 
 // Work lists of the device-raster path (capacities: xsw_plan.hpp).  A failed allocation selects the one-kernel path.
@@ -661,43 +658,16 @@ extern "C" int xsw_cross_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, 
         return fail(c, XSW_EINVAL, "cross_from_codes: raster too large for one launch");
     const long long n = (long long)lines * samples;
     if (n == 0) return XSW_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    CrossArgs A{};
-    A.n = n;
-    A.dsig_cr_scalar = dsig_cr_scalar;
-    A.is_db = sigma0_is_db;
-    A.dual_select = dual_select;
-    std::string err;
-    auto launch = [&]() {
-        if (dtype == XSW_F32 && out_dtype == XSW_F32) return xsw_launch_cross_ff(c, A, c->stream, err);
-        if (dtype == XSW_F32) return xsw_launch_cross_fd(c, A, c->stream, err);
-        if (out_dtype == XSW_F32) return xsw_launch_cross_df(c, A, c->stream, err);
-        return xsw_launch_cross_dd(c, A, c->stream, err);
-    };
-    if (mem == XSW_MEM_DEVICE) {  // asynchronous on the context's stream
-        A.inc = inc; A.s_cr = sigma0_cr; A.dsig_cr = dsig_cr; A.code_co = code_co; A.code_cr = out_code_cr; A.out_cr = out_cr;
-        const int rc = launch();
-        return rc ? fail(c, rc, "%s", err.c_str()) : XSW_OK;
-    }
-    // host rasters (synchronous): upload, one kernel, download
-    CallTemps tmp(c->stream);
     const size_t es = dtype == XSW_F32 ? 4 : 8, os = out_dtype == XSW_F32 ? 8 : 16, px = (size_t)n;
-    A.inc = tmp.alloc(px * es, inc);
-    A.s_cr = tmp.alloc(px * es, sigma0_cr);
-    if (dsig_cr) A.dsig_cr = tmp.alloc(px * es, dsig_cr);
-    if (code_co) A.code_co = (const unsigned *)tmp.alloc(px * 4, code_co);
-    if (out_code_cr) A.code_cr = (unsigned *)tmp.alloc(px * 4);
-    if (out_cr) A.out_cr = tmp.alloc(px * os);
-    if (!tmp.ok()) return tmp.refused ? fail(c, XSW_ENOMEM, "hipMalloc(%zu) failed", tmp.refused) : fail(c, XSW_EHIP, "cross_from_codes: upload failed: %s", hipGetErrorString(tmp.err));
-    int rc = launch();
-    hipError_t e = hipSuccess;
-    if (!rc && out_code_cr) e = hipMemcpyAsync(out_code_cr, A.code_cr, px * 4, hipMemcpyDeviceToHost, c->stream);
-    if (!rc && e == hipSuccess && out_cr) e = hipMemcpyAsync(out_cr, A.out_cr, px * os, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t se = tmp.finish();
-    if (rc) return fail(c, rc, "%s", err.c_str());
-    if (e == hipSuccess) e = se;
-    if (e != hipSuccess) return fail(c, XSW_EHIP, "cross_from_codes failed: %s", hipGetErrorString(e));
-    return XSW_OK;
+    Buf b[6] = {in_buf(inc, px * es), in_buf(sigma0_cr, px * es), in_buf(dsig_cr, px * es), in_buf(code_co, px * 4),
+                out_buf(out_code_cr, px * 4), out_buf(out_cr, px * os)};
+    return run(c, mem, b, [&](Buf (&x)[6]) {
+        const CrossArgs A{x[0].dev, x[1].dev, x[2].dev, (const unsigned *)x[3].dev, (unsigned *)x[4].dev, x[5].dev, n, dsig_cr_scalar,
+                          sigma0_is_db, dual_select};
+        std::string err;
+        const int rc = pair_launch(dtype, out_dtype).cross(c, A, c->stream, err);
+        return rc ? fail(c, rc, "%s", err.c_str()) : XSW_OK;
+    }, "cross_from_codes");
 }
 
 // ---- inversion cost and sigma0 residual from stored codes (xsw.h: xsw_cost_from_codes, xsw_cost_cr_from_codes; kernels: xsw_cost.hpp)
@@ -718,41 +688,18 @@ static int cost_from_codes(xsw_ctx *c, const char *who, bool cr, int64_t lines, 
         return fail(c, XSW_EINVAL, "%s: raster too large for one launch", who);
     A.n = (long long)lines * samples;
     if (A.n == 0) return XSW_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    std::string err;
-    auto launch = [&]() {
-        if (dtype == XSW_F32 && out_dtype == XSW_F32) return xsw_launch_cost_ff(c, A, cr, c->stream, err);
-        if (dtype == XSW_F32) return xsw_launch_cost_fd(c, A, cr, c->stream, err);
-        if (out_dtype == XSW_F32) return xsw_launch_cost_df(c, A, cr, c->stream, err);
-        return xsw_launch_cost_dd(c, A, cr, c->stream, err);
-    };
-    if (mem == XSW_MEM_DEVICE) {  // asynchronous on the context's stream
-        const int rc = launch();
-        return rc ? fail(c, rc, "%s", err.c_str()) : XSW_OK;
-    }
-    // host rasters (synchronous): upload, one kernel, download
-    CallTemps tmp(c->stream);
     const size_t es = dtype == XSW_F32 ? 4 : 8, os = out_dtype == XSW_F32 ? 4 : 8, px = (size_t)A.n;
-    void *host_out[4] = {A.out_J, A.out_Jsig, A.out_Jwind, A.out_res};
-    void **dev_out[4] = {&A.out_J, &A.out_Jsig, &A.out_Jwind, &A.out_res};
-    A.inc = tmp.alloc(px * es, A.inc);
-    A.s = tmp.alloc(px * es, A.s);
-    if (A.anc) A.anc = tmp.alloc(px * es * 2, A.anc);
-    if (A.dsig_cr) A.dsig_cr = tmp.alloc(px * es, A.dsig_cr);
-    if (A.code_co) A.code_co = (const unsigned *)tmp.alloc(px * 4, A.code_co);
-    if (A.code_cr) A.code_cr = (const unsigned *)tmp.alloc(px * 4, A.code_cr);
-    for (int k = 0; k < 4; ++k)
-        if (host_out[k]) *dev_out[k] = tmp.alloc(px * os);
-    if (!tmp.ok()) return tmp.refused ? fail(c, XSW_ENOMEM, "hipMalloc(%zu) failed", tmp.refused) : fail(c, XSW_EHIP, "%s: upload failed: %s", who, hipGetErrorString(tmp.err));
-    const int rc = launch();
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 4 && !rc && e == hipSuccess; ++k)
-        if (host_out[k]) e = hipMemcpyAsync(host_out[k], *dev_out[k], px * os, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t se = tmp.finish();
-    if (rc) return fail(c, rc, "%s", err.c_str());
-    if (e == hipSuccess) e = se;
-    if (e != hipSuccess) return fail(c, XSW_EHIP, "%s failed: %s", who, hipGetErrorString(e));
-    return XSW_OK;
+    Buf b[10] = {in_buf(A.inc, px * es), in_buf(A.s, px * es), in_buf(A.anc, px * es * 2), in_buf(A.dsig_cr, px * es),
+                 in_buf(A.code_co, px * 4), in_buf(A.code_cr, px * 4), out_buf(A.out_J, px * os), out_buf(A.out_Jsig, px * os),
+                 out_buf(A.out_Jwind, px * os), out_buf(A.out_res, px * os)};
+    return run(c, mem, b, [&](Buf (&x)[10]) {
+        A.inc = x[0].dev; A.s = x[1].dev; A.anc = x[2].dev; A.dsig_cr = x[3].dev;
+        A.code_co = (const unsigned *)x[4].dev; A.code_cr = (const unsigned *)x[5].dev;
+        A.out_J = x[6].dev; A.out_Jsig = x[7].dev; A.out_Jwind = x[8].dev; A.out_res = x[9].dev;
+        std::string err;
+        const int rc = pair_launch(dtype, out_dtype).cost(c, A, cr, c->stream, err);
+        return rc ? fail(c, rc, "%s", err.c_str()) : XSW_OK;
+    }, who);
 }
 
 extern "C" int xsw_cost_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
@@ -1153,28 +1100,13 @@ extern "C" int xsw_gmf_eval(xsw_ctx *c, int32_t gmf_id, int64_t n, int32_t mem, 
     if (n < 0 || !inc || !wspd || !out) return fail(c, XSW_EINVAL, "gmf_eval: bad argument");
     if (gmf_id <= GMF_CMODIFR2 && !phi) return fail(c, XSW_EINVAL, "gmf_eval: this GMF needs phi");
     if (n == 0) return XSW_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    auto launch = [&](const double *d_inc, const double *d_w, const double *d_phi, double *d_out) {
-        long long blocks = (n + 255) / 256;
-        if (blocks > 256 * 16) blocks = 256 * 16;
-        XSW_GMF_DISPATCH(gmf_id, hipLaunchKernelGGL((k_gmf_eval<M>), dim3((unsigned)blocks), dim3(256), 0, c->stream, (int)gmf_id, (long long)n, d_inc, d_w, d_phi, d_out));
-        return hipGetLastError();
-    };
-    hipError_t e;
-    if (mem == XSW_MEM_HOST) {
-        CallTemps tmp(c->stream);
-        const size_t bytes = (size_t)n * 8;
-        const double *d_inc = (const double *)tmp.alloc(bytes, inc), *d_w = (const double *)tmp.alloc(bytes, wspd);
-        const double *d_phi = phi ? (const double *)tmp.alloc(bytes, phi) : nullptr;
-        double *d_out = (double *)tmp.alloc(bytes);
-        e = tmp.err;
-        if (e == hipSuccess) e = launch(d_inc, d_w, d_phi, d_out);
-        if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream);
-        const hipError_t se = tmp.finish();
-        if (e == hipSuccess) e = se;
-    } else e = launch(inc, wspd, phi, out);
-    if (e != hipSuccess) return fail(c, XSW_EHIP, "gmf_eval failed: %s", hipGetErrorString(e));
-    return XSW_OK;
+    const size_t bytes = (size_t)n * 8;
+    Buf b[4] = {in_buf(inc, bytes), in_buf(wspd, bytes), in_buf(phi, bytes), out_buf(out, bytes)};
+    return run(c, mem, b, [&](Buf (&x)[4]) {
+        const long long blocks = std::min<long long>((n + 255) / 256, 256 * 16);
+        XSW_GMF_DISPATCH(gmf_id, hipLaunchKernelGGL((k_gmf_eval<M>), dim3((unsigned)blocks), dim3(256), 0, c->stream, (int)gmf_id, (long long)n,
+                                                    (const double *)x[0].dev, (const double *)x[1].dev, (const double *)x[2].dev, (double *)x[3].dev));
+    }, "gmf_eval");
 }
 
 // ---------------------------------------------------------------------------------------- detrend
@@ -1369,14 +1301,13 @@ extern "C" int xsw_nesz_flatten(xsw_ctx *c, int64_t lines, int64_t samples, int3
     } while (0)
 
 template <typename T, typename TN>
-static hipError_t launch_dsig(hipStream_t s, int rule, const void *inc, const void *sigma0, const void *nesz, void *out, long long n)
+static void launch_dsig(hipStream_t s, int rule, const void *inc, const void *sigma0, const void *nesz, void *out, long long n)
 {
     const unsigned blocks = (unsigned)((n + 256LL * XSW_DSIG_V - 1) / (256LL * XSW_DSIG_V));
 #define XSW_CALL(R) hipLaunchKernelGGL((k_dsig<T, TN, R>), dim3(blocks), dim3(256), 0, s, (const T *)sigma0, (const TN *)nesz, (const T *)inc, \
                                        (typename DsigOut<T, TN, R>::type *)out, n)
     XSW_DSIG_RULES(rule, XSW_CALL);
 #undef XSW_CALL
-    return hipGetLastError();
 }
 
 static bool dsig_dtype_ok(int32_t dt) { return dt == XSW_F32 || dt == XSW_F64; }
@@ -1394,32 +1325,20 @@ extern "C" int xsw_dsig(xsw_ctx *c, int32_t rule, int64_t lines, int64_t samples
     if (samples && lines > (int64_t)(0x7fffffffLL * 256 * XSW_DSIG_V) / samples) return fail(c, XSW_EINVAL, "raster too large for one launch");
     const long long n = (long long)lines * samples;
     if (n == 0) return XSW_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (rule != XSW_DSIG_S1_V2) inc = nullptr;
     const size_t es = dtype == XSW_F32 ? 4 : 8, ns = nesz_dtype == XSW_F32 ? 4 : 8;
     const size_t os = (rule != XSW_DSIG_S1_V2 && es == 4 && ns == 4) ? 4 : 8;
-    auto launch = [&](const void *di, const void *ds, const void *dn, void *dout) {
-        if (es == 4) return ns == 4 ? launch_dsig<float, float>(c->stream, rule, di, ds, dn, dout, n) : launch_dsig<float, double>(c->stream, rule, di, ds, dn, dout, n);
-        return ns == 4 ? launch_dsig<double, float>(c->stream, rule, di, ds, dn, dout, n) : launch_dsig<double, double>(c->stream, rule, di, ds, dn, dout, n);
-    };
-    hipError_t e;
-    if (mem == XSW_MEM_HOST) {
-        CallTemps tmp(c->stream);
-        const void *d_s = tmp.alloc((size_t)n * es, sigma0_cr), *d_n = tmp.alloc((size_t)n * ns, nesz_cr);
-        const void *d_i = inc ? tmp.alloc((size_t)n * es, inc) : nullptr;
-        void *d_out = tmp.alloc((size_t)n * os);
-        e = tmp.err;
-        if (e == hipSuccess) e = launch(d_i, d_s, d_n, d_out);
-        if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * os, hipMemcpyDeviceToHost, c->stream);
-        const hipError_t se = tmp.finish();
-        if (e == hipSuccess) e = se;
-    } else e = launch(inc, sigma0_cr, nesz_cr, out);
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? XSW_ENOMEM : XSW_EHIP, "dsig failed: %s", hipGetErrorString(e));
-    return XSW_OK;
+    Buf b[4] = {in_buf(rule == XSW_DSIG_S1_V2 ? inc : nullptr, (size_t)n * es), in_buf(sigma0_cr, (size_t)n * es), in_buf(nesz_cr, (size_t)n * ns),
+                out_buf(out, (size_t)n * os)};
+    return run(c, mem, b, [&](Buf (&x)[4]) {
+        if (es == 4 && ns == 4) launch_dsig<float, float>(c->stream, rule, x[0].dev, x[1].dev, x[2].dev, x[3].dev, n);
+        else if (es == 4) launch_dsig<float, double>(c->stream, rule, x[0].dev, x[1].dev, x[2].dev, x[3].dev, n);
+        else if (ns == 4) launch_dsig<double, float>(c->stream, rule, x[0].dev, x[1].dev, x[2].dev, x[3].dev, n);
+        else launch_dsig<double, double>(c->stream, rule, x[0].dev, x[1].dev, x[2].dev, x[3].dev, n);
+    }, "dsig");
 }
 
 template <typename T, typename TO>
-static hipError_t launch_dsig_flat(hipStream_t s, int rule, const void *noise, const void *inc, const void *sigma0, void *scratch, void *out,
+static void launch_dsig_flat(hipStream_t s, int rule, const void *noise, const void *inc, const void *sigma0, void *scratch, void *out,
                                    long long lines, long long samples, int nb, long long lpb)
 {
     const NeszScratch k(scratch, samples, nb);
@@ -1429,7 +1348,6 @@ static hipError_t launch_dsig_flat(hipStream_t s, int rule, const void *noise, c
                                        (const T *)inc, (TO *)out, lines, samples, e.rows_per_block)
     XSW_DSIG_RULES(rule, XSW_CALL);
 #undef XSW_CALL
-    return hipGetLastError();
 }
 
 extern "C" int xsw_dsig_flat(xsw_ctx *c, int32_t rule, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
@@ -1448,25 +1366,15 @@ extern "C" int xsw_dsig_flat(xsw_ctx *c, int32_t rule, int64_t lines, int64_t sa
     const NeszBlocks nbk = nesz_blocks(lines, samples, sizeof(NeszPartial));
     if (nbk.scratch_bytes > c->nesz_cap)  // (synchronised first: a previous call may still be using the old scratch)
         HIPCHK(c, grow(c->nesz_scratch, c->nesz_cap, nbk.scratch_bytes, &c->stream));
-    auto launch = [&](const void *dn, const void *di, const void *ds, void *dout) {
-#define XSW_CALL(T, TO) launch_dsig_flat<T, TO>(c->stream, rule, dn, di, ds, c->nesz_scratch, dout, lines, samples, (int)nbk.nb, nbk.lpb)
-        if (es == 4) return os == 4 ? XSW_CALL(float, float) : XSW_CALL(float, double);
-        return os == 4 ? XSW_CALL(double, float) : XSW_CALL(double, double);
+    Buf b[4] = {in_buf(noise, (size_t)n * es), in_buf(inc, (size_t)n * es), in_buf(sigma0_cr, (size_t)n * es), out_buf(out, (size_t)n * os)};
+    return run(c, mem, b, [&](Buf (&x)[4]) {
+#define XSW_CALL(T, TO) launch_dsig_flat<T, TO>(c->stream, rule, x[0].dev, x[1].dev, x[2].dev, c->nesz_scratch, x[3].dev, lines, samples, (int)nbk.nb, nbk.lpb)
+        if (es == 4 && os == 4) XSW_CALL(float, float);
+        else if (es == 4) XSW_CALL(float, double);
+        else if (os == 4) XSW_CALL(double, float);
+        else XSW_CALL(double, double);
 #undef XSW_CALL
-    };
-    hipError_t e;
-    if (mem == XSW_MEM_HOST) {
-        CallTemps tmp(c->stream);
-        const void *d_n = tmp.alloc((size_t)n * es, noise), *d_i = tmp.alloc((size_t)n * es, inc), *d_s = tmp.alloc((size_t)n * es, sigma0_cr);
-        void *d_out = tmp.alloc((size_t)n * os);
-        e = tmp.err;
-        if (e == hipSuccess) e = launch(d_n, d_i, d_s, d_out);
-        if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * os, hipMemcpyDeviceToHost, c->stream);
-        const hipError_t se = tmp.finish();
-        if (e == hipSuccess) e = se;
-    } else e = launch(noise, inc, sigma0_cr, out);
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? XSW_ENOMEM : XSW_EHIP, "dsig_flat failed: %s", hipGetErrorString(e));
-    return XSW_OK;
+    }, "dsig_flat");
 }
 
 extern "C" int xsw_dsig_wspd(xsw_ctx *c, int32_t rule, int64_t n, int32_t mem, const double *U, const double *snr, double *out)
@@ -1482,24 +1390,11 @@ extern "C" int xsw_dsig_wspd(xsw_ctx *c, int32_t rule, int64_t n, int32_t mem, c
     if (mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE) return fail(c, XSW_EINVAL, "dsig_wspd: bad mem kind");
     if (n < 0 || !U || !snr || !out) return fail(c, XSW_EINVAL, "dsig_wspd: bad argument");
     if (n == 0) return XSW_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    auto launch = [&](const double *d_u, const double *d_snr, double *d_out) {
+    const size_t bytes = (size_t)n * 8;
+    Buf b[3] = {in_buf(U, bytes), in_buf(snr, bytes), out_buf(out, bytes)};
+    return run(c, mem, b, [&](Buf (&x)[3]) {
         const long long blocks = std::min<long long>((n + 255) / 256, 256 * 16);
-        hipLaunchKernelGGL(k_dsig_wspd, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_u, d_snr, d_out, (long long)n, coef[rule]);
-        return hipGetLastError();
-    };
-    hipError_t e;
-    if (mem == XSW_MEM_HOST) {
-        CallTemps tmp(c->stream);
-        const size_t bytes = (size_t)n * 8;
-        const double *d_u = (const double *)tmp.alloc(bytes, U), *d_snr = (const double *)tmp.alloc(bytes, snr);
-        double *d_out = (double *)tmp.alloc(bytes);
-        e = tmp.err;
-        if (e == hipSuccess) e = launch(d_u, d_snr, d_out);
-        if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream);
-        const hipError_t se = tmp.finish();
-        if (e == hipSuccess) e = se;
-    } else e = launch(U, snr, out);
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? XSW_ENOMEM : XSW_EHIP, "dsig_wspd failed: %s", hipGetErrorString(e));
-    return XSW_OK;
+        hipLaunchKernelGGL(k_dsig_wspd, dim3((unsigned)blocks), dim3(256), 0, c->stream, (const double *)x[0].dev, (const double *)x[1].dev,
+                           (double *)x[2].dev, (long long)n, coef[rule]);
+    }, "dsig_wspd");
 }

@@ -197,15 +197,7 @@ static inline xsw::KArgs slice(const xsw::KArgs &A, const ChunkPlan::Chunk &ch, 
     return B;
 }
 
-// One (input dtype, output dtype) pair of the inversion launches per translation unit (xsw_invert_tu.hip, -DXSW_PAIR=0..3:
-// f32->f32, f32->f64, f64->f32, f64->f64), so that the four sets of kernel instantiations compile side by side.
-int xsw_launch_invert_ff(xsw_ctx *c, const xsw::KArgs &A, int algo, const LaunchCtl &lc, std::string &err);
-int xsw_launch_invert_fd(xsw_ctx *c, const xsw::KArgs &A, int algo, const LaunchCtl &lc, std::string &err);
-int xsw_launch_invert_df(xsw_ctx *c, const xsw::KArgs &A, int algo, const LaunchCtl &lc, std::string &err);
-int xsw_launch_invert_dd(xsw_ctx *c, const xsw::KArgs &A, int algo, const LaunchCtl &lc, std::string &err);
-
-// The arguments of k_cross_from_codes (xsw_cross.hpp; xsw.h: xsw_cross_from_codes) and its launches, one dtype pair per
-// translation unit next to that pair's inversion kernels.
+// The arguments of k_cross_from_codes (xsw_cross.hpp; xsw.h: xsw_cross_from_codes).
 namespace xsw {
 struct CrossArgs {
     const void *inc, *s_cr, *dsig_cr;  // dsig_cr nullable: dsig_cr_scalar broadcast as in load_pixel
@@ -216,15 +208,8 @@ struct CrossArgs {
     double dsig_cr_scalar;
     int is_db, dual_select;
 };
-}  // namespace xsw
-int xsw_launch_cross_ff(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream, std::string &err);
-int xsw_launch_cross_fd(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream, std::string &err);
-int xsw_launch_cross_df(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream, std::string &err);
-int xsw_launch_cross_dd(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream, std::string &err);
 
-// The arguments of k_cost_co / k_cost_cr (xsw_cost.hpp; xsw.h: xsw_cost_from_codes, xsw_cost_cr_from_codes) and their launches,
-// next to k_cross_from_codes in each dtype pair's translation unit.
-namespace xsw {
+// The arguments of k_cost_co / k_cost_cr (xsw_cost.hpp; xsw.h: xsw_cost_from_codes, xsw_cost_cr_from_codes).
 struct CostArgs {
     const void *inc, *s, *anc, *dsig_cr;  // s: sigma0_co (k_cost_co, with anc) or sigma0_cr (k_cost_cr, with the nullable dsig_cr)
     const unsigned *code_co, *code_cr;    // k_cost_cr: code_co nullable (every pixel XSW_CODE_NAN)
@@ -234,7 +219,21 @@ struct CostArgs {
     int is_db;
 };
 }  // namespace xsw
-int xsw_launch_cost_ff(xsw_ctx *c, const xsw::CostArgs &A, bool cr, hipStream_t stream, std::string &err);
-int xsw_launch_cost_fd(xsw_ctx *c, const xsw::CostArgs &A, bool cr, hipStream_t stream, std::string &err);
-int xsw_launch_cost_df(xsw_ctx *c, const xsw::CostArgs &A, bool cr, hipStream_t stream, std::string &err);
-int xsw_launch_cost_dd(xsw_ctx *c, const xsw::CostArgs &A, bool cr, hipStream_t stream, std::string &err);
+
+// The launches of one (input dtype, output dtype) pair: the inversion kernels, k_cross_from_codes and k_cost_co / k_cost_cr.
+// Each returns an XSW_* code and, with a non-zero one, its message in `err`.  One instance per translation unit
+// (xsw_invert_tu.hip, -DXSW_PAIR=0..3: f32->f32, f32->f64, f64->f32, f64->f64), so that the four sets of kernel
+// instantiations compile side by side; it sits behind a host function, which keeps it out of the device pass.
+struct PairLaunch {
+    int (*invert)(xsw_ctx *c, const xsw::KArgs &A, int algo, const LaunchCtl &lc, std::string &err);
+    int (*cross)(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream, std::string &err);
+    int (*cost)(xsw_ctx *c, const xsw::CostArgs &A, bool cr, hipStream_t stream, std::string &err);
+};
+const PairLaunch &xsw_pair_0(), &xsw_pair_1(), &xsw_pair_2(), &xsw_pair_3();
+
+// dtype, out_dtype: XSW_F32 or XSW_F64 each (the entries check that first).
+static inline const PairLaunch &pair_launch(int dtype, int out_dtype)
+{
+    static const PairLaunch &(*const pairs[4])() = {xsw_pair_0, xsw_pair_1, xsw_pair_2, xsw_pair_3};
+    return pairs[2 * (dtype == XSW_F64) + (out_dtype == XSW_F64)]();
+}

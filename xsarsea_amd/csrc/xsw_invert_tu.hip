@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 
 #include "xsw_host.hpp"
 #include "xsw_band.hpp"
@@ -164,20 +165,12 @@ static int launch_invert(xsw_ctx *c, const KArgs &A_in, int algo, const LaunchCt
 #ifndef XSW_PAIR
 #error "compile with -DXSW_PAIR=0..3"
 #endif
-#if XSW_PAIR == 0
-int xsw_launch_invert_ff(xsw_ctx *c, const KArgs &A, int algo, const LaunchCtl &lc, std::string &err) { return launch_invert<float, float>(c, A, algo, lc, err); }
-int xsw_launch_cross_ff(xsw_ctx *c, const CrossArgs &A, hipStream_t stream, std::string &err) { return launch_cross<float, float>(c, A, stream, err); }
-int xsw_launch_cost_ff(xsw_ctx *c, const CostArgs &A, bool cr, hipStream_t stream, std::string &err) { return launch_cost<float, float>(c, A, cr, stream, err); }
-#elif XSW_PAIR == 1
-int xsw_launch_invert_fd(xsw_ctx *c, const KArgs &A, int algo, const LaunchCtl &lc, std::string &err) { return launch_invert<float, double>(c, A, algo, lc, err); }
-int xsw_launch_cross_fd(xsw_ctx *c, const CrossArgs &A, hipStream_t stream, std::string &err) { return launch_cross<float, double>(c, A, stream, err); }
-int xsw_launch_cost_fd(xsw_ctx *c, const CostArgs &A, bool cr, hipStream_t stream, std::string &err) { return launch_cost<float, double>(c, A, cr, stream, err); }
-#elif XSW_PAIR == 2
-int xsw_launch_invert_df(xsw_ctx *c, const KArgs &A, int algo, const LaunchCtl &lc, std::string &err) { return launch_invert<double, float>(c, A, algo, lc, err); }
-int xsw_launch_cross_df(xsw_ctx *c, const CrossArgs &A, hipStream_t stream, std::string &err) { return launch_cross<double, float>(c, A, stream, err); }
-int xsw_launch_cost_df(xsw_ctx *c, const CostArgs &A, bool cr, hipStream_t stream, std::string &err) { return launch_cost<double, float>(c, A, cr, stream, err); }
-#else
-int xsw_launch_invert_dd(xsw_ctx *c, const KArgs &A, int algo, const LaunchCtl &lc, std::string &err) { return launch_invert<double, double>(c, A, algo, lc, err); }
-int xsw_launch_cross_dd(xsw_ctx *c, const CrossArgs &A, hipStream_t stream, std::string &err) { return launch_cross<double, double>(c, A, stream, err); }
-int xsw_launch_cost_dd(xsw_ctx *c, const CostArgs &A, bool cr, hipStream_t stream, std::string &err) { return launch_cost<double, double>(c, A, cr, stream, err); }
-#endif
+#define XSW_PAIR_NAME_(k) xsw_pair_##k
+#define XSW_PAIR_NAME(k) XSW_PAIR_NAME_(k)
+using TIn = std::conditional_t<(XSW_PAIR & 2) != 0, double, float>;
+using TOut = std::conditional_t<(XSW_PAIR & 1) != 0, double, float>;
+const PairLaunch &XSW_PAIR_NAME(XSW_PAIR)()
+{
+    static const PairLaunch pair = {launch_invert<TIn, TOut>, launch_cross<TIn, TOut>, launch_cost<TIn, TOut>};
+    return pair;
+}

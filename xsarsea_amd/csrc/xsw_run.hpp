@@ -1,22 +1,37 @@
-// Host side of the raster entry points outside xsw.hip (xsw_gradients.hip, xsw_streaks.hip): the argument checks they
+// Host side of the one-launch raster entry points (xsw.hip, xsw_gradients.hip, xsw_streaks.hip): the argument checks they
 // share (their launch grid, strip_grid, is xsw_plan.hpp's), and one call's buffers on the XSW_MEM_HOST and XSW_MEM_DEVICE routes.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "xsw_host.hpp"
 
 namespace {
 
 // Host buffers of one call: uploaded to temporaries, the launch runs on the context's stream, outputs come back, all before
-// the call returns.  Device buffers: the launch alone, asynchronous on the context's stream.
+// the call returns.  Device buffers: the launch alone, asynchronous on the context's stream.  A buffer the caller left out
+// has bytes == 0 and null pointers: its dev stays null on both routes.
 struct Buf {
     const void *host_in;  // input: host pointer to upload (nullptr for outputs)
     void *host_out;       // output: host pointer to fill (nullptr for inputs)
     size_t bytes;
     void *dev = nullptr;
 };
+static inline Buf in_buf(const void *p, size_t bytes) { return {p, nullptr, p ? bytes : 0}; }  // nullable input
+static inline Buf out_buf(void *p, size_t bytes) { return {nullptr, p, p ? bytes : 0}; }       // nullable output
+
+// launch(b) queues the kernels on the context's stream.  It returns nothing, or an XSW_* code: with a non-zero one the
+// message in c->err is the launch's own, and no output comes back.
+template <size_t N, typename Launch>
+static int launch_on(xsw_ctx *c, Buf (&b)[N], Launch &launch, const char *what)
+{
+    if constexpr (std::is_void_v<decltype(launch(b))>) launch(b);
+    else if (const int rc = launch(b)) return rc;
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? XSW_OK : fail(c, XSW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
+}
 
 template <size_t N, typename Launch>
 static int run(xsw_ctx *c, int32_t mem, Buf (&b)[N], Launch &&launch, const char *what)
@@ -24,9 +39,7 @@ static int run(xsw_ctx *c, int32_t mem, Buf (&b)[N], Launch &&launch, const char
     if (hipSetDevice(c->device) != hipSuccess) return fail(c, XSW_EHIP, "%s: hipSetDevice failed", what);
     if (mem == XSW_MEM_DEVICE) {
         for (auto &x : b) x.dev = x.host_out ? x.host_out : (void *)x.host_in;
-        launch(b);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? XSW_OK : fail(c, XSW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
+        return launch_on(c, b, launch, what);
     }
     CallTemps tmp(c->stream);
     for (auto &x : b)
@@ -34,10 +47,7 @@ static int run(xsw_ctx *c, int32_t mem, Buf (&b)[N], Launch &&launch, const char
     int rc = tmp.ok() ? XSW_OK : tmp.refused ? fail(c, XSW_ENOMEM, "%s: hipMalloc failed (%s)", what, hipGetErrorString(tmp.err))
                                              : fail(c, XSW_EHIP, "%s: upload failed (%s)", what, hipGetErrorString(tmp.err));
     hipError_t e;
-    if (!rc) {
-        launch(b);
-        if ((e = hipGetLastError()) != hipSuccess) rc = fail(c, XSW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
-    }
+    if (!rc) rc = launch_on(c, b, launch, what);
     for (auto &x : b)
         if (!rc && x.host_out && x.bytes && (e = hipMemcpyAsync(x.host_out, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
             rc = fail(c, XSW_EHIP, "%s: download failed (%s)", what, hipGetErrorString(e));

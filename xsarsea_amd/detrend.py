@@ -68,7 +68,7 @@ def sigma0_detrend(sigma0, inc_angle, wind_speed_gmf=np.array([10.0]), wind_dir_
         t = t.contiguous()
         res = torch.empty(t.shape, dtype=torch.float64, device=dev)
         if t.numel():
-            ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+            ctx = _device.context_of(dev)
             with _device.on_current_stream(ctx, dev):
                 ctx.detrend_raw(t.numel() // t.shape[-1], t.shape[-1], _device.xsw_dtype(t), _lib.XSW_F64, _lib.MEM_DEVICE,
                                 t.data_ptr(), ratio, res.data_ptr())

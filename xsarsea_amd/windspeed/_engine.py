@@ -4,7 +4,7 @@ import ctypes
 
 import numpy as np
 
-from .. import _host, _lib, options
+from .. import _device, _host, _lib, options
 from . import _plan
 
 
@@ -331,7 +331,6 @@ def _device_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc, dual_select, broadc
     arrays among them are uploaded).  Mixed dtypes (float32 sigma0 next to a float64 incidence, say): torch converts sigma0 to
     dB in sigma0's OWN dtype before anything is widened, after a scalar dsig_cr was broadcast from the LINEAR sigma0_cr.
     broadcast: the caller's own shape check (`invert_device`: torch's, whose error a shape mismatch has always raised there)."""
-    from .. import _device
     args = (inc, sigma0_co, sigma0_cr, None if np.isscalar(dsig_cr) else dsig_cr, anc)
     dev = _device.device_of(*(a for a in args if a is not None))
     t = [None if a is None else _device.as_tensor(a, dev) for a in args]
@@ -353,9 +352,8 @@ def invert_device(lut_co, lut_cr, inc, sigma0_co, sigma0_cr, dsig_cr, anc, dsig_
     bit).  Asynchronous on torch's current stream.  dual_select: ws_cr receives the fused where(|co|<5 | |dual|<5, co, dual).
     codes=True: the grid codes (int32 tensors holding the uint32 bit patterns) instead of the winds."""
     import torch
-    from .. import _device
     plan, dev, t = _device_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc, dual_select, broadcast=torch.broadcast_shapes)
-    ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    ctx = _device.context_of(dev)
     odt = torch.int32 if codes else _device.torch_dtype(plan.out_dtype)
     out_co = torch.empty(plan.shape, dtype=odt, device=dev) if plan.want_co else None
     out_cr = torch.empty(plan.shape, dtype=odt, device=dev) if plan.want_cr else None
@@ -374,7 +372,6 @@ def invert_device(lut_co, lut_cr, inc, sigma0_co, sigma0_cr, dsig_cr, anc, dsig_
 def _code_tensor(codes):
     """Grid codes in device memory as a torch tensor (zero copy): an int32 / uint32 tensor or any `__cuda_array_interface__` array."""
     import torch
-    from .. import _device
     t = _device.as_tensor(codes, _device.device_of(codes))
     if t.dtype not in (torch.int32, torch.uint32):
         raise TypeError(f"grid codes must be int32 or uint32, not {t.dtype}")
@@ -384,10 +381,9 @@ def _code_tensor(codes):
 def expand_device(lut_co, codes_co):
     """Co-pol grid codes in device memory (int32 tensor) -> the complex winds `invert_device` stores, on torch's current stream."""
     import torch
-    from .. import _device
     codes_co = _code_tensor(codes_co)
     dev = codes_co.device
-    ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    ctx = _device.context_of(dev)
     out_dtype = np.complex64 if options.device_out_dtype == "complex64" else np.complex128
     out = torch.empty(codes_co.shape, dtype=_device.torch_dtype(out_dtype), device=dev)
     if codes_co.numel():
@@ -412,54 +408,79 @@ def cross_plan(shape, inc, sigma0_co, anc, sigma0_cr, dsig_cr, *, device, dual_s
     return plan
 
 
-def cross_numpy(lut_co, lut_cr, plan, codes_co, inc, sigma0_cr, dsig_cr, dual_select=False):
-    """The cross-pol grid codes (uint32) of numpy rasters from the co-pol codes `codes_co`: `invert_numpy`'s arithmetic for the
-    cross-pol inputs (a float32 sigma0 converted to dB by numpy's own log10, a scalar dsig_cr broadcast from the LINEAR
-    sigma0), then xsw_cross_from_codes on host memory."""
-    shape, dt = plan.shape, plan.dtype
-    cast = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a), shape), dtype=dt)
-    sigma0_cr = np.asarray(sigma0_cr)
-    dsig = None
-    if plan.dsig == _plan.DSIG_FILL:
-        dsig = cast(dsig_raster(sigma0_cr, plan.dsig_fill))
-    elif plan.dsig == _plan.DSIG_RASTER:
-        dsig = cast(dsig_cr)
-    s_cr = cast(_to_db(sigma0_cr) if plan.is_db else sigma0_cr)
-    full_inc, cc = cast(inc), np.ascontiguousarray(codes_co, dtype=np.uint32)
-    out = np.empty(shape, np.uint32)
-    ctx = _lib.default_context(options.device)
-    if plan.n:
-        with ctx.lock:
-            ensure_luts(ctx, lut_co, lut_cr)
-            ctx.cross_from_codes_raw(plan.lines, plan.samples, plan.code, _lib.XSW_F64, _lib.MEM_HOST, full_inc.ctypes.data, cc.ctypes.data,
-                                     s_cr.ctypes.data, None if dsig is None else dsig.ctypes.data, out.ctypes.data, None,
-                                     dsig_cr_scalar=plan.dsig_scalar, sigma0_is_db=plan.is_db, dual_select=dual_select)
-    return out
+class _HostCodes:
+    """The kernel-ready numpy rasters of one from-codes call, [inc, sigma0, dsig_cr, anc, *codes] (None for an absent one), formed
+    with `invert_numpy`'s arithmetic: a scalar dsig_cr broadcast from the LINEAR sigma0 (`plan.dsig`), sigma0 to dB by numpy's
+    own log10 in its own dtype when the plan says so, everything then cast to `plan.dtype` (the ancillary wind: `plan.cdtype`),
+    the codes uint32.  `run` calls xsw_*_from_codes on host memory: synchronous, under the context's lock."""
+    mem = _lib.MEM_HOST
+
+    def __init__(self, plan, inc, sigma0, dsig_cr, anc, *codes):
+        cast = lambda a, t=plan.dtype: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a), plan.shape), dtype=t)
+        sigma0 = np.asarray(sigma0)
+        dsig = dsig_raster(sigma0, plan.dsig_fill) if plan.dsig == _plan.DSIG_FILL else (dsig_cr if plan.dsig == _plan.DSIG_RASTER else None)
+        self.plan, self.ctx = plan, _lib.default_context(options.device)
+        self.rasters = [cast(inc), cast(_to_db(sigma0) if plan.is_db else sigma0), cast(dsig), cast(anc, plan.cdtype)]
+        self.rasters += [np.ascontiguousarray(c, dtype=np.uint32) for c in codes]
+
+    @staticmethod
+    def at(a):
+        return None if a is None else a.ctypes.data
+
+    def empty(self, dtype=None):  # None: grid codes
+        return np.empty(self.plan.shape, np.uint32 if dtype is None else dtype)
+
+    def run(self, lut_co, lut_cr, call):
+        if self.plan.n:
+            with self.ctx.lock:
+                ensure_luts(self.ctx, lut_co, lut_cr)
+                call(self.ctx, *(self.at(x) for x in self.rasters))
 
 
-def cross_device(lut_co, lut_cr, plan, codes_co, inc, sigma0_cr, dsig_cr, dual_select=False, codes=False):
-    """`cross_numpy` for rasters resident in HBM, following `invert_device`: the cross-pol winds (select fused with dual_select)
-    or, codes=True, the cross-pol codes as an int32 tensor; asynchronous on torch's current stream."""
-    import torch
-    from .. import _device
-    codes_co = _code_tensor(codes_co)
-    dev = codes_co.device
-    t = [_device.as_tensor(inc, dev), _device.as_tensor(sigma0_cr, dev), None if np.isscalar(dsig_cr) else _device.as_tensor(dsig_cr, dev)]
-    if plan.dsig == _plan.DSIG_FILL:
-        t[2] = dsig_raster(t[1], plan.dsig_fill)
-    if plan.db_by == _plan.DB_TORCH:
-        t[1] = _device.to_db(t[1])
-    t = [_device.prep(x, plan.dtype, plan.shape) for x in t] + [codes_co.contiguous()]
-    ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
-    out = torch.empty(plan.shape, dtype=torch.int32 if codes else _device.torch_dtype(plan.out_dtype), device=dev)
-    p = _device.at
-    if plan.n:
-        with _device.on_current_stream(ctx, dev):
-            ensure_luts(ctx, lut_co, lut_cr)
-            ctx.cross_from_codes_raw(plan.lines, plan.samples, plan.code, plan.out_code, _lib.MEM_DEVICE, p(t[0]), p(t[3]), p(t[1]), p(t[2]),
-                                     p(out) if codes else None, None if codes else p(out), dsig_cr_scalar=plan.dsig_scalar,
-                                     sigma0_is_db=plan.is_db, dual_select=dual_select)
-            _device.keep_alive(t, dev)
+class _DeviceCodes:
+    """`_HostCodes` for rasters resident in HBM (host arrays among them are uploaded next to the codes), following
+    `invert_device`: torch's dB (`_device.to_db`) where the plan leaves it to torch, int32 codes.  `run` is asynchronous on
+    torch's current stream."""
+    mem = _lib.MEM_DEVICE
+    at = staticmethod(_device.at)
+
+    def __init__(self, plan, inc, sigma0, dsig_cr, anc, *codes):
+        codes = [_code_tensor(c) for c in codes]
+        dev = self.dev = codes[0].device
+        t = [None if (a is None or np.isscalar(a)) else _device.as_tensor(a, dev) for a in (inc, sigma0, dsig_cr, anc)]
+        if plan.dsig == _plan.DSIG_FILL:
+            t[2] = dsig_raster(t[1], plan.dsig_fill)
+        if plan.db_by == _plan.DB_TORCH:
+            t[1] = _device.to_db(t[1])
+        self.plan, self.ctx = plan, _device.context_of(dev)
+        self.rasters = [_device.prep(x, plan.cdtype if k == 3 else plan.dtype, plan.shape) for k, x in enumerate(t)] + [c.contiguous() for c in codes]
+
+    def empty(self, dtype=None):
+        import torch
+        return torch.empty(self.plan.shape, dtype=torch.int32 if dtype is None else _device.torch_dtype(dtype), device=self.dev)
+
+    def run(self, lut_co, lut_cr, call):
+        if self.plan.n:
+            with _device.on_current_stream(self.ctx, self.dev):
+                ensure_luts(self.ctx, lut_co, lut_cr)
+                call(self.ctx, *(self.at(x) for x in self.rasters))
+                _device.keep_alive(self.rasters, self.dev)
+
+
+def _codes_call(plan, inc, sigma0, dsig_cr, anc, *codes):
+    """The inputs of a from-codes call where the co-pol codes are: `_DeviceCodes` or `_HostCodes`."""
+    return (_DeviceCodes if _device.is_device_array(codes[0]) else _HostCodes)(plan, inc, sigma0, dsig_cr, anc, *codes)
+
+
+def cross_from_codes(lut_co, lut_cr, plan, codes_co, inc, sigma0_cr, dsig_cr, dual_select=False, codes=False):
+    """The cross-pol step from the co-pol codes `codes_co` (xsw_cross_from_codes; `plan` from `cross_plan`), numpy rasters on
+    host memory or device rasters on torch's current stream: the cross-pol winds (the select fused with dual_select) or,
+    codes=True, the cross-pol grid codes (numpy: uint32; torch: int32)."""
+    k = _codes_call(plan, inc, sigma0_cr, dsig_cr, None, codes_co)
+    out = k.empty() if codes else k.empty(plan.out_dtype)
+    k.run(lut_co, lut_cr, lambda ctx, inc, s_cr, dsig, _, cc: ctx.cross_from_codes_raw(
+        plan.lines, plan.samples, plan.code, plan.out_code, k.mem, inc, cc, s_cr, dsig, k.at(out) if codes else None,
+        None if codes else k.at(out), dsig_cr_scalar=plan.dsig_scalar, sigma0_is_db=plan.is_db, dual_select=dual_select))
     return out
 
 
@@ -472,94 +493,25 @@ def _real_code(out_dtype):
     return _lib.XSW_F32 if np.dtype(out_dtype) == np.float32 else _lib.XSW_F64
 
 
-def cost_numpy(lut_co, plan, codes_co, inc, sigma0, anc, dsig_co=0.1, parts=True, out_dtype=np.float64):
-    """[J, Jsig, Jwind, residual_db] (numpy, `out_dtype`) of the co-pol codes `codes_co` from the rasters they were computed
-    from: `invert_numpy`'s arithmetic for them (`plan` is the co-pol call's: a float32 sigma0 goes to dB by numpy's own log10),
-    then xsw_cost_from_codes on host memory."""
-    shape, dt = plan.shape, plan.dtype
-    cast = lambda a, t=dt: np.ascontiguousarray(np.broadcast_to(np.asarray(a), shape), dtype=t)
-    sigma0 = np.asarray(sigma0)
-    s_co = cast(_to_db(sigma0) if plan.is_db else sigma0)
-    full_inc, full_anc, cc = cast(inc), cast(anc, plan.cdtype), np.ascontiguousarray(codes_co, dtype=np.uint32)
-    outs = _cost_outputs(parts, lambda: np.empty(shape, out_dtype))
-    ctx = _lib.default_context(options.device)
-    if plan.n:
-        with ctx.lock:
-            ensure_luts(ctx, lut_co, None)
-            ctx.cost_from_codes_raw(plan.lines, plan.samples, plan.code, _real_code(out_dtype), _lib.MEM_HOST, full_inc.ctypes.data, cc.ctypes.data,
-                                    s_co.ctypes.data, full_anc.ctypes.data, *(None if o is None else o.ctypes.data for o in outs),
-                                    dsig_co=dsig_co, sigma0_is_db=plan.is_db)
+def cost_from_codes(lut_co, plan, codes_co, inc, sigma0, anc, dsig_co=0.1, parts=True, out_dtype=np.float64):
+    """[J, Jsig, Jwind, residual_db] (`out_dtype`; numpy, or torch for device rasters) of the co-pol codes `codes_co` from the
+    rasters they were computed from (xsw_cost_from_codes; `plan` is the co-pol call's, so the dB route is the search's)."""
+    k = _codes_call(plan, inc, sigma0, None, anc, codes_co)
+    outs = _cost_outputs(parts, lambda: k.empty(out_dtype))
+    k.run(lut_co, None, lambda ctx, inc, s_co, _, anc, cc: ctx.cost_from_codes_raw(
+        plan.lines, plan.samples, plan.code, _real_code(out_dtype), k.mem, inc, cc, s_co, anc, *(k.at(o) for o in outs),
+        dsig_co=dsig_co, sigma0_is_db=plan.is_db))
     return outs
 
 
-def cost_device(lut_co, plan, codes_co, inc, sigma0, anc, dsig_co=0.1, parts=True, out_dtype=np.float64):
-    """`cost_numpy` for rasters resident in HBM, following `invert_device`: torch tensors, asynchronous on torch's current stream."""
-    import torch
-    from .. import _device
-    codes_co = _code_tensor(codes_co)
-    dev = codes_co.device
-    t = [_device.as_tensor(inc, dev), _device.as_tensor(sigma0, dev), _device.as_tensor(anc, dev)]
-    if plan.db_by == _plan.DB_TORCH:
-        t[1] = _device.to_db(t[1])
-    t = [_device.prep(x, plan.cdtype if k == 2 else plan.dtype, plan.shape) for k, x in enumerate(t)] + [codes_co.contiguous()]
-    ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
-    outs = _cost_outputs(parts, lambda: torch.empty(plan.shape, dtype=_device.torch_dtype(out_dtype), device=dev))
-    p = _device.at
-    if plan.n:
-        with _device.on_current_stream(ctx, dev):
-            ensure_luts(ctx, lut_co, None)
-            ctx.cost_from_codes_raw(plan.lines, plan.samples, plan.code, _real_code(out_dtype), _lib.MEM_DEVICE, p(t[0]), p(t[3]), p(t[1]), p(t[2]),
-                                    *(p(o) for o in outs), dsig_co=dsig_co, sigma0_is_db=plan.is_db)
-            _device.keep_alive(t, dev)
-    return outs
-
-
-def cost_cr_numpy(lut_co, lut_cr, plan, codes_co, codes_cr, inc, sigma0_cr, dsig_cr, parts=True, out_dtype=np.float64):
-    """[J, Jsig, Jwind, residual_db] of the cross-pol codes `codes_cr` (from `cross_numpy`, with or without the select): the
-    cross-pol inputs formed as `cross_numpy` forms them (`plan` from `cross_plan`), then xsw_cost_cr_from_codes on host memory."""
-    shape, dt = plan.shape, plan.dtype
-    cast = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a), shape), dtype=dt)
-    sigma0_cr = np.asarray(sigma0_cr)
-    dsig = None
-    if plan.dsig == _plan.DSIG_FILL:
-        dsig = cast(dsig_raster(sigma0_cr, plan.dsig_fill))
-    elif plan.dsig == _plan.DSIG_RASTER:
-        dsig = cast(dsig_cr)
-    s_cr = cast(_to_db(sigma0_cr) if plan.is_db else sigma0_cr)
-    full_inc = cast(inc)
-    cc, ccr = np.ascontiguousarray(codes_co, dtype=np.uint32), np.ascontiguousarray(codes_cr, dtype=np.uint32)
-    outs = _cost_outputs(parts, lambda: np.empty(shape, out_dtype))
-    ctx = _lib.default_context(options.device)
-    if plan.n:
-        with ctx.lock:
-            ensure_luts(ctx, lut_co, lut_cr)
-            ctx.cost_cr_from_codes_raw(plan.lines, plan.samples, plan.code, _real_code(out_dtype), _lib.MEM_HOST, full_inc.ctypes.data, cc.ctypes.data,
-                                       ccr.ctypes.data, s_cr.ctypes.data, None if dsig is None else dsig.ctypes.data,
-                                       *(None if o is None else o.ctypes.data for o in outs), dsig_cr_scalar=plan.dsig_scalar, sigma0_is_db=plan.is_db)
-    return outs
-
-
-def cost_cr_device(lut_co, lut_cr, plan, codes_co, codes_cr, inc, sigma0_cr, dsig_cr, parts=True, out_dtype=np.float64):
-    """`cost_cr_numpy` for rasters resident in HBM, following `cross_device`; asynchronous on torch's current stream."""
-    import torch
-    from .. import _device
-    codes_co, codes_cr = _code_tensor(codes_co), _code_tensor(codes_cr)
-    dev = codes_co.device
-    t = [_device.as_tensor(inc, dev), _device.as_tensor(sigma0_cr, dev), None if np.isscalar(dsig_cr) else _device.as_tensor(dsig_cr, dev)]
-    if plan.dsig == _plan.DSIG_FILL:
-        t[2] = dsig_raster(t[1], plan.dsig_fill)
-    if plan.db_by == _plan.DB_TORCH:
-        t[1] = _device.to_db(t[1])
-    t = [_device.prep(x, plan.dtype, plan.shape) for x in t] + [codes_co.contiguous(), codes_cr.contiguous()]
-    ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
-    outs = _cost_outputs(parts, lambda: torch.empty(plan.shape, dtype=_device.torch_dtype(out_dtype), device=dev))
-    p = _device.at
-    if plan.n:
-        with _device.on_current_stream(ctx, dev):
-            ensure_luts(ctx, lut_co, lut_cr)
-            ctx.cost_cr_from_codes_raw(plan.lines, plan.samples, plan.code, _real_code(out_dtype), _lib.MEM_DEVICE, p(t[0]), p(t[3]), p(t[4]), p(t[1]),
-                                       p(t[2]), *(p(o) for o in outs), dsig_cr_scalar=plan.dsig_scalar, sigma0_is_db=plan.is_db)
-            _device.keep_alive(t, dev)
+def cost_cr_from_codes(lut_co, lut_cr, plan, codes_co, codes_cr, inc, sigma0_cr, dsig_cr, parts=True, out_dtype=np.float64):
+    """[J, Jsig, Jwind, residual_db] of the cross-pol codes `codes_cr` (from `cross_from_codes`, with or without the select): the
+    cross-pol inputs formed as that call forms them (`plan` from `cross_plan`), then xsw_cost_cr_from_codes."""
+    k = _codes_call(plan, inc, sigma0_cr, dsig_cr, None, codes_co, codes_cr)
+    outs = _cost_outputs(parts, lambda: k.empty(out_dtype))
+    k.run(lut_co, lut_cr, lambda ctx, inc, s_cr, dsig, _, cc, ccr: ctx.cost_cr_from_codes_raw(
+        plan.lines, plan.samples, plan.code, _real_code(out_dtype), k.mem, inc, cc, ccr, s_cr, dsig, *(k.at(o) for o in outs),
+        dsig_cr_scalar=plan.dsig_scalar, sigma0_is_db=plan.is_db))
     return outs
 
 
@@ -568,7 +520,6 @@ def _uploaded_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc):
     With host dB the linear sigma0 stays on the host -- `src` {STAGE_*: flat raster}, converted piece by piece on its way up,
     its tensors None -- and a scalar dsig_cr's raster is formed whole, in sigma0's own dtype, and uploaded."""
     import torch
-    from .. import _device
     h = [None if a is None or np.isscalar(a) else np.asarray(a) for a in (inc, sigma0_co, sigma0_cr, dsig_cr, anc)]
     plan = _plan.CallPlan(*(dsig_cr if (k == 3 and x is None) else _plan.meta(x) for k, x in enumerate(h)), device=False, coded=True)
     dev = torch.device("cuda", int(options.device))
@@ -597,12 +548,12 @@ def invert_coded(lut_co, lut_cr, inc, sigma0_co, sigma0_cr, dsig_cr, anc, dsig_c
     are already resident (XSW_MEM_DEVICE_SIGMA0_HOST) -- and a scalar `dsig_cr` is broadcast from the LINEAR sigma0
     (windspeed.py:122-123).  Device rasters follow `invert_device` (sigma0 -> dB fused, the dual-pol select fused)."""
     import torch
-    from .. import _device, multi_gpu
+    from .. import multi_gpu
     if _device.any_device_array(inc, sigma0_co, sigma0_cr, dsig_cr, anc):
         (plan, dev, t), src = _device_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc, dual_select), {}
     else:
         plan, dev, t, src = _uploaded_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc)
-    ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    ctx = _device.context_of(dev)
     sink.begin(plan.shape, plan.want_co, plan.want_cr, dev, _device.torch_dtype(plan.out_dtype))
     with ctx.lock:
         ensure_luts(ctx, lut_co if plan.want_co else None, lut_cr if plan.want_cr else None)  # (also on a rank whose tile is empty: it may expand)

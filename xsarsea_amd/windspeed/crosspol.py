@@ -96,16 +96,36 @@ class CopolCodes:
         the cross-pol wind before the select of windspeed.py:426-428.  codes=True: the cross-pol grid codes instead
         (include/xsw.h, out_code_cr; the select, when asked for, is the kernel's and sets XSW_CODE_PICK_CO).  ValueError for a
         shape, container or dtype mismatch with the co-pol call (module docstring), before any device call."""
-        scalar = np.isscalar(dsig_cr)
-        _refuse_containers("CopolCodes.dual", sigma0_dual, None if scalar else dsig_cr)
-        if sigma0_dual is None:
-            raise ValueError("sigma0_dual is missing")
-        for name, v in (("sigma0_dual", sigma0_dual), ("dsig_cr", None if scalar else dsig_cr)):
+        plan, lut_cr = self._cross_step("CopolCodes.dual", sigma0_dual, dsig_cr, model, kwargs, dual_select=dual_select)
+        run = lambda **kw: _engine.cross_from_codes(self.lut_co, lut_cr, plan, self.codes, self.inc, sigma0_dual, dsig_cr, **kw)
+        if self.on_device or codes:  # device rasters: the select fused into the kernel, as `invert_device` does
+            return run(dual_select=dual_select, codes=codes)
+        # numpy rasters: codes over PCIe, expanded on the host, the select with numpy's own abs (as `invert_from_model` does)
+        ws_co, ws_cr = _engine.expand_codes(self.lut_co, lut_cr, self.codes, run(codes=True))
+        return _engine.dual_select(ws_co, ws_cr) if dual_select else ws_cr
+
+    def _same_kind(self, **arrays):
+        for name, v in arrays.items():
             if v is not None and _device.is_device_array(v) != self.on_device:
                 raise ValueError(f"{name} is a {'device' if not self.on_device else 'host'} array but the co-pol codes are in "
                                  f"{'device' if self.on_device else 'host'} memory: one container kind per CopolCodes")
+
+    def _cross_step(self, who, sigma0_dual, dsig_cr, model, kwargs, dual_select=False, **codes):
+        """(plan, lut_cr) of a cross-pol step from these codes, after every refusal `dual` and `cost_dual` share (**codes:
+        `cost_dual`'s codes_cr, held to the co-pol codes' shape and container kind); nothing here touches the device."""
+        dsig = None if np.isscalar(dsig_cr) else dsig_cr
+        _refuse_containers(who, sigma0_dual, *codes.values(), dsig)
+        if any(v is None for v in (sigma0_dual, *codes.values())):
+            raise ValueError(" and ".join(["sigma0_dual", *codes]) + (" are both needed" if codes else " is missing"))
+        self._same_kind(sigma0_dual=sigma0_dual, **codes, dsig_cr=dsig)
+        for name, v in codes.items():
+            cm = _codes_meta(v)
+            if np.dtype(cm[1]) not in (np.dtype(np.uint32), np.dtype(np.int32)):
+                raise TypeError(f"{name} must be uint32 or int32 grid codes, not {np.dtype(cm[1]).name}")
+            if tuple(cm[0]) != self.shape:
+                raise ValueError(f"{name} has shape {tuple(cm[0])}, the co-pol codes have shape {self.shape}")
         plan = _engine.cross_plan(self.shape, self.inc_meta, self.sigma0_meta, self.ancillary_meta, _meta(sigma0_dual),
-                                  dsig_cr if scalar else _meta(dsig_cr), device=self.on_device, dual_select=dual_select)
+                                  dsig_cr if dsig is None else _meta(dsig), device=self.on_device, dual_select=dual_select)
         mono = _plan.CallPlan(self.inc_meta, self.sigma0_meta, None, None, self.ancillary_meta, device=self.on_device)
         if (mono.dtype, mono.db_by) != (plan.dtype, plan.db_by):
             raise ValueError(f"the dtypes of sigma0_dual / dsig_cr would make the fused dual-pol call compute its co-pol step in "
@@ -114,22 +134,7 @@ class CopolCodes:
         m = get_model(model)
         if not m.iscrosspol:
             raise ValueError(f"model {m.name} ({m.pol}) is not a cross-pol model")
-        lut_cr = _engine.lut_source(m, kwargs)
-        if self.on_device:  # the select fused into the kernel, as `invert_device` does
-            return _engine.cross_device(self.lut_co, lut_cr, plan, self.codes, self.inc, sigma0_dual, dsig_cr, dual_select=dual_select, codes=codes)
-        if codes:
-            return _engine.cross_numpy(self.lut_co, lut_cr, plan, self.codes, self.inc, sigma0_dual, dsig_cr, dual_select=dual_select)
-        # numpy rasters: codes over PCIe, expanded on the host, the select with numpy's own abs (as `invert_from_model` does)
-        codes_cr = _engine.cross_numpy(self.lut_co, lut_cr, plan, self.codes, self.inc, sigma0_dual, dsig_cr)
-        ws_co, ws_cr = _engine.expand_codes(self.lut_co, lut_cr, self.codes, codes_cr)
-        return _engine.dual_select(ws_co, ws_cr) if dual_select else ws_cr
-
-
-    def _same_kind(self, **arrays):
-        for name, v in arrays.items():
-            if v is not None and _device.is_device_array(v) != self.on_device:
-                raise ValueError(f"{name} is a {'device' if not self.on_device else 'host'} array but the co-pol codes are in "
-                                 f"{'device' if self.on_device else 'host'} memory: one container kind per CopolCodes")
+        return plan, _engine.lut_source(m, kwargs)
 
     def cost(self, sigma0, ancillary_wind, dsig_co=None, parts=True, out_dtype=None):
         """The cost the co-pol search minimised, at its minimum: `InversionCost` with J = Jwind + Jsig of windspeed.py:216-225 at
@@ -156,39 +161,17 @@ class CopolCodes:
             dsig_co = 0.1 if self.dsig_co is None else self.dsig_co
         if not np.isscalar(dsig_co) or not float(dsig_co) == float(dsig_co) or float(dsig_co) == 0.0:
             raise ValueError(f"dsig_co must be a scalar other than 0 and NaN, not {dsig_co!r}")
-        run = _engine.cost_device if self.on_device else _engine.cost_numpy
-        return InversionCost(*run(self.lut_co, plan, self.codes, self.inc, sigma0, ancillary_wind, dsig_co=float(dsig_co), parts=parts,
-                                  out_dtype=_real_dtype(out_dtype)))
+        return InversionCost(*_engine.cost_from_codes(self.lut_co, plan, self.codes, self.inc, sigma0, ancillary_wind, dsig_co=float(dsig_co),
+                                                      parts=parts, out_dtype=_real_dtype(out_dtype)))
 
     def cost_dual(self, sigma0_dual, codes_cr, dsig_cr=0.1, model=None, parts=True, out_dtype=None, **kwargs):
         """The cost the cross-pol search of `.dual(sigma0_dual, dsig_cr=..., model=..., **kwargs)` minimised, at its minimum:
         `InversionCost` with J = Jsig_cr [+ Jwind_cr] of windspeed.py:257-264 (Jwind NaN and J = Jsig where there is no co-pol
         wind).  codes_cr: what `.dual(..., codes=True)` returned, with or without dual_select (the select does not enter the
         cost).  The same refusals as `.dual`, before any device call."""
-        scalar = np.isscalar(dsig_cr)
-        _refuse_containers("CopolCodes.cost_dual", sigma0_dual, codes_cr, None if scalar else dsig_cr)
-        if sigma0_dual is None or codes_cr is None:
-            raise ValueError("sigma0_dual and codes_cr are both needed")
-        self._same_kind(sigma0_dual=sigma0_dual, codes_cr=codes_cr, dsig_cr=None if scalar else dsig_cr)
-        cm = _codes_meta(codes_cr)
-        if np.dtype(cm[1]) not in (np.dtype(np.uint32), np.dtype(np.int32)):
-            raise TypeError(f"codes_cr must be uint32 or int32 grid codes, not {np.dtype(cm[1]).name}")
-        if tuple(cm[0]) != self.shape:
-            raise ValueError(f"codes_cr has shape {tuple(cm[0])}, the co-pol codes have shape {self.shape}")
-        plan = _engine.cross_plan(self.shape, self.inc_meta, self.sigma0_meta, self.ancillary_meta, _meta(sigma0_dual),
-                                  dsig_cr if scalar else _meta(dsig_cr), device=self.on_device)
-        mono = _plan.CallPlan(self.inc_meta, self.sigma0_meta, None, None, self.ancillary_meta, device=self.on_device)
-        if (mono.dtype, mono.db_by) != (plan.dtype, plan.db_by):
-            raise ValueError(f"the dtypes of sigma0_dual / dsig_cr would make the fused dual-pol call compute in {np.dtype(plan.dtype).name} "
-                             f"with sigma0 in dB by {plan.db_by}, but the stored codes were computed in {np.dtype(mono.dtype).name} with dB by "
-                             f"{mono.db_by}: pass cross-pol rasters of the co-pol rasters' dtype")
-        m = get_model(model)
-        if not m.iscrosspol:
-            raise ValueError(f"model {m.name} ({m.pol}) is not a cross-pol model")
-        lut_cr = _engine.lut_source(m, kwargs)
-        run = _engine.cost_cr_device if self.on_device else _engine.cost_cr_numpy
-        return InversionCost(*run(self.lut_co, lut_cr, plan, self.codes, codes_cr, self.inc, sigma0_dual, dsig_cr, parts=parts,
-                                  out_dtype=_real_dtype(out_dtype)))
+        plan, lut_cr = self._cross_step("CopolCodes.cost_dual", sigma0_dual, dsig_cr, model, kwargs, codes_cr=codes_cr)
+        return InversionCost(*_engine.cost_cr_from_codes(self.lut_co, lut_cr, plan, self.codes, codes_cr, self.inc, sigma0_dual, dsig_cr,
+                                                         parts=parts, out_dtype=_real_dtype(out_dtype)))
 
 
 def invert_copol_codes(inc, sigma0, /, ancillary_wind=None, dsig_co=0.1, model=None, **kwargs):

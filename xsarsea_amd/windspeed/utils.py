@@ -48,10 +48,9 @@ def _shape_of(a):
 
 def _device_call(arrays):
     """(device, context) of a call whose arguments hold a device array."""
-    import torch
-    from .. import _device, _lib
+    from .. import _device
     dev = _device.device_of(*arrays)
-    return dev, _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+    return dev, _device.context_of(dev)
 
 
 def _get_dsig_wspd_device(name, U_crosspol, SNR_cr):
@@ -183,7 +182,7 @@ def nesz_flattening(noise, inc):
         t_n, t_i = t_n.to(dt).contiguous(), t_i.to(dt).expand(t_n.shape).contiguous()
         out = torch.empty(t_n.shape, dtype=torch.float64, device=dev)
         if t_n.numel():
-            ctx = _lib.default_context(dev.index if dev.index is not None else torch.cuda.current_device())
+            ctx = _device.context_of(dev)
             with _device.on_current_stream(ctx, dev):
                 ctx.nesz_flatten_raw(t_n.shape[0], t_n.shape[1], _device.xsw_dtype(t_n), _lib.MEM_DEVICE, t_n.data_ptr(), t_i.data_ptr(),
                                      out.data_ptr())
