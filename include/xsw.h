@@ -194,7 +194,9 @@ int xsw_lut_upload(xsw_ctx *ctx, const xsw_lut *co, const xsw_lut *cr);
  * allocated the one-kernel path runs; any other LUT, and XSW_ALGO_EXACT, take the general kernel (k_invert).
  * Results do not depend on the route.  Environment switches for A/B measurements and the tests of every route: XSW_LONG_RUN=0
  * (no k_invert_band2), XSW_NO_BLOCKS_KERNEL=1, XSW_NO_BAND=1 (general kernel only), XSW_NO_RECORDS=1, XSW_NO_STRIP_MASKS=1,
- * XSW_B2_REFINE_MIN / XSW_B2_AREA / XSW_B2_ROWS_MAX / XSW_TAIL_SWEEP (routing thresholds: INTEGRATION.md). */
+ * XSW_B2_REFINE_MIN / XSW_B2_AREA / XSW_B2_ROWS_MAX / XSW_TAIL_SWEEP (routing thresholds), XSW_LIST_CAP_TEST / XSW_FAIL_LIST_ALLOC
+ * (tiny work lists / none): the table is in INTEGRATION.md, the switches and what follows from them in csrc/xsw_plan.hpp
+ * (RouteKnobs, ChainPlan). */
 int xsw_invert(xsw_ctx *ctx, const xsw_invert_args *args);
 
 /* Grid codes -> complex winds (the store of __invert_from_model_1d: wind_co = wspd * exp(1j * deg2rad(+-phi)) :235-247,

@@ -487,13 +487,12 @@ static int dispatch_invert(xsw_ctx *c, const KArgs &A, int dtype, int out_dtype,
 // Work lists of the device-raster path (capacities: xsw_plan.hpp).  A failed allocation selects the one-kernel path.
 static void ensure_list(xsw_ctx *c, long long n, long long lines)
 {
-    static const long long test_cap = env_int("XSW_LIST_CAP_TEST", 0, 16);  // tests: a tiny capacity, so that the overflow route runs
-    const size_t want = context_list_cap(n, test_cap), want_strips = strips_for(n, lines);
+    const RouteKnobs &knobs = route_knobs();  // list_cap_test, fail_list_alloc: the tests' overflow and allocation-failure routes
+    const size_t want = context_list_cap(n, knobs.list_cap_test), want_strips = strips_for(n, lines);
     if (want <= c->lists.list_cap && want_strips <= c->lists.mask_strips) return;
     (void)hipStreamSynchronize(c->stream);  // the old lists may still be in use
-    static const bool no_list = env_flag("XSW_FAIL_LIST_ALLOC");  // tests: the allocation-failure route
     c->lists.list_cap = c->lists.mask_strips = 0;  // (no lists: the one-kernel path)
-    if (grow(c->lists.base, c->lists_bytes, no_list ? 0 : WorkLists{nullptr, want, want_strips}.bytes()) != hipSuccess) (void)hipGetLastError();
+    if (grow(c->lists.base, c->lists_bytes, knobs.fail_list_alloc ? 0 : WorkLists{nullptr, want, want_strips}.bytes()) != hipSuccess) (void)hipGetLastError();
     if (c->lists.base) { c->lists.list_cap = want; c->lists.mask_strips = want_strips; }
 }
 

@@ -72,11 +72,6 @@ namespace xsw {
 #ifndef XSW_SWEEP_MAX
 #define XSW_SWEEP_MAX 128        // rows a direction may hold in k_invert_band2's batched sweep before the pixel is left to k_invert_list
 #endif
-#ifndef XSW_TAIL_SWEEP
-#define XSW_TAIL_SWEEP 256  // rows past the monotone ones a window may hold for k_invert_band2's tail sweep (KArgs::tail_max; 0: off;
-                            // environment XSW_TAIL_SWEEP).  Measured (Mpx/s, 0 / 96 / 192 / 400 rows): a-priori x 1.6 1107 / 1186 / 1193 / 1191,
-                            // x 2.5 252 / 331 / 394 / 396, incidence 17..33 deg x 1.6 421 / 473 / 570 / 560, 17..25 deg 2460 / 2654 / 2612 / 2651
-#endif
 #ifndef XSW_B2_HARD_AREA
 #define XSW_B2_HARD_AREA 256  // band candidates (run x directions) from which a handed pixel is marked for k_invert_band2's refinement
 #endif

@@ -48,9 +48,6 @@ namespace xsw {
 #ifndef XSW_JOINT_ROUNDS_EASY
 #define XSW_JOINT_ROUNDS_EASY 0  // joint-shrink rounds of the waves that are not refined (band and chord of the record's own bound only)
 #endif
-#ifndef XSW_B2_ROWS_MAX
-#define XSW_B2_ROWS_MAX 4096  // rows (candidates) the live arc may hold after step B: beyond, the pixel is k_invert_blocks's (environment XSW_B2_ROWS_MAX)
-#endif
 
 struct Band2Slot {  // 56 bytes per pixel in LDS, read by every lane of its segment (broadcast)
     double s, ah, bh, jub;

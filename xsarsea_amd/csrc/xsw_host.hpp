@@ -89,14 +89,14 @@ static inline int fail(xsw_ctx *c, int code, const char *fmt, ...)
     return code;
 }
 
-// Environment knobs (experiments, A/B measurements, the tests' forced routes).  A caller keeps the value in a function-local
-// static, so a knob is read once per process.  env_int: the variable's integer clamped to [lo, hi], or dflt when it is unset.
-static inline long long env_int(const char *name, long long dflt, long long lo = LLONG_MIN, long long hi = LLONG_MAX)
+// Environment knobs: env_int / env_flag (xsw_plan.hpp).  A caller keeps the value in a function-local static, so a knob is read
+// once per process.  The switches that shape an inversion are read together, on their first use by an inversion launch
+// (launch_invert, ensure_list); not `static inline`: one copy for the whole library, not one per translation unit.
+inline const RouteKnobs &route_knobs()
 {
-    const char *v = getenv(name);
-    return v ? std::min(std::max(atoll(v), lo), hi) : dflt;
+    static const RouteKnobs k = RouteKnobs::from_env();
+    return k;
 }
-static inline bool env_flag(const char *name) { return getenv(name) != nullptr; }
 
 // ---- device memory.  Two patterns, each spelled once: a sequence of allocations and stream operations whose first error
 // sticks (DevSeq; CallTemps is one that owns what it allocates), and a buffer that is kept and replaced by a larger one (grow).
@@ -181,6 +181,24 @@ struct LaunchCtl {
     bool timing;      // xsw_timing_enable events (context stream only)
     WorkLists lists;  // base == nullptr: one-kernel path
 };
+
+// What launch_invert's route plan (ChainPlan, xsw_plan.hpp) reads of the tables, the call and its work lists.
+static_assert(RouteFacts::PRUNED == XSW_ALGO_PRUNED && RouteFacts::EXHAUSTIVE == XSW_ALGO_EXHAUSTIVE && RouteFacts::EXACT == XSW_ALGO_EXACT &&
+              RouteFacts::EXHAUSTIVE_F64 == XSW_ALGO_EXHAUSTIVE_F64, "RouteFacts::Algo (xsw_plan.hpp) is XSW_ALGO_*");
+static inline RouteFacts route_facts(const xsw::DevTables &T, const xsw::KArgs &A, int algo, const LaunchCtl &lc)
+{
+    RouteFacts f;
+    f.prunable = T.prunable; f.co_off32 = T.co_off32; f.band_mul24 = T.band_mul24; f.cr_monotone = T.cr_monotone; f.blk_span_ok = T.blk_span_ok;
+    f.mono_rows = T.mono_rows; f.inv_rows = T.inv_rows; f.blk = T.blk; f.csphi32 = T.csphi32; f.tail_min = T.tail_min;
+    f.n_w = T.n_w; f.n_phi = T.n_phi;
+    f.lines = A.lines; f.samples = A.samples; f.n = A.n;
+    f.algo = algo;
+    f.s_co = A.s_co; f.s_cr = A.s_cr;
+    f.mono = !A.s_cr && !A.out_cr && !A.code_cr;
+    f.stats = A.stats; f.stats_chain = A.stats_chain;
+    f.lists = lc.lists.base; f.mask_strips = lc.lists.mask_strips;
+    return f;
+}
 
 // A for one chunk of its raster: the chunk's shape, and every raster pointer that is set moved to the chunk's first pixel
 // (es: bytes of an input element, os: of an output pixel).
