@@ -114,6 +114,8 @@ def test_statistics_instantiation_counts_per_pixel(ctx_default):
 _ROUTE_SCRIPT = r"""
 import sys, numpy as np
 sys.path.insert(0, {repo!r}); sys.path.insert(0, {repo!r} + "/tests")
+if {device!r}:
+    import torch  # (before libxsw.so is loaded: seconds faster than after it)
 from oracle import lut as olut
 from util import lut_dicts, bits_equal
 from test_gpu_band_pool import _classes_scene
@@ -121,11 +123,27 @@ from xsarsea_amd import _lib
 co, _ = lut_dicts(olut.to_lut("gmf_cmod5n"), None)
 ctx = _lib.Context(0)
 ctx.upload_luts(co=co)
-for lines, samples, seed in ((39, 333, 3), (6, 900, 4)):
+# (the overflow routes: rasters of some 40 000 pixels -- a tenth of such a scene is k_invert_band2's, and list B holds 1200)
+for lines, samples, seed in (((119, 333, 3), (14, 2500, 4)) if {device!r} else ((39, 333, 3), (6, 900, 4))):
     inc, s_vv, anc = _classes_scene(lines, samples, seed)
-    got = ctx.invert_host(inc, sigma0_co=s_vv, anc=anc, algo="pruned", want_idx=True)
+    if {device!r}:  # device rasters: the context's own work lists, the only ones XSW_LIST_CAP_TEST shrinks (host rasters go through the workers' lists)
+        dev = torch.device("cuda", 0)
+        t = [torch.from_numpy(a).to(dev) for a in (inc, s_vv, anc)]
+        out = torch.empty(inc.shape, dtype=torch.complex128, device=dev)
+        idx = torch.empty(inc.shape + (3,), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        ctx.timing_enable(True)
+        ctx.invert_raw(lines, samples, _lib.XSW_F64, _lib.XSW_F64, _lib.MEM_DEVICE, t[0].data_ptr(), t[1].data_ptr(), None, None, t[2].data_ptr(),
+                       out.data_ptr(), None, out_idx=idx.data_ptr(), algo=_lib.ALGO_PRUNED)
+        tm = ctx.timing()
+        ctx.timing_enable(False)
+        got = (out.cpu().numpy(), None, idx.cpu().numpy())
+        handed = (tm["last_list_pixels"], tm["last_band2_pixels"], tm["last_blocks_pixels"])
+    else:
+        got = ctx.invert_host(inc, sigma0_co=s_vv, anc=anc, algo="pruned", want_idx=True)
+        handed = (-1, -1, -1)
     ex = ctx.invert_host(inc, sigma0_co=s_vv, anc=anc, algo="exhaustive", want_idx=True)
-    print("RESULT", lines, samples, int(bits_equal(got[0], ex[0]) and np.array_equal(got[2], ex[2])))
+    print("RESULT", lines, samples, int(bits_equal(got[0], ex[0]) and np.array_equal(got[2], ex[2])), *handed)
 """
 
 
@@ -133,7 +151,12 @@ for lines, samples, seed in ((39, 333, 3), (6, 900, 4)):
 def test_hand_over_routes(route):
     """The hand-over routes of k_invert_band forced, in a fresh process (the switches are read once): every eligible pixel to
     k_invert_band2 / none, overflowing lists (strip masks, and without them), the stage-1 live arc always / never, list B as
-    indices -- on heights that leave partial workgroups."""
+    indices -- on heights that leave partial workgroups.  The two overflow routes invert device rasters (the context's lists are
+    the ones XSW_LIST_CAP_TEST shrinks to 300 entries for list G and 4 x 300 each for lists B and C; on host rasters the workers'
+    lists of 16384 entries or more never overflowed, whatever the variable said) and show from the lists' counters that list B
+    overflowed.  With 300 entries the 39 x 333 scene of the other routes hands 1007 pixels to k_invert_band2, 100 to k_invert_blocks
+    and none to k_invert_list: nothing overflows there either, hence the larger rasters (heights 119 and 14: partial workgroups
+    all the same).  An overflowing list G: tests/test_gpu_route_geometry.py, cap64."""
     env = {k: v for k, v in os.environ.items() if not k.startswith("XSW_")}
     env.update({"long-run-1": {"XSW_LONG_RUN": "1"}, "long-run-0": {"XSW_LONG_RUN": "0"}, "list-300": {"XSW_LIST_CAP_TEST": "300"},
                 "arc-always": {"XSW_ARC_MIN": "8", "XSW_ARC_CROWD": "1"}, "arc-never": {"XSW_ARC_MIN": "0"},
@@ -141,9 +164,13 @@ def test_hand_over_routes(route):
                 "no-masks-300": {"XSW_LIST_CAP_TEST": "300", "XSW_NO_STRIP_MASKS": "1"}}[route])
     if "XSW_LIB" in os.environ:
         env["XSW_LIB"] = os.environ["XSW_LIB"]
-    r = subprocess.run([sys.executable, "-c", _ROUTE_SCRIPT.format(repo=REPO)], env=env, capture_output=True, text=True, timeout=600)
+    overflow = route in ("list-300", "no-masks-300")
+    r = subprocess.run([sys.executable, "-c", _ROUTE_SCRIPT.format(repo=REPO, device=overflow)], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     rows = [l.split() for l in r.stdout.splitlines() if l.startswith("RESULT")]
     assert len(rows) == 2
-    for _, lines, samples, ok in rows:
+    for _, lines, samples, ok, n_g, n_b, n_c in rows:
         assert ok == "1", (route, lines, samples)
+        print(route, lines, samples, "handed to k_invert_list / k_invert_band2 / k_invert_blocks:", n_g, n_b, n_c)
+        if overflow:
+            assert int(n_b) > 4 * 300, (route, lines, samples, "list B did not overflow", n_g, n_b, n_c)

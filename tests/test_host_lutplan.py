@@ -343,6 +343,34 @@ def test_scalars_and_flags_at_the_gates(ask):
     assert flag(5)[38:] == [0, 0, 1, 1, 1]  # phi_180: 180 - span < 2
 
 
+def test_flags_of_the_route_geometries(ask):
+    """The seven LUT shapes of tests/route_geometry.py are there for the flags below (tests/test_gpu_route_geometry.py forces every
+    inversion route on each of them): a later change of the pads or of the block sizes must fail here instead of quietly leaving
+    the GPU test with seven controls.  All of them run the chain (prunable, band_mul24, co_off32)."""
+    import route_geometry as rg
+    #                 phi_pad % 8, phi_180, blk_span_ok, cell_span_ok, block columns
+    want = {"pad4_half": (4, 1, 1, 1, 5),      # misaligned odd rows of inv_rows
+            "pad4_full": (4, 1, 1, 1, 10),     # ... on a full circle: phi_180 all the same (180 - span < 2, the reference's rule)
+            "open_half": (4, 0, 1, 1, 5),      # 0..175 degrees: phi_180 == 0 needs a span below 178
+            "narrow": (4, 1, 0, 0, 1),         # 12 directions 16.4 degrees apart: one block column, and 15 steps span 245 degrees
+            "coarse_full": (4, 1, 0, 0, 2),    # 15 degree steps: no k_invert_blocks
+            "tail": (4, 1, 1, 1, 5),
+            "default_like": (0, 1, 1, 1, 12)}  # the control
+    assert list(want) == list(rg.GEOMETRIES)
+    axes = {}
+    for name in want:
+        lco, _ = rg.build_luts(name)
+        axes[name] = (lco.incidence, lco.wspd, lco.phi)
+    got = check_scalars(ask, [axes[name] + (1, 1) for name in want])
+    for (name, w), g in zip(want.items(), got):
+        geo = rg.GEOMETRIES[name]
+        assert g[:3] == [geo["n_inc"], geo["n_w"], geo["n_phi"]], name
+        assert (g[3] % 8, g[5], g[17], g[12], g[14]) == w, (name, g[:19])
+        assert g[6] == 1 and g[8] == 1 and g[7] == 1, (name, "prunable, band_mul24, co_off32", g[:19])
+    assert got[1][4] != got[1][1]  # pad4_full: w_pad != n_w
+    assert rg.GEOMETRIES["pad4_full"]["n_wcr"] % 4 != 0
+
+
 def p_host_tables(w, phi, cos_phi=None, sin_phi=None, out_dir=None, abs_co=None, dual_dir=None):
     """xsw.hip:478-542 restated; math.cos / sin / atan2 are the C library's, as the defaults are; hypot is taken from libm itself
     (CPython's math.hypot has been its own algorithm since 3.8 and differs from libm's in the last bit)."""
