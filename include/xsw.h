@@ -278,6 +278,54 @@ int xsw_cost_cr_from_codes(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t
                            const void *sigma0_cr, const void *dsig_cr, double dsig_cr_scalar, void *out_J, void *out_Jsig,
                            void *out_Jwind, void *out_residual);
 
+/* Additive to XSW_VERSION 4.  The WIDTH of the minimum the co-pol search found, from its stored codes: the error bars of the
+ * retrieved wind.  J_co (windspeed.py:216-225) is a Bayesian cost, the posterior is ~ exp(-J / 2), so near the minimum the
+ * covariance of (wind speed, direction) is 2 H^-1 with H the Hessian of J.  H is taken by second differences over the 3 x 3
+ * grid points around (iw, ip), the point the code names; J[k][l] is the cost at (iw + k, ip + l), evaluated exactly as
+ * xsw_cost_from_codes evaluates it (each is an element of the reference's dense J_co, bit for bit), and the spacings are the
+ * LUT axes' own (hw- = w[iw] - w[iw-1], hw+ = w[iw+1] - w[iw], hp-, hp+ likewise in degrees; the axes may be non-uniform):
+ *   Jww = 2 ((J[1][0] - J[0][0]) / hw+ + (J[-1][0] - J[0][0]) / hw-) / (hw+ + hw-)
+ *   Jpp = 2 ((J[0][1] - J[0][0]) / hp+ + (J[0][-1] - J[0][0]) / hp-) / (hp+ + hp-)
+ *   Jwp = ((J[1][1] - J[1][-1]) - (J[-1][1] - J[-1][-1])) / ((hw+ + hw-) (hp+ + hp-))
+ *   det = Jww Jpp - Jwp Jwp
+ *   out_wspd_std sqrt(2 Jpp / det), m/s      out_dir_std sqrt(2 Jww / det), degrees      out_corr -Jwp / sqrt(Jww Jpp)
+ *   out_flag     uint8, XSW_UNC_* bits; any bit set: the three real outputs are NaN
+ * XSW_UNC_NO_SOLUTION: the code is no grid code of the context's CURRENT co-pol LUT, or the incidence is NaN (the rules of
+ * xsw_cost_from_codes).  XSW_UNC_WSPD_BORDER / XSW_UNC_PHI_BORDER: iw / ip is the first or last index of its axis (both may be
+ * set).  There is NO wrap of a 0..360 axis and NO mirror of a 0..180 axis -- with a 0..180 LUT the folded cost is not symmetric
+ * about 0 / 180 deg, because of |Im anc| -- so a solution on a border has no estimate.  For these three nothing outside the
+ * table, indeed nothing of it, is read.  XSW_UNC_NOT_CONVEX: interior, but not (Jww > 0 and Jpp > 0 and det > 0): a saddle or
+ * flat stencil, or a NaN sigma0 / ancillary wind next to a valid code.  Bit 30 of the code (the -phi solution) does not enter.
+ * Real outputs are `lines x samples` rasters of out_dtype (XSW_F32: the float64 value rounded once), out_flag one of uint8;
+ * each may be NULL (not computed, never written), at least one must be given.  Inputs as in xsw_cost_from_codes.
+ * Bytes per pixel, float32 rasters: 20 read (code, incidence, sigma0, ancillary wind), nine 8-byte LUT entries gathered as three
+ * 24-byte runs phi_pad * 8 bytes apart, 4 or 8 written per real output and 1 for the flag.
+ * XSW_EINVAL, before any launch, with a message in xsw_last_error: no output requested, no co-pol LUT installed, dsig_co NaN or
+ * 0, a NULL input, a bad dtype or mem, a raster too large for one launch.  XSW_MEM_DEVICE: one kernel (k_unc_co), asynchronous
+ * on the context's stream; XSW_MEM_HOST: upload, kernel, download, returns with the outputs filled. */
+#define XSW_UNC_NO_SOLUTION 1u
+#define XSW_UNC_WSPD_BORDER 2u
+#define XSW_UNC_PHI_BORDER  4u
+#define XSW_UNC_NOT_CONVEX  8u
+int xsw_uncertainty_from_codes(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                               int32_t sigma0_is_db, const void *inc, const uint32_t *code_co, const void *sigma0_co, const void *anc,
+                               double dsig_co, void *out_wspd_std, void *out_dir_std, void *out_corr, uint8_t *out_flag);
+
+/* Additive to XSW_VERSION 4.  The 1-D analogue for the cross-pol search: J_cr[k] (windspeed.py:257-264) at icr + k, k = -1, 0, 1,
+ * by the rules of xsw_cost_cr_from_codes (Jwind_cr enters only where the co-pol code names a grid point; XSW_CODE_PICK_CO is
+ * ignored; code_co NULL: every pixel XSW_CODE_NAN; dsig_cr a raster or NULL: dsig_cr_scalar broadcast):
+ *   Jww = the same second difference on the cross-pol speed axis      out_wspd_std sqrt(2 / Jww), m/s
+ *   out_flag     XSW_UNC_NO_SOLUTION (no cross-pol search ran for the pixel, an index at or beyond n_wspd_cr, NaN incidence),
+ *                XSW_UNC_WSPD_BORDER (icr is 0 or n_wspd_cr - 1), XSW_UNC_NOT_CONVEX (interior, not Jww > 0; also a NaN
+ *                sigma0_cr / dsig_cr next to a valid code)
+ * Bytes per pixel, float32 rasters: 16 read (+ 4 with a dsig_cr raster), one 24-byte run of the LUT gathered, 4 or 8 + 1 written.
+ * XSW_EINVAL, before any launch: no output requested, no cross-pol LUT installed, code_co given and no co-pol LUT installed, a
+ * NULL inc / code_cr / sigma0_cr, a bad dtype or mem, a raster too large for one launch.  One kernel (k_unc_cr). */
+int xsw_uncertainty_cr_from_codes(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                                  int32_t sigma0_is_db, const void *inc, const uint32_t *code_co, const uint32_t *code_cr,
+                                  const void *sigma0_cr, const void *dsig_cr, double dsig_cr_scalar, void *out_wspd_std,
+                                  uint8_t *out_flag);
+
 /* Page-locked host memory for rasters a caller fills itself (XSW_MEM_HOST_PINNED); freed by xsw_host_free or with the context. */
 int xsw_host_alloc(xsw_ctx *ctx, size_t bytes, void **out);
 int xsw_host_free(xsw_ctx *ctx, void *p);

@@ -12,6 +12,7 @@ from . import _build, _host
 XSW_F32, XSW_F64 = 0, 1
 MEM_HOST, MEM_DEVICE, MEM_HOST_PINNED, MEM_DEVICE_SIGMA0_HOST = 0, 1, 2, 3
 CODE_NAN_RE, CODE_NAN, CODE_PICK_CO, CODE_NO_INDEX = 0xFFFFFFFF, 0xFFFFFFFE, 0x40000000, 0x3FFFFFFF
+UNC_NO_SOLUTION, UNC_WSPD_BORDER, UNC_PHI_BORDER, UNC_NOT_CONVEX = 1, 2, 4, 8  # XSW_UNC_*: the bits of an uncertainty flag raster
 ALGO_AUTO, ALGO_PRUNED, ALGO_EXHAUSTIVE, ALGO_EXACT, ALGO_EXHAUSTIVE_F64 = 0, 1, 2, 3, 4
 ALGOS = {"auto": ALGO_AUTO, "pruned": ALGO_PRUNED, "exhaustive": ALGO_EXHAUSTIVE, "exact": ALGO_EXACT,
          "exhaustive_f64": ALGO_EXHAUSTIVE_F64}
@@ -47,6 +48,7 @@ EXPORTS = (
     "xsw_grad_hist_masked", "xsw_grad_keep_f64", "xsw_grad_keep_u8",
     "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary",
     "xsw_cross_from_codes", "xsw_cost_from_codes", "xsw_cost_cr_from_codes",
+    "xsw_uncertainty_from_codes", "xsw_uncertainty_cr_from_codes",
     "xsw_dsig", "xsw_dsig_flat", "xsw_dsig_wspd",
 )
 
@@ -213,6 +215,10 @@ def load():
             [ctypes.c_double] + [ctypes.c_void_p] * 4
         lib.xsw_cost_cr_from_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 5 + \
             [ctypes.c_double] + [ctypes.c_void_p] * 4
+        lib.xsw_uncertainty_from_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 4 + \
+            [ctypes.c_double] + [ctypes.c_void_p] * 4
+        lib.xsw_uncertainty_cr_from_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 5 + \
+            [ctypes.c_double] + [ctypes.c_void_p] * 2
         lib.xsw_dsig.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_dsig_flat.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_dsig_wspd.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 3
@@ -471,6 +477,25 @@ class Context:
         self._check(self._lib.xsw_cost_cr_from_codes(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(sigma0_is_db)), inc, code_co,
                                                      code_cr, sigma0_cr, dsig_cr, float(dsig_cr_scalar), out_J, out_Jsig, out_Jwind, out_residual),
                     "xsw_cost_cr_from_codes")
+
+    @_locked
+    def uncertainty_from_codes_raw(self, lines, samples, dtype, out_dtype, mem, inc, code_co, sigma0_co, anc, out_wspd_std, out_dir_std=None,
+                                   out_corr=None, out_flag=None, dsig_co=0.1, sigma0_is_db=False):
+        """Thin call of xsw_uncertainty_from_codes (pointers are ints or None): the standard deviations of wind speed (m/s) and
+        direction (degrees) and their correlation from the curvature of J_co around the grid point of every co-pol code, each into
+        a real raster of `out_dtype`, and the uint8 UNC_* flags (None: not computed)."""
+        self._check(self._lib.xsw_uncertainty_from_codes(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(sigma0_is_db)), inc,
+                                                         code_co, sigma0_co, anc, float(dsig_co), out_wspd_std, out_dir_std, out_corr, out_flag),
+                    "xsw_uncertainty_from_codes")
+
+    @_locked
+    def uncertainty_cr_from_codes_raw(self, lines, samples, dtype, out_dtype, mem, inc, code_co, code_cr, sigma0_cr, dsig_cr, out_wspd_std,
+                                      out_flag=None, dsig_cr_scalar=0.1, sigma0_is_db=False):
+        """Thin call of xsw_uncertainty_cr_from_codes: the 1-D analogue for the cross-pol codes `code_cr` (code_co None: cross-pol
+        only; dsig_cr None: the scalar broadcast)."""
+        self._check(self._lib.xsw_uncertainty_cr_from_codes(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(sigma0_is_db)), inc,
+                                                            code_co, code_cr, sigma0_cr, dsig_cr, float(dsig_cr_scalar), out_wspd_std, out_flag),
+                    "xsw_uncertainty_cr_from_codes")
 
     def expand_codes_on_stream(self, stream, n, out_dtype, code_co, code_cr, out_co, out_cr):
         """xsw_expand_codes_on_stream: device codes -> device winds on `stream` (a HIP stream handle as an int), the context's

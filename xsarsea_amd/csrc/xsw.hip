@@ -726,6 +726,64 @@ extern "C" int xsw_cost_cr_from_codes(xsw_ctx *c, int64_t lines, int64_t samples
     return cost_from_codes(c, "cost_cr_from_codes", true, lines, samples, dtype, out_dtype, mem, A);
 }
 
+// ---- wind uncertainty from stored codes (xsw.h: xsw_uncertainty_from_codes, xsw_uncertainty_cr_from_codes; kernels: xsw_uncertainty.hpp)
+// One body for the two entries, as cost_from_codes: A holds the caller's pointers; every check comes before any launch.
+static int uncertainty_from_codes(xsw_ctx *c, const char *who, bool cr, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype,
+                                  int32_t mem, UncArgs A)
+{
+    if (lines < 0 || samples < 0) return fail(c, XSW_EINVAL, "negative raster shape");
+    if ((dtype != XSW_F32 && dtype != XSW_F64) || (out_dtype != XSW_F32 && out_dtype != XSW_F64))
+        return fail(c, XSW_EINVAL, "dtype/out_dtype must be XSW_F32 or XSW_F64");
+    if (mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE) return fail(c, XSW_EINVAL, "bad mem kind");
+    if (!A.inc || !A.s || (cr ? !A.code_cr : (!A.code_co || !A.anc))) return fail(c, XSW_EINVAL, "%s: an input raster is NULL", who);
+    if (!A.out_wspd_std && !A.out_dir_std && !A.out_corr && !A.out_flag) return fail(c, XSW_EINVAL, "%s: no output requested", who);
+    if (cr ? !c->have_cr : !c->have_co) return fail(c, XSW_EINVAL, "%s: no %s LUT installed", who, cr ? "cross-pol" : "co-pol");
+    if (cr && A.code_co && !c->have_co) return fail(c, XSW_EINVAL, "%s: co-pol codes given but no co-pol LUT installed", who);
+    if (!cr && (A.dsig_co != A.dsig_co || A.dsig_co == 0.0)) return fail(c, XSW_EINVAL, "%s: dsig_co is NaN or 0", who);
+    if (lines && samples > (int64_t)(0x7fffffffLL * 256) / lines)  // (no overflow of lines * samples; one launch of 256-pixel blocks)
+        return fail(c, XSW_EINVAL, "%s: raster too large for one launch", who);
+    A.n = (long long)lines * samples;
+    if (A.n == 0) return XSW_OK;
+    const size_t es = dtype == XSW_F32 ? 4 : 8, os = out_dtype == XSW_F32 ? 4 : 8, px = (size_t)A.n;
+    Buf b[10] = {in_buf(A.inc, px * es), in_buf(A.s, px * es), in_buf(A.anc, px * es * 2), in_buf(A.dsig_cr, px * es),
+                 in_buf(A.code_co, px * 4), in_buf(A.code_cr, px * 4), out_buf(A.out_wspd_std, px * os), out_buf(A.out_dir_std, px * os),
+                 out_buf(A.out_corr, px * os), out_buf(A.out_flag, px)};
+    return run(c, mem, b, [&](Buf (&x)[10]) {
+        A.inc = x[0].dev; A.s = x[1].dev; A.anc = x[2].dev; A.dsig_cr = x[3].dev;
+        A.code_co = (const unsigned *)x[4].dev; A.code_cr = (const unsigned *)x[5].dev;
+        A.out_wspd_std = x[6].dev; A.out_dir_std = x[7].dev; A.out_corr = x[8].dev; A.out_flag = (unsigned char *)x[9].dev;
+        std::string err;
+        const int rc = pair_launch(dtype, out_dtype).unc(c, A, cr, c->stream, err);
+        return rc ? fail(c, rc, "%s", err.c_str()) : XSW_OK;
+    }, who);
+}
+
+extern "C" int xsw_uncertainty_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                                          int32_t sigma0_is_db, const void *inc, const uint32_t *code_co, const void *sigma0_co,
+                                          const void *anc, double dsig_co, void *out_wspd_std, void *out_dir_std, void *out_corr,
+                                          uint8_t *out_flag)
+{
+    if (!c) return XSW_EINVAL;
+    UncArgs A{};
+    A.inc = inc; A.s = sigma0_co; A.anc = anc; A.code_co = code_co;
+    A.out_wspd_std = out_wspd_std; A.out_dir_std = out_dir_std; A.out_corr = out_corr; A.out_flag = out_flag;
+    A.dsig_co = dsig_co; A.is_db = sigma0_is_db;
+    return uncertainty_from_codes(c, "uncertainty_from_codes", false, lines, samples, dtype, out_dtype, mem, A);
+}
+
+extern "C" int xsw_uncertainty_cr_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                                             int32_t sigma0_is_db, const void *inc, const uint32_t *code_co, const uint32_t *code_cr,
+                                             const void *sigma0_cr, const void *dsig_cr, double dsig_cr_scalar, void *out_wspd_std,
+                                             uint8_t *out_flag)
+{
+    if (!c) return XSW_EINVAL;
+    UncArgs A{};
+    A.inc = inc; A.s = sigma0_cr; A.dsig_cr = dsig_cr; A.code_co = code_co; A.code_cr = code_cr;
+    A.out_wspd_std = out_wspd_std; A.out_flag = out_flag;
+    A.dsig_cr_scalar = dsig_cr_scalar; A.is_db = sigma0_is_db;
+    return uncertainty_from_codes(c, "uncertainty_cr_from_codes", true, lines, samples, dtype, out_dtype, mem, A);
+}
+
 // ---- host-memory paths: chunks through a ring of workers (thread + stream + page-locked staging + device staging each)
 static int host_thread_count(const xsw_ctx *c)
 {

@@ -28,6 +28,47 @@ __device__ __forceinline__ void cost_store(void *out, long long i, double v)
     if (out) ((TO *)out)[i] = (TO)v;
 }
 
+// J_co of windspeed.py:216-225 at grid point (iw, ip) of incidence slice i_inc, with its terms and lut_db - sigma0_db: the ONE
+// statement of the co-pol cost from stored codes (k_cost_co: at the code's point; k_unc_co, xsw_uncertainty.hpp: at its nine
+// stencil points).  a, b: Re / Im (|Im| for a 0..180 LUT) of the ancillary wind.  A term not wanted stays NaN, and J with it.
+__device__ __forceinline__ double cost_co_at(const DevTables &L, int i_inc, int iw, int ip, double s_db, double a, double b, double dsig_co,
+                                             bool want_wind, bool want_sig, double &Jsig, double &Jwind, double &res)
+{
+    const double lutv = L.co[((size_t)i_inc * (size_t)L.n_w + (size_t)iw) * (size_t)L.phi_pad + (size_t)ip];
+    res = lutv - s_db;
+    if (want_wind) {  // exact_J_co's order
+        const double w = L.w[iw];
+        const double t1 = (w * L.cphi[ip] - a) * 0.5;
+        const double t2 = (w * L.sphi[ip] - b) * 0.5;
+        Jwind = t1 * t1 + t2 * t2;
+    }
+    if (want_sig) {
+        const double d = (lutv - s_db) / dsig_co;
+        Jsig = d * d;
+    }
+    return Jwind + Jsig;
+}
+
+// J_cr of windspeed.py:257-264 at cross-pol speed index icr of incidence row i_inc_cr, likewise (k_cost_cr; k_unc_cr at its
+// three stencil points).  have_co: the co-pol code names grid point `flat` of the co-pol LUT, whose |wind_co| enters Jwind.
+__device__ __forceinline__ double cost_cr_at(const DevTables &L, int i_inc_cr, unsigned icr, double s_db, double dsig, bool have_co, unsigned flat,
+                                             bool want_wind, bool want_sig, double &Jsig, double &Jwind, double &res)
+{
+    const double lutv = L.cr[(size_t)i_inc_cr * (size_t)L.wcr_pad + (size_t)icr];
+    res = lutv - s_db;
+    if (want_sig) {
+        const double d = (lutv - s_db) / dsig;
+        Jsig = d * d;
+    }
+    double J = Jsig;
+    if (have_co && want_wind) {  // exact_J_cr's order
+        const double t = (L.wcr[icr] - L.abs_co[flat]) * 0.5;
+        Jwind = t * t;
+        J = Jsig + Jwind;
+    }
+    return J;
+}
+
 // co-pol: windspeed.py:212-225 at (i_wspd, i_phi) = (flat / n_phi, flat % n_phi); bit 30 (the -phi choice) does not enter the cost
 template <typename T, typename TO>
 __global__ __launch_bounds__(256, 8) void k_cost_co(DevTables L, CostArgs A)
@@ -51,19 +92,7 @@ __global__ __launch_bounds__(256, 8) void k_cost_co(DevTables L, CostArgs A)
     if (grid_code && inc == inc) {
         const int i_inc = nearest_index(L.inc, L.n_inc, inc, L.inc_uniform != 0, L.inc0, L.inv_incstep);
         const int iw = (int)(flat / (unsigned)L.n_phi), ip = (int)(flat - (unsigned)iw * (unsigned)L.n_phi);
-        const double lutv = L.co[((size_t)i_inc * (size_t)L.n_w + (size_t)iw) * (size_t)L.phi_pad + (size_t)ip];
-        res = lutv - s_db;
-        if (want_wind) {  // exact_J_co's order
-            const double w = L.w[iw];
-            const double t1 = (w * L.cphi[ip] - a) * 0.5;
-            const double t2 = (w * L.sphi[ip] - b) * 0.5;
-            Jwind = t1 * t1 + t2 * t2;
-        }
-        if (want_sig) {
-            const double d = (lutv - s_db) / A.dsig_co;
-            Jsig = d * d;
-        }
-        J = Jwind + Jsig;
+        J = cost_co_at(L, i_inc, iw, ip, s_db, a, b, A.dsig_co, want_wind, want_sig, Jsig, Jwind, res);
     }
     cost_store<TO>(A.out_J, i, J);
     cost_store<TO>(A.out_Jsig, i, Jsig);
@@ -91,20 +120,9 @@ __global__ __launch_bounds__(256, 8) void k_cost_cr(DevTables L, CostArgs A)
     double J = nan, Jsig = nan, Jwind = nan, res = nan;
     if (searched) {
         const int i_inc_cr = nearest_index(L.inc_cr, L.n_inc_cr, inc, L.inc_cr_uniform != 0, L.inc_cr0, L.inv_inccrstep);
-        const double lutv = L.cr[(size_t)i_inc_cr * (size_t)L.wcr_pad + (size_t)icr];
-        res = lutv - s_db;
-        if (want_sig) {
-            const double d = (lutv - s_db) / dsig;
-            Jsig = d * d;
-        }
-        J = Jsig;
         const unsigned plane = (unsigned)(L.n_w * L.n_phi), flat = code & 0x3FFFFFFFu;
         const bool have_co = !(code & 0x80000000u) && flat < plane;  // (the incidence is not NaN here)
-        if (have_co && want_wind) {  // exact_J_cr's order
-            const double t = (L.wcr[icr] - L.abs_co[flat]) * 0.5;
-            Jwind = t * t;
-            J = Jsig + Jwind;
-        }
+        J = cost_cr_at(L, i_inc_cr, icr, s_db, dsig, have_co, flat, want_wind, want_sig, Jsig, Jwind, res);
     }
     cost_store<TO>(A.out_J, i, J);
     cost_store<TO>(A.out_Jsig, i, Jsig);

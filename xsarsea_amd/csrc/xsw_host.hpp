@@ -236,9 +236,21 @@ struct CostArgs {
     double dsig_co, dsig_cr_scalar;
     int is_db;
 };
+
+// The arguments of k_unc_co / k_unc_cr (xsw_uncertainty.hpp; xsw.h: xsw_uncertainty_from_codes, xsw_uncertainty_cr_from_codes).
+struct UncArgs {
+    const void *inc, *s, *anc, *dsig_cr;  // as in CostArgs
+    const unsigned *code_co, *code_cr;    // k_unc_cr: code_co nullable (every pixel XSW_CODE_NAN)
+    void *out_wspd_std, *out_dir_std, *out_corr;  // each nullable: reals of the output dtype (k_unc_cr: out_wspd_std alone)
+    unsigned char *out_flag;                      // nullable: XSW_UNC_* bits
+    long long n;
+    double dsig_co, dsig_cr_scalar;
+    int is_db;
+};
 }  // namespace xsw
 
-// The launches of one (input dtype, output dtype) pair: the inversion kernels, k_cross_from_codes and k_cost_co / k_cost_cr.
+// The launches of one (input dtype, output dtype) pair: the inversion kernels, k_cross_from_codes, k_cost_co / k_cost_cr and
+// k_unc_co / k_unc_cr.
 // Each returns an XSW_* code and, with a non-zero one, its message in `err`.  One instance per translation unit
 // (xsw_invert_tu.hip, -DXSW_PAIR=0..3: f32->f32, f32->f64, f64->f32, f64->f64), so that the four sets of kernel
 // instantiations compile side by side; it sits behind a host function, which keeps it out of the device pass.
@@ -246,6 +258,7 @@ struct PairLaunch {
     int (*invert)(xsw_ctx *c, const xsw::KArgs &A, int algo, const LaunchCtl &lc, std::string &err);
     int (*cross)(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream, std::string &err);
     int (*cost)(xsw_ctx *c, const xsw::CostArgs &A, bool cr, hipStream_t stream, std::string &err);
+    int (*unc)(xsw_ctx *c, const xsw::UncArgs &A, bool cr, hipStream_t stream, std::string &err);
 };
 const PairLaunch &xsw_pair_0(), &xsw_pair_1(), &xsw_pair_2(), &xsw_pair_3();
 

@@ -455,9 +455,10 @@ class _DeviceCodes:
         self.plan, self.ctx = plan, _device.context_of(dev)
         self.rasters = [_device.prep(x, plan.cdtype if k == 3 else plan.dtype, plan.shape) for k, x in enumerate(t)] + [c.contiguous() for c in codes]
 
-    def empty(self, dtype=None):
+    def empty(self, dtype=None):  # None: grid codes; uint8: a flag raster
         import torch
-        return torch.empty(self.plan.shape, dtype=torch.int32 if dtype is None else _device.torch_dtype(dtype), device=self.dev)
+        t = torch.int32 if dtype is None else torch.uint8 if np.dtype(dtype) == np.uint8 else _device.torch_dtype(dtype)
+        return torch.empty(self.plan.shape, dtype=t, device=self.dev)
 
     def run(self, lut_co, lut_cr, call):
         if self.plan.n:
@@ -510,6 +511,28 @@ def cost_cr_from_codes(lut_co, lut_cr, plan, codes_co, codes_cr, inc, sigma0_cr,
     k = _codes_call(plan, inc, sigma0_cr, dsig_cr, None, codes_co, codes_cr)
     outs = _cost_outputs(parts, lambda: k.empty(out_dtype))
     k.run(lut_co, lut_cr, lambda ctx, inc, s_cr, dsig, _, cc, ccr: ctx.cost_cr_from_codes_raw(
+        plan.lines, plan.samples, plan.code, _real_code(out_dtype), k.mem, inc, cc, ccr, s_cr, dsig, *(k.at(o) for o in outs),
+        dsig_cr_scalar=plan.dsig_scalar, sigma0_is_db=plan.is_db))
+    return outs
+
+
+def uncertainty_from_codes(lut_co, plan, codes_co, inc, sigma0, anc, dsig_co=0.1, out_dtype=np.float64):
+    """[wspd_std, dir_std, corr] (`out_dtype`) and the uint8 flag raster (numpy, or torch for device rasters) of the co-pol codes
+    `codes_co` from the rasters they were computed from (xsw_uncertainty_from_codes; `plan` is the co-pol call's)."""
+    k = _codes_call(plan, inc, sigma0, None, anc, codes_co)
+    outs = [k.empty(out_dtype) for _ in range(3)] + [k.empty(np.uint8)]
+    k.run(lut_co, None, lambda ctx, inc, s_co, _, anc, cc: ctx.uncertainty_from_codes_raw(
+        plan.lines, plan.samples, plan.code, _real_code(out_dtype), k.mem, inc, cc, s_co, anc, *(k.at(o) for o in outs),
+        dsig_co=dsig_co, sigma0_is_db=plan.is_db))
+    return outs
+
+
+def uncertainty_cr_from_codes(lut_co, lut_cr, plan, codes_co, codes_cr, inc, sigma0_cr, dsig_cr, out_dtype=np.float64):
+    """[wspd_std, flag] of the cross-pol codes `codes_cr`: the cross-pol inputs formed as `cost_cr_from_codes` forms them, then
+    xsw_uncertainty_cr_from_codes."""
+    k = _codes_call(plan, inc, sigma0_cr, dsig_cr, None, codes_co, codes_cr)
+    outs = [k.empty(out_dtype), k.empty(np.uint8)]
+    k.run(lut_co, lut_cr, lambda ctx, inc, s_cr, dsig, _, cc, ccr: ctx.uncertainty_cr_from_codes_raw(
         plan.lines, plan.samples, plan.code, _real_code(out_dtype), k.mem, inc, cc, ccr, s_cr, dsig, *(k.at(o) for o in outs),
         dsig_cr_scalar=plan.dsig_scalar, sigma0_is_db=plan.is_db))
     return outs

@@ -5,6 +5,8 @@ another cross-pol GMF, another `dsig_cr` -- each time one pass of `xsw_cross_fro
     cc = invert_copol_codes(inc, sigma0_vv, ancillary_wind=anc, model="gmf_cmod5n")
     wind_co = cc.wind()                                            # == invert_from_model(inc, sigma0_vv, ...) mono
     wind_dual = cc.dual(sigma0_vh, dsig_cr=dsig, model="gmf_s1_v2")  # == invert_from_model(inc, vv, vh, ...)[1]
+    fit = cc.cost(sigma0_vv, anc)                                  # InversionCost: J at the minimum, its terms, the residual
+    bars = cc.uncertainty(sigma0_vv, anc)                          # InversionUncertainty: wspd_std, dir_std, corr, flag
 
 numpy rasters (numpy out) and device rasters (torch CUDA tensors / `__cuda_array_interface__`; torch out, asynchronous on
 torch's current stream) only: xarray / dask containers are not handled here.  The bit equality with the fused call holds for
@@ -57,6 +59,24 @@ class InversionCost:
 
     def __init__(self, J, Jsig=None, Jwind=None, residual_db=None):
         self.J, self.Jsig, self.Jwind, self.residual_db = J, Jsig, Jwind, residual_db
+
+    def __getitem__(self, name):
+        return getattr(self, name)
+
+
+class InversionUncertainty:
+    """Result of `CopolCodes.uncertainty` / `.uncertainty_dual`: how well the solution is DETERMINED (where `InversionCost` says
+    how well it fits), from the curvature of the cost around the stored grid point (posterior ~ exp(-J / 2): covariance = 2 H^-1,
+    H by second differences on the LUT axes' own spacings).  wspd_std in m/s, dir_std in degrees, corr their correlation (both
+    None for the cross-pol search, which has one axis), flag a uint8 raster of bits (`FLAGS`): 1 no solution, 2 the solution
+    lies on a border of the wind-speed axis, 4 on a border of the direction axis, 8 interior but the stencil is not convex
+    (also: a NaN sigma0 / a-priori next to a valid code).  Any flag: the real rasters are NaN there.  Borders are not wrapped
+    (0..360 axes) or mirrored (0..180 axes: the folded cost is not symmetric about 0 / 180 deg because of |Im(ancillary)|), so
+    a solution on a border has no estimate."""
+    FLAGS = {"no_solution": 1, "wspd_border": 2, "phi_border": 4, "not_convex": 8}
+
+    def __init__(self, wspd_std, dir_std=None, corr=None, flag=None):
+        self.wspd_std, self.dir_std, self.corr, self.flag = wspd_std, dir_std, corr, flag
 
     def __getitem__(self, name):
         return getattr(self, name)
@@ -136,13 +156,10 @@ class CopolCodes:
             raise ValueError(f"model {m.name} ({m.pol}) is not a cross-pol model")
         return plan, _engine.lut_source(m, kwargs)
 
-    def cost(self, sigma0, ancillary_wind, dsig_co=None, parts=True, out_dtype=None):
-        """The cost the co-pol search minimised, at its minimum: `InversionCost` with J = Jwind + Jsig of windspeed.py:216-225 at
-        the stored grid point (bit for bit the minimum of the reference's dense J_co), its two terms and residual_db = lut_db -
-        sigma0_db.  sigma0 / ancillary_wind: the rasters `invert_copol_codes` was given (a raster of another shape or dtype is
-        refused: the cost would not be the one the search minimised).  dsig_co=None: the co-pol call's (else 0.1).
-        parts=False: J alone.  out_dtype: float64 (default) or float32.  ValueError / TypeError before any device call."""
-        _refuse_containers("CopolCodes.cost", sigma0, ancillary_wind)
+    def _co_step(self, who, sigma0, ancillary_wind, dsig_co):
+        """(plan, dsig_co) of a pass over the co-pol rasters from these codes, after every refusal `cost` and `uncertainty` share;
+        nothing here touches the device."""
+        _refuse_containers(who, sigma0, ancillary_wind)
         if sigma0 is None or ancillary_wind is None:
             raise ValueError("sigma0 and ancillary_wind are both needed: the rasters the co-pol codes were computed from")
         self._same_kind(sigma0=sigma0, ancillary_wind=ancillary_wind)
@@ -161,8 +178,26 @@ class CopolCodes:
             dsig_co = 0.1 if self.dsig_co is None else self.dsig_co
         if not np.isscalar(dsig_co) or not float(dsig_co) == float(dsig_co) or float(dsig_co) == 0.0:
             raise ValueError(f"dsig_co must be a scalar other than 0 and NaN, not {dsig_co!r}")
-        return InversionCost(*_engine.cost_from_codes(self.lut_co, plan, self.codes, self.inc, sigma0, ancillary_wind, dsig_co=float(dsig_co),
+        return plan, float(dsig_co)
+
+    def cost(self, sigma0, ancillary_wind, dsig_co=None, parts=True, out_dtype=None):
+        """The cost the co-pol search minimised, at its minimum: `InversionCost` with J = Jwind + Jsig of windspeed.py:216-225 at
+        the stored grid point (bit for bit the minimum of the reference's dense J_co), its two terms and residual_db = lut_db -
+        sigma0_db.  sigma0 / ancillary_wind: the rasters `invert_copol_codes` was given (a raster of another shape or dtype is
+        refused: the cost would not be the one the search minimised).  dsig_co=None: the co-pol call's (else 0.1).
+        parts=False: J alone.  out_dtype: float64 (default) or float32.  ValueError / TypeError before any device call."""
+        plan, dsig_co = self._co_step("CopolCodes.cost", sigma0, ancillary_wind, dsig_co)
+        return InversionCost(*_engine.cost_from_codes(self.lut_co, plan, self.codes, self.inc, sigma0, ancillary_wind, dsig_co=dsig_co,
                                                       parts=parts, out_dtype=_real_dtype(out_dtype)))
+
+    def uncertainty(self, sigma0, ancillary_wind, dsig_co=None, out_dtype=None):
+        """The error bars of the co-pol wind: `InversionUncertainty` with wspd_std (m/s), dir_std (degrees), their correlation
+        and a uint8 flag raster, from the second differences of J_co (windspeed.py:216-225) over the 3 x 3 grid points around the
+        stored one (include/xsw.h: xsw_uncertainty_from_codes).  Arguments and refusals as `cost`.  A solution on the first or
+        last index of an axis has no estimate (flag 2 / 4): a 0..360 direction axis is not wrapped, a 0..180 one not mirrored."""
+        plan, dsig_co = self._co_step("CopolCodes.uncertainty", sigma0, ancillary_wind, dsig_co)
+        return InversionUncertainty(*_engine.uncertainty_from_codes(self.lut_co, plan, self.codes, self.inc, sigma0, ancillary_wind,
+                                                                    dsig_co=dsig_co, out_dtype=_real_dtype(out_dtype)))
 
     def cost_dual(self, sigma0_dual, codes_cr, dsig_cr=0.1, model=None, parts=True, out_dtype=None, **kwargs):
         """The cost the cross-pol search of `.dual(sigma0_dual, dsig_cr=..., model=..., **kwargs)` minimised, at its minimum:
@@ -172,6 +207,15 @@ class CopolCodes:
         plan, lut_cr = self._cross_step("CopolCodes.cost_dual", sigma0_dual, dsig_cr, model, kwargs, codes_cr=codes_cr)
         return InversionCost(*_engine.cost_cr_from_codes(self.lut_co, lut_cr, plan, self.codes, codes_cr, self.inc, sigma0_dual, dsig_cr,
                                                          parts=parts, out_dtype=_real_dtype(out_dtype)))
+
+    def uncertainty_dual(self, sigma0_dual, codes_cr, dsig_cr=0.1, model=None, out_dtype=None, **kwargs):
+        """The error bar of the cross-pol wind speed of `.dual(sigma0_dual, dsig_cr=..., model=..., **kwargs)`:
+        `InversionUncertainty(wspd_std, None, None, flag)` from the second difference of J_cr (windspeed.py:257-264) over the three
+        speeds around the stored one.  codes_cr and the refusals as `cost_dual`; the select does not enter."""
+        plan, lut_cr = self._cross_step("CopolCodes.uncertainty_dual", sigma0_dual, dsig_cr, model, kwargs, codes_cr=codes_cr)
+        std, flag = _engine.uncertainty_cr_from_codes(self.lut_co, lut_cr, plan, self.codes, codes_cr, self.inc, sigma0_dual, dsig_cr,
+                                                      out_dtype=_real_dtype(out_dtype))
+        return InversionUncertainty(std, None, None, flag)
 
 
 def invert_copol_codes(inc, sigma0, /, ancillary_wind=None, dsig_co=0.1, model=None, **kwargs):
