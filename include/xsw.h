@@ -326,6 +326,38 @@ int xsw_uncertainty_cr_from_codes(xsw_ctx *ctx, int64_t lines, int64_t samples, 
                                   const void *sigma0_cr, const void *dsig_cr, double dsig_cr_scalar, void *out_wspd_std,
                                   uint8_t *out_flag);
 
+/* ---- the forward operator on rasters.  Additive to XSW_VERSION 4.  sigma0 in dB that the context's CURRENT co-pol table
+ * T[i][w][p] (axes ai, aw, ap) predicts for the wind (wspd, phi) at incidence inc, per pixel, and the derivatives of that
+ * interpolant.  Every input is up-cast to float64; only IEEE + - * / follow, in this order, without fused multiply-adds:
+ *   fold (fold_phi != 0 only): p = fmod(phi, 360); if (p < 0) p = p + 360; reflected = p > ap[n_phi - 1]; if (reflected)
+ *        p = 360 - p  (sigma0(phi) = sigma0(-phi): a 0..180 table reflects, a 0..360 table never does, a 0..90 table leaves such
+ *        a pixel outside).  fold_phi == 0: p = phi, reflected = false.
+ *   cell, per axis: hi = clip(first index with axis[hi] >= x, 1, n - 1), lo = hi - 1 (numpy.searchsorted, side left: a value
+ *        equal to node j > 0 takes the cell below it).
+ *   lerp, always slope = (y_hi - y_lo) / (x_hi - x_lo), y = slope * (x - x_lo) + y_lo: along the incidence for the four (w, p)
+ *        corners (v[a][b]), then along the wind speed (slopes s_b, values u_b, b = 0, 1), then along the direction (slope sp).
+ *   out_db    the last value, dB
+ *   out_dwspd ((s_1 - s_0) / (p_hi - p_lo)) * (p - p_lo) + s_0, dB per m/s
+ *   out_dphi  reflected ? -sp : sp, dB per degree
+ * NaN in every output where one of the three coordinates is NaN or lies outside [axis[0], axis[n - 1]] (the direction: after the
+ * fold); such a pixel reads nothing of the table.  out_db is bit for bit the table's linear interpolation axis by axis
+ * (scipy interp1d's statements).  Outputs are `lines x samples` rasters of out_dtype (XSW_F32: the float64 value rounded once);
+ * each may be NULL (not computed, never written), at least one must be given.
+ * Bytes per pixel, float32 rasters: 12 read, eight 8-byte LUT entries gathered as four adjacent pairs in two incidence planes,
+ * 4 or 8 written per output.
+ * Before any launch, with a message in xsw_last_error: XSW_ENOLUT without a co-pol LUT; XSW_EINVAL for no output requested, a
+ * NULL input, a bad shape, dtype or mem, an axis of the LUT with fewer than two points (there is no cell on it), a raster too
+ * large for one launch.  An empty raster returns XSW_OK and launches nothing.  XSW_MEM_DEVICE: one kernel (k_lut_eval_co),
+ * asynchronous on the context's stream; XSW_MEM_HOST: upload, kernel, download, returns with the outputs filled. */
+int xsw_lut_eval(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem, int32_t fold_phi,
+                 const void *inc, const void *wspd, const void *phi, void *out_db, void *out_dwspd, void *out_dphi);
+
+/* Additive to XSW_VERSION 4.  The 2-D analogue on the cross-pol table cr[i][w]: incidence, then wind speed; out_dwspd is the
+ * speed slope; there is no direction.  Bytes per pixel, float32 rasters: 8 read, four LUT entries gathered as two adjacent
+ * pairs, 4 or 8 written per output.  Refusals as xsw_lut_eval, for the cross-pol LUT.  One kernel (k_lut_eval_cr). */
+int xsw_lut_eval_cr(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem, const void *inc,
+                    const void *wspd, void *out_db, void *out_dwspd);
+
 /* Page-locked host memory for rasters a caller fills itself (XSW_MEM_HOST_PINNED); freed by xsw_host_free or with the context. */
 int xsw_host_alloc(xsw_ctx *ctx, size_t bytes, void **out);
 int xsw_host_free(xsw_ctx *ctx, void *p);

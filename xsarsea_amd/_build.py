@@ -111,6 +111,25 @@ def kernel_resources(lib=None):
     return sorted(out, key=lambda d: d["kernel"])
 
 
+def kernel_mnemonics(name_part, lib=None):
+    """{kernel symbol: {mnemonic: count}} from the disassembly of every kernel of libxsw.so's gfx950 code objects whose
+    name holds `name_part`: what the compiler made of a kernel whose loads matter (tests/test_forward_cpu.py holds
+    k_lut_eval_co / k_lut_eval_cr to 8-byte gathers with it, so that a compiler that merges them again does not go unnoticed)."""
+    import collections
+    import re
+    import tempfile
+    lib = lib or LIB
+    llvm = "/opt/rocm/lib/llvm/bin"
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        for co in _code_objects(lib, td):
+            notes = subprocess.check_output([f"{llvm}/llvm-readelf", "--notes", co], text=True)
+            for sym in sorted({n for n in re.findall(r"\.name:\s+(\S+)", notes) if name_part in n}):
+                text = subprocess.check_output([f"{llvm}/llvm-objdump", "-d", f"--disassemble-symbols={sym}", co], text=True)
+                out[sym] = dict(collections.Counter(m for m in re.findall(r"^\s+([a-z][a-z0-9_]+)\s", text, flags=re.M)))
+    return out
+
+
 def write_kernel_resources(path):
     rows = kernel_resources()
     with open(path, "w") as f:

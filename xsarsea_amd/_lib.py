@@ -49,6 +49,7 @@ EXPORTS = (
     "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary",
     "xsw_cross_from_codes", "xsw_cost_from_codes", "xsw_cost_cr_from_codes",
     "xsw_uncertainty_from_codes", "xsw_uncertainty_cr_from_codes",
+    "xsw_lut_eval", "xsw_lut_eval_cr",
     "xsw_dsig", "xsw_dsig_flat", "xsw_dsig_wspd",
 )
 
@@ -219,6 +220,8 @@ def load():
             [ctypes.c_double] + [ctypes.c_void_p] * 4
         lib.xsw_uncertainty_cr_from_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 5 + \
             [ctypes.c_double] + [ctypes.c_void_p] * 2
+        lib.xsw_lut_eval.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 6
+        lib.xsw_lut_eval_cr.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_dsig.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_dsig_flat.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_dsig_wspd.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 3
@@ -496,6 +499,20 @@ class Context:
         self._check(self._lib.xsw_uncertainty_cr_from_codes(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(sigma0_is_db)), inc,
                                                             code_co, code_cr, sigma0_cr, dsig_cr, float(dsig_cr_scalar), out_wspd_std, out_flag),
                     "xsw_uncertainty_cr_from_codes")
+
+    @_locked
+    def lut_eval_raw(self, lines, samples, dtype, out_dtype, mem, inc, wspd, phi, out_db, out_dwspd=None, out_dphi=None, fold_phi=True):
+        """Thin call of xsw_lut_eval (pointers are ints or None): sigma0 in dB that the context's co-pol table predicts for the wind
+        (wspd, phi) at incidence inc, and the derivatives of that interpolant in dB per m/s and dB per degree, each into a real
+        raster of `out_dtype` (None: not computed)."""
+        self._check(self._lib.xsw_lut_eval(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(fold_phi)), inc, wspd, phi,
+                                           out_db, out_dwspd, out_dphi), "xsw_lut_eval")
+
+    @_locked
+    def lut_eval_cr_raw(self, lines, samples, dtype, out_dtype, mem, inc, wspd, out_db, out_dwspd=None):
+        """Thin call of xsw_lut_eval_cr: the same on the cross-pol table, which has no direction."""
+        self._check(self._lib.xsw_lut_eval_cr(self._h, int(lines), int(samples), dtype, out_dtype, mem, inc, wspd, out_db, out_dwspd),
+                    "xsw_lut_eval_cr")
 
     def expand_codes_on_stream(self, stream, n, out_dtype, code_co, code_cr, out_co, out_cr):
         """xsw_expand_codes_on_stream: device codes -> device winds on `stream` (a HIP stream handle as an int), the context's

@@ -784,6 +784,57 @@ extern "C" int xsw_uncertainty_cr_from_codes(xsw_ctx *c, int64_t lines, int64_t 
     return uncertainty_from_codes(c, "uncertainty_cr_from_codes", true, lines, samples, dtype, out_dtype, mem, A);
 }
 
+// ---- the forward operator on rasters (xsw.h: xsw_lut_eval, xsw_lut_eval_cr; kernels: xsw_forward.hpp)
+// One body for the two entries, as cost_from_codes: A holds the caller's pointers; every check comes before any launch.
+static int lut_eval(xsw_ctx *c, const char *who, bool cr, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                    FwdArgs A)
+{
+    if (lines < 0 || samples < 0) return fail(c, XSW_EINVAL, "negative raster shape");
+    if ((dtype != XSW_F32 && dtype != XSW_F64) || (out_dtype != XSW_F32 && out_dtype != XSW_F64))
+        return fail(c, XSW_EINVAL, "dtype/out_dtype must be XSW_F32 or XSW_F64");
+    if (mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE) return fail(c, XSW_EINVAL, "bad mem kind");
+    if (!A.inc || !A.wspd || (!cr && !A.phi)) return fail(c, XSW_EINVAL, "%s: an input raster is NULL", who);
+    if (!A.out_db && !A.out_dwspd && !A.out_dphi) return fail(c, XSW_EINVAL, "%s: no output requested", who);
+    if (cr ? !c->have_cr : !c->have_co) return fail(c, XSW_ENOLUT, "%s: no %s LUT installed", who, cr ? "cross-pol" : "co-pol");
+    if (cr ? (c->T.n_inc_cr < 2 || c->T.n_wcr < 2) : (c->T.n_inc < 2 || c->T.n_w < 2 || c->T.n_phi < 2))  // (no cell to interpolate in)
+        return fail(c, XSW_EINVAL, "%s: an axis of the %s LUT has fewer than two points", who, cr ? "cross-pol" : "co-pol");
+    if (lines && samples > (int64_t)(0x7fffffffLL * 256) / lines)  // (no overflow of lines * samples; one launch of 256-pixel blocks)
+        return fail(c, XSW_EINVAL, "%s: raster too large for one launch", who);
+    A.n = (long long)lines * samples;
+    if (A.n == 0) return XSW_OK;
+    const size_t es = dtype == XSW_F32 ? 4 : 8, os = out_dtype == XSW_F32 ? 4 : 8, px = (size_t)A.n;
+    Buf b[6] = {in_buf(A.inc, px * es), in_buf(A.wspd, px * es), in_buf(A.phi, px * es),
+                out_buf(A.out_db, px * os), out_buf(A.out_dwspd, px * os), out_buf(A.out_dphi, px * os)};
+    return run(c, mem, b, [&](Buf (&x)[6]) {
+        A.inc = x[0].dev; A.wspd = x[1].dev; A.phi = x[2].dev;
+        A.out_db = x[3].dev; A.out_dwspd = x[4].dev; A.out_dphi = x[5].dev;
+        std::string err;
+        const int rc = pair_launch(dtype, out_dtype).fwd(c, A, cr, c->stream, err);
+        return rc ? fail(c, rc, "%s", err.c_str()) : XSW_OK;
+    }, who);
+}
+
+extern "C" int xsw_lut_eval(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem, int32_t fold_phi,
+                            const void *inc, const void *wspd, const void *phi, void *out_db, void *out_dwspd, void *out_dphi)
+{
+    if (!c) return XSW_EINVAL;
+    FwdArgs A{};
+    A.inc = inc; A.wspd = wspd; A.phi = phi;
+    A.out_db = out_db; A.out_dwspd = out_dwspd; A.out_dphi = out_dphi;
+    A.fold_phi = fold_phi != 0;
+    return lut_eval(c, "lut_eval", false, lines, samples, dtype, out_dtype, mem, A);
+}
+
+extern "C" int xsw_lut_eval_cr(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem, const void *inc,
+                               const void *wspd, void *out_db, void *out_dwspd)
+{
+    if (!c) return XSW_EINVAL;
+    FwdArgs A{};
+    A.inc = inc; A.wspd = wspd;
+    A.out_db = out_db; A.out_dwspd = out_dwspd;
+    return lut_eval(c, "lut_eval_cr", true, lines, samples, dtype, out_dtype, mem, A);
+}
+
 // ---- host-memory paths: chunks through a ring of workers (thread + stream + page-locked staging + device staging each)
 static int host_thread_count(const xsw_ctx *c)
 {

@@ -247,10 +247,18 @@ struct UncArgs {
     double dsig_co, dsig_cr_scalar;
     int is_db;
 };
+
+// The arguments of k_lut_eval_co / k_lut_eval_cr (xsw_forward.hpp; xsw.h: xsw_lut_eval, xsw_lut_eval_cr).
+struct FwdArgs {
+    const void *inc, *wspd, *phi;          // phi: k_lut_eval_co only
+    void *out_db, *out_dwspd, *out_dphi;   // each nullable: reals of the output dtype (k_lut_eval_cr: no out_dphi)
+    long long n;
+    int fold_phi;
+};
 }  // namespace xsw
 
-// The launches of one (input dtype, output dtype) pair: the inversion kernels, k_cross_from_codes, k_cost_co / k_cost_cr and
-// k_unc_co / k_unc_cr.
+// The launches of one (input dtype, output dtype) pair: the inversion kernels, k_cross_from_codes, k_cost_co / k_cost_cr,
+// k_unc_co / k_unc_cr and k_lut_eval_co / k_lut_eval_cr.
 // Each returns an XSW_* code and, with a non-zero one, its message in `err`.  One instance per translation unit
 // (xsw_invert_tu.hip, -DXSW_PAIR=0..3: f32->f32, f32->f64, f64->f32, f64->f64), so that the four sets of kernel
 // instantiations compile side by side; it sits behind a host function, which keeps it out of the device pass.
@@ -259,6 +267,7 @@ struct PairLaunch {
     int (*cross)(xsw_ctx *c, const xsw::CrossArgs &A, hipStream_t stream, std::string &err);
     int (*cost)(xsw_ctx *c, const xsw::CostArgs &A, bool cr, hipStream_t stream, std::string &err);
     int (*unc)(xsw_ctx *c, const xsw::UncArgs &A, bool cr, hipStream_t stream, std::string &err);
+    int (*fwd)(xsw_ctx *c, const xsw::FwdArgs &A, bool cr, hipStream_t stream, std::string &err);
 };
 const PairLaunch &xsw_pair_0(), &xsw_pair_1(), &xsw_pair_2(), &xsw_pair_3();
 

@@ -14,6 +14,7 @@
 #include "xsw_cross.hpp"
 #include "xsw_cost.hpp"
 #include "xsw_uncertainty.hpp"
+#include "xsw_forward.hpp"
 
 using namespace xsw;
 
@@ -93,6 +94,7 @@ using TIn = std::conditional_t<(XSW_PAIR & 2) != 0, double, float>;
 using TOut = std::conditional_t<(XSW_PAIR & 1) != 0, double, float>;
 const PairLaunch &XSW_PAIR_NAME(XSW_PAIR)()
 {
-    static const PairLaunch pair = {launch_invert<TIn, TOut>, launch_cross<TIn, TOut>, launch_cost<TIn, TOut>, launch_unc<TIn, TOut>};
+    static const PairLaunch pair = {launch_invert<TIn, TOut>, launch_cross<TIn, TOut>, launch_cost<TIn, TOut>, launch_unc<TIn, TOut>,
+                                    launch_fwd<TIn, TOut>};
     return pair;
 }

@@ -1,10 +1,12 @@
 """windspeed: wind retrieval from sigma0 and models (public names of `xsarsea.windspeed`)."""
 __all__ = ["invert_from_model", "available_models", "get_model", "register_cmod7", "register_pickle_luts", "register_nc_luts",
-           "register_luts", "nesz_flattening", "GmfModel", "Model", "gmfs", "gmfs_impl", "get_dsig", "get_dsig_wspd", "dsig_from_nesz", "invert_copol_codes", "CopolCodes", "InversionCost", "InversionUncertainty"]
+           "register_luts", "nesz_flattening", "GmfModel", "Model", "gmfs", "gmfs_impl", "get_dsig", "get_dsig_wspd", "dsig_from_nesz", "invert_copol_codes", "CopolCodes", "InversionCost", "InversionUncertainty",
+           "simulate_sigma0", "SimulatedSigma0"]
 
 from . import gmfs, gmfs_impl
 from .cmod7 import register_cmod7
 from .crosspol import CopolCodes, InversionCost, InversionUncertainty, invert_copol_codes
+from .forward import SimulatedSigma0, simulate_sigma0
 from .gmfs import GmfModel
 from .models import Model, available_models, get_model, register_luts, register_nc_luts
 from .pickle_luts import register_pickle_luts

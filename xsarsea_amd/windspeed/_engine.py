@@ -538,6 +538,47 @@ def uncertainty_cr_from_codes(lut_co, lut_cr, plan, codes_co, codes_cr, inc, sig
     return outs
 
 
+def _lut_eval(lut, cross, plan, rasters, n_out, out_dtype, call):
+    """The host path of `lut_eval` / `lut_eval_cr`, in the manner of `_HostCodes` / `_DeviceCodes`: the rasters as the kernel reads
+    them (`plan.dtype`, contiguous), `n_out` outputs of `out_dtype`, the LUT installed in its slot, then
+    call(ctx, mem, input addresses, output addresses).  numpy rasters: host memory, synchronous, under the context's lock;
+    device rasters: torch outputs, asynchronous on torch's current stream."""
+    luts = (None, lut) if cross else (lut, None)
+    if _device.is_device_array(rasters[0]):
+        import torch
+        dev = _device.device_of(*rasters)
+        t = [_device.prep(_device.as_tensor(a, dev), plan.dtype, plan.shape) for a in rasters]
+        outs = [torch.empty(plan.shape, dtype=_device.torch_dtype(out_dtype), device=dev) for _ in range(n_out)]
+        if plan.n:
+            ctx = _device.context_of(dev)
+            with _device.on_current_stream(ctx, dev):
+                ensure_luts(ctx, *luts)
+                call(ctx, _lib.MEM_DEVICE, [_device.at(x) for x in t], [_device.at(o) for o in outs])
+                _device.keep_alive(t, dev)
+        return outs
+    t = [np.ascontiguousarray(a, dtype=plan.dtype) for a in rasters]
+    outs = [np.empty(plan.shape, out_dtype) for _ in range(n_out)]
+    if plan.n:
+        ctx = _lib.default_context(options.device)
+        with ctx.lock:
+            ensure_luts(ctx, *luts)
+            call(ctx, _lib.MEM_HOST, [x.ctypes.data for x in t], [o.ctypes.data for o in outs])
+    return outs
+
+
+def lut_eval(lut_co, plan, inc, wspd, phi, fold_phi=True, jacobian=False, out_dtype=np.float64):
+    """[sigma0_db] or, jacobian=True, [sigma0_db, dwspd, dphi] (`out_dtype`; numpy, or torch for device rasters) that the co-pol
+    dB LUT `lut_co` predicts for the wind (wspd, phi) at `inc` (xsw_lut_eval; `plan` a `_plan.ForwardPlan` of the three)."""
+    return _lut_eval(lut_co, False, plan, (inc, wspd, phi), 3 if jacobian else 1, out_dtype, lambda ctx, mem, ins, outs: ctx.lut_eval_raw(
+        plan.lines, plan.samples, plan.code, _real_code(out_dtype), mem, *ins, *outs, fold_phi=fold_phi))
+
+
+def lut_eval_cr(lut_cr, plan, inc, wspd, jacobian=False, out_dtype=np.float64):
+    """[sigma0_db] or [sigma0_db, dwspd] of the cross-pol dB LUT `lut_cr`, which has no direction (xsw_lut_eval_cr)."""
+    return _lut_eval(lut_cr, True, plan, (inc, wspd), 2 if jacobian else 1, out_dtype, lambda ctx, mem, ins, outs: ctx.lut_eval_cr_raw(
+        plan.lines, plan.samples, plan.code, _real_code(out_dtype), mem, *ins, *outs))
+
+
 def _uploaded_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc):
     """`_device_rasters` for a tile of numpy rasters, which follow `invert_numpy`'s arithmetic: (plan, device, tensors, src).
     With host dB the linear sigma0 stays on the host -- `src` {STAGE_*: flat raster}, converted piece by piece on its way up,

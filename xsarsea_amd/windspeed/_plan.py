@@ -57,3 +57,22 @@ class CallPlan:
         self.out_code, self.out_item = (_lib.XSW_F32, 8) if self.out_dtype == np.complex64 else (_lib.XSW_F64, 16)
         self.algo = _lib.algo_code(options.algo)
         self.fused_select = bool(dual_select and device and self.want_co and self.want_cr)
+
+
+class ForwardPlan:
+    """One `xsw_lut_eval` / `xsw_lut_eval_cr` call from metadata only: inc, wspd, phi (None for a cross-pol table) as (shape, dtype),
+    all of one shape.  Every raster float32: the kernel reads them as such and widens in registers; else everything is float64."""
+
+    def __init__(self, inc, wspd, phi=None):
+        rasters = [m for m in (inc, wspd, phi) if m is not None]
+        shapes = {tuple(m[0]) for m in rasters}
+        if len(shapes) != 1:
+            raise ValueError(f"inc, wspd and phi must have one shape, not {sorted(shapes)}")
+        for m in rasters:
+            if np.dtype(m[1]) not in (np.dtype(np.float32), np.dtype(np.float64)):
+                raise TypeError(f"rasters must be float32 or float64, not {np.dtype(m[1]).name}")
+        self.shape = shapes.pop()
+        self.n = int(np.prod(self.shape, dtype=np.int64))
+        self.lines, self.samples = _lib.lines_samples(self.shape)
+        f32 = all(np.dtype(m[1]) == np.float32 for m in rasters)
+        self.dtype, self.code = (np.float32, _lib.XSW_F32) if f32 else (np.float64, _lib.XSW_F64)

@@ -180,7 +180,9 @@ class Model:
 
 
 class LutModel(Model):
-    """Model defined by a stored table; evaluation = multilinear interpolation of the table."""
+    """Model defined by a stored table; evaluation = multilinear interpolation of the table: scalars and 1-D arrays on the host
+    (three 1-D arrays: their outer product, as the reference's `lut.interp`), rasters of one shape pointwise on the device
+    (`forward.lut_model_rasters`; dB tables)."""
 
     _name_prefix = "nc_lut_"
     _priority = None
@@ -190,7 +192,12 @@ class LutModel(Model):
         all_scalar = all(np.isscalar(v) for v in vals)
         all_1d = not all_scalar and all(getattr(v, "ndim", None) == 1 for v in vals)
         if not (all_scalar or all_1d):
-            raise NotImplementedError("Only scalar or 1D array are implemented for LutModel")
+            from . import forward
+            if not forward.same_shape_rasters(vals):
+                raise NotImplementedError("Only scalar or 1D array are implemented for LutModel")
+            # rasters: pointwise, on the device (`forward`), plain `interp` semantics: no fold of the direction, NaN outside
+            kwargs.pop("broadcast", None)
+            return forward.lut_model_rasters(self, inc, wspd, phi, units, kwargs)
         kwargs.pop("broadcast", None)
         lut = self._lut(units=units, **kwargs)
         # plain `lut.interp(...)` in the reference (models.py:330-346): points outside the table are NaN, not an error
