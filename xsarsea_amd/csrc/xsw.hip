@@ -496,39 +496,21 @@ static void ensure_list(xsw_ctx *c, long long n, long long lines)
     if (c->lists.base) { c->lists.list_cap = want; c->lists.mask_strips = want_strips; }
 }
 
-// ---- grid codes -> complex winds (xsw.h: xsw_expand_codes)
+// ---- grid codes -> complex winds (xsw.h: xsw_expand_codes; the codes and their winds: xsw_codes.hpp, expand_co / expand_cr)
 template <typename TO>
 __global__ __launch_bounds__(256) void k_expand(const double *__restrict__ sol, const double *__restrict__ dual_dir, const double *__restrict__ wcr,
                                                 long long plane, int n_wcr, long long n, const unsigned *__restrict__ cc, const unsigned *__restrict__ cr,
                                                 typename Cx<TO>::type *__restrict__ out_co, typename Cx<TO>::type *__restrict__ out_cr)
 {
     typedef typename Cx<TO>::type cx_t;
-    const double nan = __builtin_nan("");
+    const auto read = [](const double *table, long long k) { const double2 z = ((const double2 *)table)[k]; return Wind{z.x, z.y}; };
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const unsigned a = cc ? cc[i] : K_CODE_NAN;
-        double co_re = nan, co_im = nan;
-        bool have_co = false;
-        long long k = 0;
-        if (a == K_CODE_NAN_RE) co_im = 0.0;
-        else if (!(a & 0x80000000u) && (long long)(a & 0x3FFFFFFFu) < plane) {  // anything else (XSW_CODE_NAN, or not a code of this LUT): (nan, nan)
-            k = (long long)(a & 0x3FFFFFFFu) + (long long)((a >> 30) & 1u) * plane;
-            const double2 z = ((const double2 *)sol)[k];
-            co_re = z.x; co_im = z.y;
-            have_co = true;
-        }
-        if (out_co) { cx_t z; z.x = (TO)co_re; z.y = (TO)co_im; out_co[i] = z; }
+        Wind co;
+        const CoPoint p = expand_co(cc ? cc[i] : XSW_CODE_NAN, plane, sol, read, co);
+        if (out_co) { cx_t z; z.x = (TO)co.re; z.y = (TO)co.im; out_co[i] = z; }
         if (out_cr && cr) {
-            const unsigned b = cr[i];
-            double re = nan, im = nan;
-            if (b == K_CODE_NAN_RE) im = 0.0;
-            else if (b & 0x80000000u) { }
-            else if (b & K_CODE_PICK_CO) { re = co_re; im = co_im; }
-            else if ((int)(b & K_CODE_NO_INDEX) < n_wcr) {
-                const double wd = wcr[b & K_CODE_NO_INDEX];
-                if (have_co) { const double2 u = ((const double2 *)dual_dir)[k]; re = wd * u.x; im = wd * u.y + 0.0 * u.x; }
-                else { re = wd; im = 0.0; }
-            }
-            cx_t z; z.x = (TO)re; z.y = (TO)im; out_cr[i] = z;
+            const Wind dual = expand_cr(cr[i], p, co, n_wcr, dual_dir, wcr, read);
+            cx_t z; z.x = (TO)dual.re; z.y = (TO)dual.im; out_cr[i] = z;
         }
     }
 }
@@ -546,44 +528,24 @@ template <typename TO>
 static void expand_host(const xsw_ctx *c, size_t n, const uint32_t *cc, const uint32_t *cr, TO *out_co, TO *out_cr, int32_t *idx)
 {
     typedef TO cx_t __attribute__((ext_vector_type(2)));
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    const size_t plane = (size_t)c->T.n_w * c->T.n_phi;
+    const long long plane = (long long)c->T.n_w * c->T.n_phi, n_wcr = (long long)c->h_wcr.size();
     const int nP = c->T.n_phi;
-    const double *sol = c->h_sol.data(), *dual = c->h_dual.data(), *wcr = c->h_wcr.data();
-    const size_t n_wcr = c->h_wcr.size();
+    const auto read = [](const double *table, long long k) { return Wind{table[2 * k], table[2 * k + 1]}; };
     for (size_t i = 0; i < n; ++i) {
-        const uint32_t a = cc ? cc[i] : XSW_CODE_NAN;
-        double co_re = nan, co_im = nan;
-        bool have_co = false;
-        size_t k = 0;
-        if (a == XSW_CODE_NAN_RE) co_im = 0.0;
-        else if (!(a & 0x80000000u) && (size_t)(a & 0x3FFFFFFFu) < plane) {  // anything else (XSW_CODE_NAN, or not a code of this LUT): (nan, nan)
-            k = (size_t)(a & 0x3FFFFFFFu) + (size_t)((a >> 30) & 1u) * plane;
-            co_re = sol[2 * k]; co_im = sol[2 * k + 1];
-            have_co = true;
-        }
-        if (out_co) { cx_t z; z.x = (TO)co_re; z.y = (TO)co_im; stream_store((cx_t *)(out_co + 2 * i), z); }
-        uint32_t b = XSW_CODE_NO_INDEX;
-        if (cr) {
-            b = cr[i];
-            if (out_cr) {
-                double re = nan, im = nan;
-                if (b == XSW_CODE_NAN_RE) im = 0.0;
-                else if (b & 0x80000000u) { }
-                else if (b & XSW_CODE_PICK_CO) { re = co_re; im = co_im; }
-                else if ((size_t)(b & XSW_CODE_NO_INDEX) < n_wcr) {
-                    const double wd = wcr[b & XSW_CODE_NO_INDEX];
-                    if (have_co) { const double ux = dual[2 * k], uy = dual[2 * k + 1]; re = wd * ux; im = wd * uy + 0.0 * ux; }
-                    else { re = wd; im = 0.0; }
-                }
-                cx_t z; z.x = (TO)re; z.y = (TO)im; stream_store((cx_t *)(out_cr + 2 * i), z);
-            }
+        Wind co;
+        const unsigned a = cc ? cc[i] : XSW_CODE_NAN;
+        const CoPoint p = expand_co(a, plane, c->h_sol.data(), read, co);
+        if (out_co) { cx_t z; z.x = (TO)co.re; z.y = (TO)co.im; stream_store((cx_t *)(out_co + 2 * i), z); }
+        if (cr && out_cr) {
+            const Wind dual = expand_cr(cr[i], p, co, n_wcr, c->h_dual.data(), c->h_wcr.data(), read);
+            cx_t z; z.x = (TO)dual.re; z.y = (TO)dual.im; stream_store((cx_t *)(out_cr + 2 * i), z);
         }
         if (idx) {
-            const int flat = (int)(a & 0x3FFFFFFFu);
-            idx[3 * i + 0] = have_co ? flat / nP : -1;
-            idx[3 * i + 1] = have_co ? flat % nP : -1;
-            idx[3 * i + 2] = ((b & 0x80000000u) || (b & XSW_CODE_NO_INDEX) == XSW_CODE_NO_INDEX) ? -1 : (int)(b & XSW_CODE_NO_INDEX);
+            const CrCode b = cr_decode(cr ? cr[i] : XSW_CODE_NO_INDEX);
+            const int flat = (int)co_decode(a, plane).flat();
+            idx[3 * i + 0] = p.have ? flat / nP : -1;
+            idx[3 * i + 1] = p.have ? flat % nP : -1;
+            idx[3 * i + 2] = (b.nan_re() || b.foreign() || b.index() == XSW_CODE_NO_INDEX) ? -1 : (int)b.index();
         }
     }
 }
@@ -639,67 +601,74 @@ static int expand_codes_on(xsw_ctx *c, hipStream_t stream, int64_t n, int32_t me
     return XSW_OK;
 }
 
+// ---- the one-pixel-per-lane passes over rasters and the context's tables.  Every entry: check_raster_call, its own refusals,
+// pixel_count (xsw_run.hpp), then run(); every check comes before any launch.
+// queue(member, A, cr...): the launch of PairLaunch `member` on the context's stream, its message moved into c->err
+template <typename Member, typename Args, typename... Cr>
+static int queue(xsw_ctx *c, int32_t dtype, int32_t out_dtype, Member member, const Args &A, Cr... cr)
+{
+    std::string err;
+    const int rc = (pair_launch(dtype, out_dtype).*member)(c, A, cr..., c->stream, err);
+    return rc ? fail(c, rc, "%s", err.c_str()) : XSW_OK;
+}
+
 // ---- the cross-pol step from stored co-pol codes (xsw.h: xsw_cross_from_codes; kernel: xsw_cross.hpp)
 extern "C" int xsw_cross_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
                                     int32_t sigma0_is_db, int32_t dual_select, const void *inc, const uint32_t *code_co,
                                     const void *sigma0_cr, const void *dsig_cr, double dsig_cr_scalar, uint32_t *out_code_cr, void *out_cr)
 {
     if (!c) return XSW_EINVAL;
-    if (lines < 0 || samples < 0) return fail(c, XSW_EINVAL, "negative raster shape");
-    if ((dtype != XSW_F32 && dtype != XSW_F64) || (out_dtype != XSW_F32 && out_dtype != XSW_F64))
-        return fail(c, XSW_EINVAL, "dtype/out_dtype must be XSW_F32 or XSW_F64");
-    if (mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE) return fail(c, XSW_EINVAL, "bad mem kind");
+    if (int rc = check_raster_call(c, lines, samples, dtype, out_dtype, mem)) return rc;
     if (!inc || !sigma0_cr) return fail(c, XSW_EINVAL, "cross_from_codes: inc or sigma0_cr is NULL");
     if (!out_code_cr && !out_cr) return fail(c, XSW_EINVAL, "cross_from_codes: neither out_code_cr nor out_cr given");
     if (!c->have_cr) return fail(c, XSW_ENOLUT, "cross_from_codes: no cross-pol LUT uploaded");
     if (code_co && !c->have_co) return fail(c, XSW_ENOLUT, "co-pol codes given but no co-pol LUT on this context");
-    if (lines && samples > (int64_t)(0x7fffffffLL * 256) / lines)  // (no overflow of lines * samples; one launch of 256-pixel blocks)
-        return fail(c, XSW_EINVAL, "cross_from_codes: raster too large for one launch");
-    const long long n = (long long)lines * samples;
+    long long n;
+    size_t es, os;
+    if (int rc = pixel_count(c, "cross_from_codes", lines, samples, dtype, out_dtype, n, es, os)) return rc;
     if (n == 0) return XSW_OK;
-    const size_t es = dtype == XSW_F32 ? 4 : 8, os = out_dtype == XSW_F32 ? 8 : 16, px = (size_t)n;
+    const size_t px = (size_t)n;
     Buf b[6] = {in_buf(inc, px * es), in_buf(sigma0_cr, px * es), in_buf(dsig_cr, px * es), in_buf(code_co, px * 4),
-                out_buf(out_code_cr, px * 4), out_buf(out_cr, px * os)};
+                out_buf(out_code_cr, px * 4), out_buf(out_cr, px * os * 2)};
     return run(c, mem, b, [&](Buf (&x)[6]) {
         const CrossArgs A{x[0].dev, x[1].dev, x[2].dev, (const unsigned *)x[3].dev, (unsigned *)x[4].dev, x[5].dev, n, dsig_cr_scalar,
                           sigma0_is_db, dual_select};
-        std::string err;
-        const int rc = pair_launch(dtype, out_dtype).cross(c, A, c->stream, err);
-        return rc ? fail(c, rc, "%s", err.c_str()) : XSW_OK;
+        return queue(c, dtype, out_dtype, &PairLaunch::cross, A);
     }, "cross_from_codes");
 }
 
-// ---- inversion cost and sigma0 residual from stored codes (xsw.h: xsw_cost_from_codes, xsw_cost_cr_from_codes; kernels: xsw_cost.hpp)
-// One body for the two entries: A holds the caller's pointers (cr: the cross-pol entry); every check comes before any launch.
-static int cost_from_codes(xsw_ctx *c, const char *who, bool cr, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype,
-                           int32_t mem, CostArgs A)
+// ---- inversion cost / sigma0 residual and wind uncertainty from stored codes (xsw.h: xsw_cost_from_codes, xsw_cost_cr_from_codes,
+// xsw_uncertainty_from_codes, xsw_uncertainty_cr_from_codes; kernels: xsw_cost.hpp, xsw_uncertainty.hpp).  One body for the four
+// entries: A holds the caller's pointers (cr: a cross-pol entry), `outs` names A's four outputs, the last of last_elem bytes per
+// pixel (0: a real of the output dtype, as the other three), `member` is the PairLaunch entry that runs.
+template <typename Args>
+static int pass_from_codes(xsw_ctx *c, const char *who, bool cr, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                           Args A, void *Args::*const (&outs)[4], size_t last_elem,
+                           int (*PairLaunch::*member)(xsw_ctx *, const Args &, bool, hipStream_t, std::string &))
 {
-    if (lines < 0 || samples < 0) return fail(c, XSW_EINVAL, "negative raster shape");
-    if ((dtype != XSW_F32 && dtype != XSW_F64) || (out_dtype != XSW_F32 && out_dtype != XSW_F64))
-        return fail(c, XSW_EINVAL, "dtype/out_dtype must be XSW_F32 or XSW_F64");
-    if (mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE) return fail(c, XSW_EINVAL, "bad mem kind");
+    if (int rc = check_raster_call(c, lines, samples, dtype, out_dtype, mem)) return rc;
     if (!A.inc || !A.s || (cr ? !A.code_cr : (!A.code_co || !A.anc))) return fail(c, XSW_EINVAL, "%s: an input raster is NULL", who);
-    if (!A.out_J && !A.out_Jsig && !A.out_Jwind && !A.out_res) return fail(c, XSW_EINVAL, "%s: no output requested", who);
+    if (!(A.*outs[0]) && !(A.*outs[1]) && !(A.*outs[2]) && !(A.*outs[3])) return fail(c, XSW_EINVAL, "%s: no output requested", who);
     if (cr ? !c->have_cr : !c->have_co) return fail(c, XSW_EINVAL, "%s: no %s LUT installed", who, cr ? "cross-pol" : "co-pol");
     if (cr && A.code_co && !c->have_co) return fail(c, XSW_EINVAL, "%s: co-pol codes given but no co-pol LUT installed", who);
     if (!cr && (A.dsig_co != A.dsig_co || A.dsig_co == 0.0)) return fail(c, XSW_EINVAL, "%s: dsig_co is NaN or 0", who);
-    if (lines && samples > (int64_t)(0x7fffffffLL * 256) / lines)  // (no overflow of lines * samples; one launch of 256-pixel blocks)
-        return fail(c, XSW_EINVAL, "%s: raster too large for one launch", who);
-    A.n = (long long)lines * samples;
+    size_t es, os;
+    if (int rc = pixel_count(c, who, lines, samples, dtype, out_dtype, A.n, es, os)) return rc;
     if (A.n == 0) return XSW_OK;
-    const size_t es = dtype == XSW_F32 ? 4 : 8, os = out_dtype == XSW_F32 ? 4 : 8, px = (size_t)A.n;
+    const size_t px = (size_t)A.n;
     Buf b[10] = {in_buf(A.inc, px * es), in_buf(A.s, px * es), in_buf(A.anc, px * es * 2), in_buf(A.dsig_cr, px * es),
-                 in_buf(A.code_co, px * 4), in_buf(A.code_cr, px * 4), out_buf(A.out_J, px * os), out_buf(A.out_Jsig, px * os),
-                 out_buf(A.out_Jwind, px * os), out_buf(A.out_res, px * os)};
+                 in_buf(A.code_co, px * 4), in_buf(A.code_cr, px * 4), out_buf(A.*outs[0], px * os), out_buf(A.*outs[1], px * os),
+                 out_buf(A.*outs[2], px * os), out_buf(A.*outs[3], px * (last_elem ? last_elem : os))};
     return run(c, mem, b, [&](Buf (&x)[10]) {
         A.inc = x[0].dev; A.s = x[1].dev; A.anc = x[2].dev; A.dsig_cr = x[3].dev;
         A.code_co = (const unsigned *)x[4].dev; A.code_cr = (const unsigned *)x[5].dev;
-        A.out_J = x[6].dev; A.out_Jsig = x[7].dev; A.out_Jwind = x[8].dev; A.out_res = x[9].dev;
-        std::string err;
-        const int rc = pair_launch(dtype, out_dtype).cost(c, A, cr, c->stream, err);
-        return rc ? fail(c, rc, "%s", err.c_str()) : XSW_OK;
+        for (int k = 0; k < 4; ++k) A.*outs[k] = x[6 + k].dev;
+        return queue(c, dtype, out_dtype, member, A, cr);
     }, who);
 }
+
+static void *CostArgs::*const cost_outs[4] = {&CostArgs::out_J, &CostArgs::out_Jsig, &CostArgs::out_Jwind, &CostArgs::out_res};
+static void *UncArgs::*const unc_outs[4] = {&UncArgs::out_wspd_std, &UncArgs::out_dir_std, &UncArgs::out_corr, &UncArgs::out_flag};
 
 extern "C" int xsw_cost_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
                                    int32_t sigma0_is_db, const void *inc, const uint32_t *code_co, const void *sigma0_co, const void *anc,
@@ -710,7 +679,7 @@ extern "C" int xsw_cost_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, i
     A.inc = inc; A.s = sigma0_co; A.anc = anc; A.code_co = code_co;
     A.out_J = out_J; A.out_Jsig = out_Jsig; A.out_Jwind = out_Jwind; A.out_res = out_residual;
     A.dsig_co = dsig_co; A.is_db = sigma0_is_db;
-    return cost_from_codes(c, "cost_from_codes", false, lines, samples, dtype, out_dtype, mem, A);
+    return pass_from_codes(c, "cost_from_codes", false, lines, samples, dtype, out_dtype, mem, A, cost_outs, 0, &PairLaunch::cost);
 }
 
 extern "C" int xsw_cost_cr_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
@@ -723,39 +692,7 @@ extern "C" int xsw_cost_cr_from_codes(xsw_ctx *c, int64_t lines, int64_t samples
     A.inc = inc; A.s = sigma0_cr; A.dsig_cr = dsig_cr; A.code_co = code_co; A.code_cr = code_cr;
     A.out_J = out_J; A.out_Jsig = out_Jsig; A.out_Jwind = out_Jwind; A.out_res = out_residual;
     A.dsig_cr_scalar = dsig_cr_scalar; A.is_db = sigma0_is_db;
-    return cost_from_codes(c, "cost_cr_from_codes", true, lines, samples, dtype, out_dtype, mem, A);
-}
-
-// ---- wind uncertainty from stored codes (xsw.h: xsw_uncertainty_from_codes, xsw_uncertainty_cr_from_codes; kernels: xsw_uncertainty.hpp)
-// One body for the two entries, as cost_from_codes: A holds the caller's pointers; every check comes before any launch.
-static int uncertainty_from_codes(xsw_ctx *c, const char *who, bool cr, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype,
-                                  int32_t mem, UncArgs A)
-{
-    if (lines < 0 || samples < 0) return fail(c, XSW_EINVAL, "negative raster shape");
-    if ((dtype != XSW_F32 && dtype != XSW_F64) || (out_dtype != XSW_F32 && out_dtype != XSW_F64))
-        return fail(c, XSW_EINVAL, "dtype/out_dtype must be XSW_F32 or XSW_F64");
-    if (mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE) return fail(c, XSW_EINVAL, "bad mem kind");
-    if (!A.inc || !A.s || (cr ? !A.code_cr : (!A.code_co || !A.anc))) return fail(c, XSW_EINVAL, "%s: an input raster is NULL", who);
-    if (!A.out_wspd_std && !A.out_dir_std && !A.out_corr && !A.out_flag) return fail(c, XSW_EINVAL, "%s: no output requested", who);
-    if (cr ? !c->have_cr : !c->have_co) return fail(c, XSW_EINVAL, "%s: no %s LUT installed", who, cr ? "cross-pol" : "co-pol");
-    if (cr && A.code_co && !c->have_co) return fail(c, XSW_EINVAL, "%s: co-pol codes given but no co-pol LUT installed", who);
-    if (!cr && (A.dsig_co != A.dsig_co || A.dsig_co == 0.0)) return fail(c, XSW_EINVAL, "%s: dsig_co is NaN or 0", who);
-    if (lines && samples > (int64_t)(0x7fffffffLL * 256) / lines)  // (no overflow of lines * samples; one launch of 256-pixel blocks)
-        return fail(c, XSW_EINVAL, "%s: raster too large for one launch", who);
-    A.n = (long long)lines * samples;
-    if (A.n == 0) return XSW_OK;
-    const size_t es = dtype == XSW_F32 ? 4 : 8, os = out_dtype == XSW_F32 ? 4 : 8, px = (size_t)A.n;
-    Buf b[10] = {in_buf(A.inc, px * es), in_buf(A.s, px * es), in_buf(A.anc, px * es * 2), in_buf(A.dsig_cr, px * es),
-                 in_buf(A.code_co, px * 4), in_buf(A.code_cr, px * 4), out_buf(A.out_wspd_std, px * os), out_buf(A.out_dir_std, px * os),
-                 out_buf(A.out_corr, px * os), out_buf(A.out_flag, px)};
-    return run(c, mem, b, [&](Buf (&x)[10]) {
-        A.inc = x[0].dev; A.s = x[1].dev; A.anc = x[2].dev; A.dsig_cr = x[3].dev;
-        A.code_co = (const unsigned *)x[4].dev; A.code_cr = (const unsigned *)x[5].dev;
-        A.out_wspd_std = x[6].dev; A.out_dir_std = x[7].dev; A.out_corr = x[8].dev; A.out_flag = (unsigned char *)x[9].dev;
-        std::string err;
-        const int rc = pair_launch(dtype, out_dtype).unc(c, A, cr, c->stream, err);
-        return rc ? fail(c, rc, "%s", err.c_str()) : XSW_OK;
-    }, who);
+    return pass_from_codes(c, "cost_cr_from_codes", true, lines, samples, dtype, out_dtype, mem, A, cost_outs, 0, &PairLaunch::cost);
 }
 
 extern "C" int xsw_uncertainty_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
@@ -768,7 +705,7 @@ extern "C" int xsw_uncertainty_from_codes(xsw_ctx *c, int64_t lines, int64_t sam
     A.inc = inc; A.s = sigma0_co; A.anc = anc; A.code_co = code_co;
     A.out_wspd_std = out_wspd_std; A.out_dir_std = out_dir_std; A.out_corr = out_corr; A.out_flag = out_flag;
     A.dsig_co = dsig_co; A.is_db = sigma0_is_db;
-    return uncertainty_from_codes(c, "uncertainty_from_codes", false, lines, samples, dtype, out_dtype, mem, A);
+    return pass_from_codes(c, "uncertainty_from_codes", false, lines, samples, dtype, out_dtype, mem, A, unc_outs, 1, &PairLaunch::unc);
 }
 
 extern "C" int xsw_uncertainty_cr_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
@@ -781,36 +718,30 @@ extern "C" int xsw_uncertainty_cr_from_codes(xsw_ctx *c, int64_t lines, int64_t 
     A.inc = inc; A.s = sigma0_cr; A.dsig_cr = dsig_cr; A.code_co = code_co; A.code_cr = code_cr;
     A.out_wspd_std = out_wspd_std; A.out_flag = out_flag;
     A.dsig_cr_scalar = dsig_cr_scalar; A.is_db = sigma0_is_db;
-    return uncertainty_from_codes(c, "uncertainty_cr_from_codes", true, lines, samples, dtype, out_dtype, mem, A);
+    return pass_from_codes(c, "uncertainty_cr_from_codes", true, lines, samples, dtype, out_dtype, mem, A, unc_outs, 1, &PairLaunch::unc);
 }
 
 // ---- the forward operator on rasters (xsw.h: xsw_lut_eval, xsw_lut_eval_cr; kernels: xsw_forward.hpp)
-// One body for the two entries, as cost_from_codes: A holds the caller's pointers; every check comes before any launch.
+// One body for the two entries: A holds the caller's pointers.
 static int lut_eval(xsw_ctx *c, const char *who, bool cr, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
                     FwdArgs A)
 {
-    if (lines < 0 || samples < 0) return fail(c, XSW_EINVAL, "negative raster shape");
-    if ((dtype != XSW_F32 && dtype != XSW_F64) || (out_dtype != XSW_F32 && out_dtype != XSW_F64))
-        return fail(c, XSW_EINVAL, "dtype/out_dtype must be XSW_F32 or XSW_F64");
-    if (mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE) return fail(c, XSW_EINVAL, "bad mem kind");
+    if (int rc = check_raster_call(c, lines, samples, dtype, out_dtype, mem)) return rc;
     if (!A.inc || !A.wspd || (!cr && !A.phi)) return fail(c, XSW_EINVAL, "%s: an input raster is NULL", who);
     if (!A.out_db && !A.out_dwspd && !A.out_dphi) return fail(c, XSW_EINVAL, "%s: no output requested", who);
     if (cr ? !c->have_cr : !c->have_co) return fail(c, XSW_ENOLUT, "%s: no %s LUT installed", who, cr ? "cross-pol" : "co-pol");
     if (cr ? (c->T.n_inc_cr < 2 || c->T.n_wcr < 2) : (c->T.n_inc < 2 || c->T.n_w < 2 || c->T.n_phi < 2))  // (no cell to interpolate in)
         return fail(c, XSW_EINVAL, "%s: an axis of the %s LUT has fewer than two points", who, cr ? "cross-pol" : "co-pol");
-    if (lines && samples > (int64_t)(0x7fffffffLL * 256) / lines)  // (no overflow of lines * samples; one launch of 256-pixel blocks)
-        return fail(c, XSW_EINVAL, "%s: raster too large for one launch", who);
-    A.n = (long long)lines * samples;
+    size_t es, os;
+    if (int rc = pixel_count(c, who, lines, samples, dtype, out_dtype, A.n, es, os)) return rc;
     if (A.n == 0) return XSW_OK;
-    const size_t es = dtype == XSW_F32 ? 4 : 8, os = out_dtype == XSW_F32 ? 4 : 8, px = (size_t)A.n;
+    const size_t px = (size_t)A.n;
     Buf b[6] = {in_buf(A.inc, px * es), in_buf(A.wspd, px * es), in_buf(A.phi, px * es),
                 out_buf(A.out_db, px * os), out_buf(A.out_dwspd, px * os), out_buf(A.out_dphi, px * os)};
     return run(c, mem, b, [&](Buf (&x)[6]) {
         A.inc = x[0].dev; A.wspd = x[1].dev; A.phi = x[2].dev;
         A.out_db = x[3].dev; A.out_dwspd = x[4].dev; A.out_dphi = x[5].dev;
-        std::string err;
-        const int rc = pair_launch(dtype, out_dtype).fwd(c, A, cr, c->stream, err);
-        return rc ? fail(c, rc, "%s", err.c_str()) : XSW_OK;
+        return queue(c, dtype, out_dtype, &PairLaunch::fwd, A, cr);
     }, who);
 }
 

@@ -369,7 +369,7 @@ __device__ __forceinline__ void wave_tail(const DevTables &L, const KArgs &A, lo
         const double inc = ld<T>(A.inc, i);
         const T x = ((const T *)A.s_cr)[i];
         const double s_cr = to_db(x, A.is_db);
-        const double dsig = A.dsig_cr ? (double)((const T *)A.dsig_cr)[i] : (double)(T)(x * (T)0 + (T)A.dsig_cr_scalar);
+        const double dsig = dsig_cr_at<T>(A.dsig_cr, i, x, A.dsig_cr_scalar);
         need_cr = in && !(flags & (F_EARLY_NAN | F_CR_RAW_NAN)) && s_cr == s_cr && dsig == dsig;
         const bool here = need_cr && !unresolved;
         const int i_inc_cr = here ? nearest_index(L.inc_cr, L.n_inc_cr, inc, L.inc_cr_uniform != 0, L.inc_cr0, L.inv_inccrstep) : 0;

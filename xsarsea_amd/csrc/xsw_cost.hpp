@@ -18,15 +18,9 @@
 // J = Jsig.  A NaN sigma0 / ancillary wind / dsig_cr next to a code that names a grid point gives NaN by the arithmetic.
 #pragma once
 #include "xsw_device.hpp"  // DevTables, to_db, nearest_index, ld, Cx
-#include "xsw_host.hpp"    // xsw_ctx, CostArgs, seterr
+#include "xsw_host.hpp"    // CostArgs
 
 namespace xsw {
-
-template <typename TO>
-__device__ __forceinline__ void cost_store(void *out, long long i, double v)
-{
-    if (out) ((TO *)out)[i] = (TO)v;
-}
 
 // J_co of windspeed.py:216-225 at grid point (iw, ip) of incidence slice i_inc, with its terms and lut_db - sigma0_db: the ONE
 // statement of the co-pol cost from stored codes (k_cost_co: at the code's point; k_unc_co, xsw_uncertainty.hpp: at its nine
@@ -77,27 +71,21 @@ __global__ __launch_bounds__(256, 8) void k_cost_co(DevTables L, CostArgs A)
     if (i >= A.n) return;
     const double nan = __builtin_nan("");
     const bool want_wind = A.out_J || A.out_Jwind, want_sig = A.out_J || A.out_Jsig;  // (uniform)
-    const unsigned code = A.code_co[i];
+    const CoCode code = co_decode(A.code_co[i], (unsigned)(L.n_w * L.n_phi));
     const double inc = ld<T>(A.inc, i);
     const double s_db = to_db(((const T *)A.s)[i], A.is_db);
     double a = 0.0, b = 0.0;
-    if (want_wind) {
-        const typename Cx<T>::type z = ((const typename Cx<T>::type *)A.anc)[i];
-        a = (double)z.x;
-        b = L.phi_180 ? fabs((double)z.y) : (double)z.y;  // windspeed.py:218-219
-    }
-    const unsigned plane = (unsigned)(L.n_w * L.n_phi), flat = code & 0x3FFFFFFFu;
-    const bool grid_code = !(code & 0x80000000u) && flat < plane;
+    if (want_wind) anc_at<T>(A.anc, i, L.phi_180, a, b);
     double J = nan, Jsig = nan, Jwind = nan, res = nan;
-    if (grid_code && inc == inc) {
+    if (code.grid() && inc == inc) {
         const int i_inc = nearest_index(L.inc, L.n_inc, inc, L.inc_uniform != 0, L.inc0, L.inv_incstep);
-        const int iw = (int)(flat / (unsigned)L.n_phi), ip = (int)(flat - (unsigned)iw * (unsigned)L.n_phi);
+        const int iw = (int)(code.flat() / (unsigned)L.n_phi), ip = (int)(code.flat() - (unsigned)iw * (unsigned)L.n_phi);
         J = cost_co_at(L, i_inc, iw, ip, s_db, a, b, A.dsig_co, want_wind, want_sig, Jsig, Jwind, res);
     }
-    cost_store<TO>(A.out_J, i, J);
-    cost_store<TO>(A.out_Jsig, i, Jsig);
-    cost_store<TO>(A.out_Jwind, i, Jwind);
-    cost_store<TO>(A.out_res, i, res);
+    store_opt<TO>(A.out_J, i, J);
+    store_opt<TO>(A.out_Jsig, i, Jsig);
+    store_opt<TO>(A.out_Jwind, i, Jwind);
+    store_opt<TO>(A.out_res, i, res);
 }
 
 // cross-pol: windspeed.py:254-264 at i_wspd_cr = the code's index; have_co / |wind_co| from the co-pol code as in k_cross_from_codes
@@ -108,38 +96,23 @@ __global__ __launch_bounds__(256, 8) void k_cost_cr(DevTables L, CostArgs A)
     if (i >= A.n) return;
     const double nan = __builtin_nan("");
     const bool want_wind = A.out_J || A.out_Jwind, want_sig = A.out_J || A.out_Jsig;  // (uniform)
-    const unsigned code_cr = A.code_cr[i];
-    const unsigned code = (A.code_co && want_wind) ? A.code_co[i] : K_CODE_NAN;
+    const CrCode code_cr = cr_decode(A.code_cr[i]);
+    const CoCode code = co_decode((A.code_co && want_wind) ? A.code_co[i] : XSW_CODE_NAN, (unsigned)(L.n_w * L.n_phi));
     const double inc = ld<T>(A.inc, i);
     const T x = ((const T *)A.s)[i];
     const double s_db = to_db(x, A.is_db);
     double dsig = nan;
-    if (want_sig) dsig = A.dsig_cr ? (double)((const T *)A.dsig_cr)[i] : (double)(T)(x * (T)0 + (T)A.dsig_cr_scalar);  // windspeed.py:122-123
-    const unsigned icr = code_cr & K_CODE_NO_INDEX;
-    const bool searched = code_cr != K_CODE_NAN_RE && icr != K_CODE_NO_INDEX && icr < (unsigned)L.n_wcr && inc == inc;
+    if (want_sig) dsig = dsig_cr_at<T>(A.dsig_cr, i, x, A.dsig_cr_scalar);
+    const bool searched = cr_index_lenient(code_cr, (unsigned)L.n_wcr) && inc == inc;
     double J = nan, Jsig = nan, Jwind = nan, res = nan;
     if (searched) {
         const int i_inc_cr = nearest_index(L.inc_cr, L.n_inc_cr, inc, L.inc_cr_uniform != 0, L.inc_cr0, L.inv_inccrstep);
-        const unsigned plane = (unsigned)(L.n_w * L.n_phi), flat = code & 0x3FFFFFFFu;
-        const bool have_co = !(code & 0x80000000u) && flat < plane;  // (the incidence is not NaN here)
-        J = cost_cr_at(L, i_inc_cr, icr, s_db, dsig, have_co, flat, want_wind, want_sig, Jsig, Jwind, res);
+        J = cost_cr_at(L, i_inc_cr, code_cr.index(), s_db, dsig, code.grid(), code.flat(), want_wind, want_sig, Jsig, Jwind, res);
     }
-    cost_store<TO>(A.out_J, i, J);
-    cost_store<TO>(A.out_Jsig, i, Jsig);
-    cost_store<TO>(A.out_Jwind, i, Jwind);
-    cost_store<TO>(A.out_res, i, res);
-}
-
-template <typename T, typename TO>
-static int launch_cost(xsw_ctx *c, const CostArgs &A, bool cr, hipStream_t stream, std::string &err)
-{
-    const long long nblocks = (A.n + 255) / 256;
-    if (nblocks > 0x7fffffffLL) return seterr(err, XSW_EINVAL, "raster too large for one launch");
-    if (cr) hipLaunchKernelGGL((k_cost_cr<T, TO>), dim3((unsigned)nblocks), dim3(256), 0, stream, c->T, A);
-    else hipLaunchKernelGGL((k_cost_co<T, TO>), dim3((unsigned)nblocks), dim3(256), 0, stream, c->T, A);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return seterr(err, XSW_EHIP, "launch failed: %s", hipGetErrorString(e));
-    return XSW_OK;
+    store_opt<TO>(A.out_J, i, J);
+    store_opt<TO>(A.out_Jsig, i, Jsig);
+    store_opt<TO>(A.out_Jwind, i, Jwind);
+    store_opt<TO>(A.out_res, i, res);
 }
 
 }  // namespace xsw

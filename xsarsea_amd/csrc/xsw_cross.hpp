@@ -14,7 +14,7 @@
 // beyond n_wspd * n_phi: codes of another LUT, stale memory) reads no table: the pixel is handled as XSW_CODE_NAN_RE.
 #pragma once
 #include "xsw_device.hpp"  // DevTables, to_db, nearest_index, the search_cr_* and exact_scan_cr of invert_strip, Cx
-#include "xsw_host.hpp"    // xsw_ctx, CrossArgs, seterr
+#include "xsw_host.hpp"    // CrossArgs
 
 namespace xsw {
 
@@ -31,18 +31,17 @@ __global__ __launch_bounds__(256, 8) void k_cross_from_codes(DevTables L, CrossA
 
     // ---- load_pixel's cross-pol half (windspeed.py:198-209, :252-254), the co-pol half replaced by the code
     const double inc = ld<T>(A.inc, il);
-    const unsigned code = A.code_co ? A.code_co[il] : K_CODE_NAN;
+    const CoCode code = co_decode(A.code_co ? A.code_co[il] : XSW_CODE_NAN, (unsigned)(L.n_w * L.n_phi));
     const T x = ((const T *)A.s_cr)[il];
     const double s_cr = to_db(x, A.is_db);
-    const double dsig = A.dsig_cr ? (double)((const T *)A.dsig_cr)[il] : (double)(T)(x * (T)0 + (T)A.dsig_cr_scalar);
-    const unsigned plane = (unsigned)(L.n_w * L.n_phi), flat = code & 0x3FFFFFFFu;
-    const bool grid_code = !(code & 0x80000000u) && flat < plane;
-    const bool early = inc != inc || (code != K_CODE_NAN && !grid_code);  // XSW_CODE_NAN_RE, or no code of this LUT
-    const bool have_co = !early && grid_code;
+    const double dsig = dsig_cr_at<T>(A.dsig_cr, il, x, A.dsig_cr_scalar);
+    const bool grid = code.grid();
+    const bool early = inc != inc || (code.code != XSW_CODE_NAN && !grid);  // XSW_CODE_NAN_RE, or no code of this LUT
+    const bool have_co = !early && grid;
     const bool need = in && !early && s_cr == s_cr && dsig == dsig;
     int i_inc_cr = 0;
     if (need) i_inc_cr = nearest_index(L.inc_cr, L.n_inc_cr, inc, L.inc_cr_uniform != 0, L.inc_cr0, L.inv_inccrstep);
-    const double aco = have_co ? L.abs_co[flat] : nan;  // np.abs(wind_co)
+    const double aco = have_co ? L.abs_co[code.flat()] : nan;  // np.abs(wind_co)
 
     // ---- the search of invert_strip (windspeed.py:255-269): one pixel per lane, the undecided ones cooperatively
     int icr = 0;
@@ -64,7 +63,7 @@ __global__ __launch_bounds__(256, 8) void k_cross_from_codes(DevTables L, CrossA
     if (!in) return;
 
     // ---- store_pixel's cross-pol half (windspeed.py:269-278, select :426-428)
-    const size_t k_co = (size_t)flat + (size_t)((code >> 30) & 1u) * plane;  // [sign][i_wspd][i_phi] of dual_dir and sol
+    const size_t k_co = (size_t)code.k();  // [sign][i_wspd][i_phi] of dual_dir and sol
     double cr_re = nan, cr_im = early ? 0.0 : nan;
     if (need) {
         const double wd = L.wcr[icr];
@@ -94,18 +93,7 @@ __global__ __launch_bounds__(256, 8) void k_cross_from_codes(DevTables L, CrossA
         cx_t z; z.x = (TO)cr_re; z.y = (TO)cr_im;
         ((cx_t *)A.out_cr)[i] = z;
     }
-    if (A.code_cr) A.code_cr[i] = early ? K_CODE_NAN_RE : ((need ? (unsigned)icr : K_CODE_NO_INDEX) | (picked_co ? K_CODE_PICK_CO : 0u));
-}
-
-template <typename T, typename TO>
-static int launch_cross(xsw_ctx *c, const CrossArgs &A, hipStream_t stream, std::string &err)
-{
-    const long long nblocks = (A.n + 255) / 256;
-    if (nblocks > 0x7fffffffLL) return seterr(err, XSW_EINVAL, "raster too large for one launch");
-    hipLaunchKernelGGL((k_cross_from_codes<T, TO>), dim3((unsigned)nblocks), dim3(256), 0, stream, c->T, A);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return seterr(err, XSW_EHIP, "launch failed: %s", hipGetErrorString(e));
-    return XSW_OK;
+    if (A.code_cr) A.code_cr[i] = early ? XSW_CODE_NAN_RE : cr_encode(need ? (unsigned)icr : XSW_CODE_NO_INDEX, picked_co);
 }
 
 }  // namespace xsw

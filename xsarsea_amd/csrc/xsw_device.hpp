@@ -23,6 +23,7 @@
 
 #include <type_traits>
 
+#include "xsw_codes.hpp"    // the grid codes: co_decode / co_encode, cr_decode / cr_encode
 #include "xsw_lutplan.hpp"  // the table shapes (XSW_INV_BINS, XSW_TAIL_LEVELS, XSW_BLK_*, XSW_CELL_*)
 
 namespace xsw {
@@ -116,11 +117,6 @@ struct KArgs {
     double dsig_co, inv_dsig_co, dsig_cr_scalar;
     int is_db, dual_select;
 };
-
-// grid codes (xsw.h): bits 0..29 flat index (i_wspd * n_phi + i_phi; cross-pol: i_wspd_cr), bit 30 the -phi solution
-// (cross-pol: bit 30 = the dual select picked the co-pol wind, index 0x3FFFFFFF = no cross-pol search ran)
-enum : unsigned { K_CODE_NAN_RE = 0xFFFFFFFFu /* (nan, 0) */, K_CODE_NAN = 0xFFFFFFFEu /* (nan, nan) */,
-                  K_CODE_PICK_CO = 0x40000000u, K_CODE_NO_INDEX = 0x3FFFFFFFu };
 
 enum : int { F_NEED_CO = 1, F_NEED_CR = 2, F_EARLY_NAN = 4, F_CO_FINITE = 8, F_CR_RAW_NAN = 16 /* band kernel: a raw cross-pol input is NaN */,
              F_CO_LOOSE = 32 /* general kernel: finite inputs, but a bound far above the scale of the scores: block pyramid, no forward differences */,
@@ -1233,6 +1229,26 @@ template <> struct Cx<double> { typedef double2 type; };
 
 template <typename T> __device__ __forceinline__ double ld(const void *p, long long i) { return (double)((const T *)p)[i]; }
 
+// ---- what the one-pixel-per-lane passes share (load_pixel; xsw_cross.hpp, xsw_cost.hpp, xsw_uncertainty.hpp, xsw_forward.hpp)
+// a real output nobody asked for is null
+template <typename TO> __device__ __forceinline__ void store_opt(void *out, long long i, double v)
+{
+    if (out) ((TO *)out)[i] = (TO)v;
+}
+// dsig_cr of pixel i: the raster's, or the scalar broadcast as sigma0_cr * 0 + dsig_cr in the raster dtype (x: the pixel's raw
+// sigma0_cr; windspeed.py:122-123)
+template <typename T> __device__ __forceinline__ double dsig_cr_at(const void *raster, long long i, T x, double scalar)
+{
+    return raster ? (double)((const T *)raster)[i] : (double)(T)(x * (T)0 + (T)scalar);
+}
+// the ancillary wind of pixel i: a = Re, b = Im, |Im| for a 0..180 LUT (fold; windspeed.py:218-219)
+template <typename T> __device__ __forceinline__ void anc_at(const void *anc, long long i, bool fold, double &a, double &b)
+{
+    const typename Cx<T>::type z = ((const typename Cx<T>::type *)anc)[i];
+    a = (double)z.x;
+    b = fold ? fabs((double)z.y) : (double)z.y;
+}
+
 // ------------------------------------------------------------------------------------------------
 
 // Loads pixel `il` (already clamped in range), converts to dB, classifies it (windspeed.py:198-209,
@@ -1247,14 +1263,9 @@ __device__ __forceinline__ void load_pixel(const DevTables &L, const KArgs &A, l
     if (CR && A.s_cr) {
         const T x = ((const T *)A.s_cr)[il];
         P.s_cr = to_db(x, A.is_db);
-        // scalar dsig_cr is broadcast as sigma0_cr*0 + dsig_cr in the raster dtype (windspeed.py:122-123)
-        P.dsig = A.dsig_cr ? (double)((const T *)A.dsig_cr)[il] : (double)(T)(x * (T)0 + (T)A.dsig_cr_scalar);
+        P.dsig = dsig_cr_at<T>(A.dsig_cr, il, x, A.dsig_cr_scalar);
     }
-    if (A.anc) {
-        typename Cx<T>::type z = ((const typename Cx<T>::type *)A.anc)[il];
-        P.a_re = (double)z.x;
-        P.a_im = (double)z.y;
-    }
+    if (A.anc) anc_at<T>(A.anc, il, false, P.a_re, P.a_im);  // (unfolded: the +-phi choice of store_pixel reads Im itself; b_eff below)
     P.flags = 0; P.i_inc = 0; P.i_inc_cr = 0;
     if (in) {
         const bool anc_nan = (P.a_re != P.a_re || P.a_im != P.a_im) && !(isinf(P.a_re) || isinf(P.a_im));  // isnan(hypot)
@@ -1342,7 +1353,7 @@ __device__ __forceinline__ void store_pixel(const DevTables &L, const KArgs &A, 
     }
     // the answer as grid codes (xsw.h): what xsw_expand_codes turns back into exactly the values formed above
     if (A.code_co)
-        A.code_co[i] = (P.flags & F_EARLY_NAN) ? K_CODE_NAN_RE : (P.flags & F_NEED_CO) ? ((unsigned)my_flat | ((unsigned)sgn << 30)) : K_CODE_NAN;
+        A.code_co[i] = (P.flags & F_EARLY_NAN) ? XSW_CODE_NAN_RE : (P.flags & F_NEED_CO) ? co_encode((unsigned)my_flat, (unsigned)sgn) : XSW_CODE_NAN;
     if (CR && (A.out_cr || A.code_cr)) {
         bool picked_co = false;
         if (A.dual_select) {  // xr.where((|co| < 5) | (|dual| < 5), co, dual)  (windspeed.py:426-428)
@@ -1361,8 +1372,7 @@ __device__ __forceinline__ void store_pixel(const DevTables &L, const KArgs &A, 
             ((cx_t *)A.out_cr)[i] = z;
         }
         if (A.code_cr)
-            A.code_cr[i] = (P.flags & F_EARLY_NAN) ? K_CODE_NAN_RE
-                                                     : (((P.flags & F_NEED_CR) ? (unsigned)my_icr : K_CODE_NO_INDEX) | (picked_co ? K_CODE_PICK_CO : 0u));
+            A.code_cr[i] = (P.flags & F_EARLY_NAN) ? XSW_CODE_NAN_RE : cr_encode((P.flags & F_NEED_CR) ? (unsigned)my_icr : XSW_CODE_NO_INDEX, picked_co);
     }
     if (A.out_idx) {
         A.out_idx[3 * i + 0] = o_iw;

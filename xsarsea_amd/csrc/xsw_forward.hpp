@@ -16,7 +16,7 @@
 // pixel reads nothing of the table.
 #pragma once
 #include "xsw_device.hpp"  // DevTables, ld
-#include "xsw_host.hpp"    // xsw_ctx, FwdArgs, seterr
+#include "xsw_host.hpp"    // FwdArgs
 
 namespace xsw {
 
@@ -67,12 +67,6 @@ __device__ __forceinline__ size_t next_entry()
     return one;
 }
 
-template <typename TO>
-__device__ __forceinline__ void fwd_store(void *out, long long i, double v)
-{
-    if (out) ((TO *)out)[i] = (TO)v;
-}
-
 // co-pol: incidence for the four (w, p) corners, then wind speed for the two directions, then direction
 template <typename T, typename TO>
 __global__ __launch_bounds__(256, 8) void k_lut_eval_co(DevTables L, FwdArgs A)
@@ -114,9 +108,9 @@ __global__ __launch_bounds__(256, 8) void k_lut_eval_co(DevTables L, FwdArgs A)
         }
         if (want_dw) dwspd = lerp_at(lerp_slope(s0, s1, p0, p1), p, p0, s0);  // the same lerp statement on the two speed slopes
     }
-    fwd_store<TO>(A.out_db, i, db);
-    fwd_store<TO>(A.out_dwspd, i, dwspd);
-    fwd_store<TO>(A.out_dphi, i, dphi);
+    store_opt<TO>(A.out_db, i, db);
+    store_opt<TO>(A.out_dwspd, i, dwspd);
+    store_opt<TO>(A.out_dphi, i, dphi);
 }
 
 // cross-pol: the 2-D analogue on cr[i][w]: incidence, then wind speed; no direction
@@ -140,20 +134,8 @@ __global__ __launch_bounds__(256, 8) void k_lut_eval_cr(DevTables L, FwdArgs A)
         dwspd = lerp_slope(v0, v1, w0, w1);
         db = lerp_at(dwspd, wspd, w0, v0);
     }
-    fwd_store<TO>(A.out_db, i, db);
-    fwd_store<TO>(A.out_dwspd, i, dwspd);
-}
-
-template <typename T, typename TO>
-static int launch_fwd(xsw_ctx *c, const FwdArgs &A, bool cr, hipStream_t stream, std::string &err)
-{
-    const long long nblocks = (A.n + 255) / 256;
-    if (nblocks > 0x7fffffffLL) return seterr(err, XSW_EINVAL, "raster too large for one launch");
-    if (cr) hipLaunchKernelGGL((k_lut_eval_cr<T, TO>), dim3((unsigned)nblocks), dim3(256), 0, stream, c->T, A);
-    else hipLaunchKernelGGL((k_lut_eval_co<T, TO>), dim3((unsigned)nblocks), dim3(256), 0, stream, c->T, A);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return seterr(err, XSW_EHIP, "launch failed: %s", hipGetErrorString(e));
-    return XSW_OK;
+    store_opt<TO>(A.out_db, i, db);
+    store_opt<TO>(A.out_dwspd, i, dwspd);
 }
 
 }  // namespace xsw

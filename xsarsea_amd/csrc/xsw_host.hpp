@@ -227,26 +227,19 @@ struct CrossArgs {
     int is_db, dual_select;
 };
 
-// The arguments of k_cost_co / k_cost_cr (xsw_cost.hpp; xsw.h: xsw_cost_from_codes, xsw_cost_cr_from_codes).
-struct CostArgs {
-    const void *inc, *s, *anc, *dsig_cr;  // s: sigma0_co (k_cost_co, with anc) or sigma0_cr (k_cost_cr, with the nullable dsig_cr)
-    const unsigned *code_co, *code_cr;    // k_cost_cr: code_co nullable (every pixel XSW_CODE_NAN)
-    void *out_J, *out_Jsig, *out_Jwind, *out_res;  // each nullable: reals of the output dtype
+// What the cost and the uncertainty passes read (xsw_cost.hpp, xsw_uncertainty.hpp): the codes and the rasters they were found from.
+struct CodesIn {
+    const void *inc, *s, *anc, *dsig_cr;  // s: sigma0_co (co-pol kernels, with anc) or sigma0_cr (cross-pol ones, with the nullable dsig_cr)
+    const unsigned *code_co, *code_cr;    // cross-pol kernels: code_co nullable (every pixel XSW_CODE_NAN)
     long long n;
     double dsig_co, dsig_cr_scalar;
     int is_db;
 };
-
-// The arguments of k_unc_co / k_unc_cr (xsw_uncertainty.hpp; xsw.h: xsw_uncertainty_from_codes, xsw_uncertainty_cr_from_codes).
-struct UncArgs {
-    const void *inc, *s, *anc, *dsig_cr;  // as in CostArgs
-    const unsigned *code_co, *code_cr;    // k_unc_cr: code_co nullable (every pixel XSW_CODE_NAN)
-    void *out_wspd_std, *out_dir_std, *out_corr;  // each nullable: reals of the output dtype (k_unc_cr: out_wspd_std alone)
-    unsigned char *out_flag;                      // nullable: XSW_UNC_* bits
-    long long n;
-    double dsig_co, dsig_cr_scalar;
-    int is_db;
-};
+// k_cost_co / k_cost_cr (xsw.h: xsw_cost_from_codes, xsw_cost_cr_from_codes): each output nullable, reals of the output dtype
+struct CostArgs : CodesIn { void *out_J, *out_Jsig, *out_Jwind, *out_res; };
+// k_unc_co / k_unc_cr (xsw.h: xsw_uncertainty_from_codes, xsw_uncertainty_cr_from_codes): likewise (k_unc_cr: out_wspd_std alone);
+// out_flag: nullable, uint8 XSW_UNC_* bits
+struct UncArgs : CodesIn { void *out_wspd_std, *out_dir_std, *out_corr, *out_flag; };
 
 // The arguments of k_lut_eval_co / k_lut_eval_cr (xsw_forward.hpp; xsw.h: xsw_lut_eval, xsw_lut_eval_cr).
 struct FwdArgs {
@@ -256,6 +249,19 @@ struct FwdArgs {
     int fold_phi;
 };
 }  // namespace xsw
+
+// The launch of every one-pixel-per-lane raster pass (k_cross_from_codes, k_cost_*, k_unc_*, k_lut_eval_*): 256 lanes per block
+// over n pixels.  An XSW_* code and, with a non-zero one, its message in `err`.
+template <typename Kernel, typename Args>
+static int launch_pixels(Kernel kernel, const xsw::DevTables &tables, const Args &A, long long n, hipStream_t stream, std::string &err)
+{
+    const long long nblocks = (n + 255) / 256;
+    if (nblocks > 0x7fffffffLL) return seterr(err, XSW_EINVAL, "raster too large for one launch");
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nblocks), dim3(256), 0, stream, tables, A);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return seterr(err, XSW_EHIP, "launch failed: %s", hipGetErrorString(e));
+    return XSW_OK;
+}
 
 // The launches of one (input dtype, output dtype) pair: the inversion kernels, k_cross_from_codes, k_cost_co / k_cost_cr,
 // k_unc_co / k_unc_cr and k_lut_eval_co / k_lut_eval_cr.

@@ -94,7 +94,11 @@ using TIn = std::conditional_t<(XSW_PAIR & 2) != 0, double, float>;
 using TOut = std::conditional_t<(XSW_PAIR & 1) != 0, double, float>;
 const PairLaunch &XSW_PAIR_NAME(XSW_PAIR)()
 {
-    static const PairLaunch pair = {launch_invert<TIn, TOut>, launch_cross<TIn, TOut>, launch_cost<TIn, TOut>, launch_unc<TIn, TOut>,
-                                    launch_fwd<TIn, TOut>};
+    static const PairLaunch pair = {
+        launch_invert<TIn, TOut>,
+        [](xsw_ctx *c, const CrossArgs &A, hipStream_t s, std::string &e) { return launch_pixels(k_cross_from_codes<TIn, TOut>, c->T, A, A.n, s, e); },
+        [](xsw_ctx *c, const CostArgs &A, bool cr, hipStream_t s, std::string &e) { return launch_pixels(cr ? k_cost_cr<TIn, TOut> : k_cost_co<TIn, TOut>, c->T, A, A.n, s, e); },
+        [](xsw_ctx *c, const UncArgs &A, bool cr, hipStream_t s, std::string &e) { return launch_pixels(cr ? k_unc_cr<TIn, TOut> : k_unc_co<TIn, TOut>, c->T, A, A.n, s, e); },
+        [](xsw_ctx *c, const FwdArgs &A, bool cr, hipStream_t s, std::string &e) { return launch_pixels(cr ? k_lut_eval_cr<TIn, TOut> : k_lut_eval_co<TIn, TOut>, c->T, A, A.n, s, e); }};
     return pair;
 }

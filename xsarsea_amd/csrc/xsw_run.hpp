@@ -58,6 +58,28 @@ static int run(xsw_ctx *c, int32_t mem, Buf (&b)[N], Launch &&launch, const char
 
 static bool bad_mem(int32_t mem) { return mem != XSW_MEM_HOST && mem != XSW_MEM_DEVICE; }
 
+// The refusals every one-pixel-per-lane raster entry opens with, in this order: shape, dtype pair, memory kind.
+static int check_raster_call(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem)
+{
+    if (lines < 0 || samples < 0) return fail(c, XSW_EINVAL, "negative raster shape");
+    if ((dtype != XSW_F32 && dtype != XSW_F64) || (out_dtype != XSW_F32 && out_dtype != XSW_F64))
+        return fail(c, XSW_EINVAL, "dtype/out_dtype must be XSW_F32 or XSW_F64");
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
+    return XSW_OK;
+}
+
+// The pixels of such a call and the bytes of an input element (es) and of a real output element (os); XSW_EINVAL for a raster
+// beyond one launch of 256-pixel blocks (checked without forming an overflowing lines * samples).
+static int pixel_count(xsw_ctx *c, const char *who, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, long long &n, size_t &es,
+                       size_t &os)
+{
+    if (lines && samples > (int64_t)(0x7fffffffLL * 256) / lines) return fail(c, XSW_EINVAL, "%s: raster too large for one launch", who);
+    n = (long long)lines * samples;
+    es = dtype == XSW_F32 ? 4 : 8;
+    os = out_dtype == XSW_F32 ? 4 : 8;
+    return XSW_OK;
+}
+
 // The kernels index a raster's axes (and count windows) with int.
 static bool fits_int(int64_t a, int64_t b = 0) { return a <= 0x7fffffffLL && b <= 0x7fffffffLL; }
 

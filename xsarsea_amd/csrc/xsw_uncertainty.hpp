@@ -21,8 +21,8 @@
 // flag: the real outputs are NaN; for the first three nothing of a LUT is read.  A pixel on a border diverges from its wave's
 // interior pixels at ONE branch (it skips the stencil); the outputs nobody asked for are skipped under wave-uniform conditions.
 #pragma once
-#include "xsw_cost.hpp"  // cost_co_at, cost_cr_at, cost_store; DevTables, to_db, nearest_index, ld, Cx
-#include "xsw_host.hpp"  // xsw_ctx, UncArgs, seterr
+#include "xsw_cost.hpp"  // cost_co_at, cost_cr_at; DevTables, to_db, nearest_index, ld, Cx
+#include "xsw_host.hpp"  // UncArgs
 
 namespace xsw {
 
@@ -38,17 +38,15 @@ __global__ __launch_bounds__(256, 8) void k_unc_co(DevTables L, UncArgs A)
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= A.n) return;
     const double nan = __builtin_nan("");
-    const unsigned code = A.code_co[i];
+    const CoCode code = co_decode(A.code_co[i], (unsigned)(L.n_w * L.n_phi));
     const double inc = ld<T>(A.inc, i);
     const double s_db = to_db(((const T *)A.s)[i], A.is_db);
-    const typename Cx<T>::type z = ((const typename Cx<T>::type *)A.anc)[i];
-    const double a = (double)z.x, b = L.phi_180 ? fabs((double)z.y) : (double)z.y;  // windspeed.py:218-219
-    const unsigned plane = (unsigned)(L.n_w * L.n_phi), flat = code & 0x3FFFFFFFu;
-    const bool grid_code = !(code & 0x80000000u) && flat < plane;
+    double a, b;
+    anc_at<T>(A.anc, i, L.phi_180, a, b);
     unsigned flag = XSW_UNC_NO_SOLUTION;
     double wspd_std = nan, dir_std = nan, corr = nan;
-    if (grid_code && inc == inc) {
-        const int iw = (int)(flat / (unsigned)L.n_phi), ip = (int)(flat - (unsigned)iw * (unsigned)L.n_phi);
+    if (code.grid() && inc == inc) {
+        const int iw = (int)(code.flat() / (unsigned)L.n_phi), ip = (int)(code.flat() - (unsigned)iw * (unsigned)L.n_phi);
         flag = ((iw == 0 || iw == L.n_w - 1) ? XSW_UNC_WSPD_BORDER : 0u) | ((ip == 0 || ip == L.n_phi - 1) ? XSW_UNC_PHI_BORDER : 0u);
         if (!flag) {  // 1 <= iw <= n_w - 2 and 1 <= ip <= n_phi - 2: the stencil lies inside the table
             const int i_inc = nearest_index(L.inc, L.n_inc, inc, L.inc_uniform != 0, L.inc0, L.inv_incstep);
@@ -73,10 +71,10 @@ __global__ __launch_bounds__(256, 8) void k_unc_co(DevTables L, UncArgs A)
             }
         }
     }
-    cost_store<TO>(A.out_wspd_std, i, wspd_std);
-    cost_store<TO>(A.out_dir_std, i, dir_std);
-    cost_store<TO>(A.out_corr, i, corr);
-    if (A.out_flag) A.out_flag[i] = (unsigned char)flag;
+    store_opt<TO>(A.out_wspd_std, i, wspd_std);
+    store_opt<TO>(A.out_dir_std, i, dir_std);
+    store_opt<TO>(A.out_corr, i, corr);
+    if (A.out_flag) ((unsigned char *)A.out_flag)[i] = (unsigned char)flag;
 }
 
 // cross-pol: the 1-D analogue on J_cr at icr - 1, icr, icr + 1; have_co / |wind_co| from the co-pol code as in k_cost_cr
@@ -86,26 +84,24 @@ __global__ __launch_bounds__(256, 8) void k_unc_cr(DevTables L, UncArgs A)
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= A.n) return;
     const double nan = __builtin_nan("");
-    const unsigned code_cr = A.code_cr[i];
-    const unsigned code = A.code_co ? A.code_co[i] : K_CODE_NAN;
+    const CrCode code_cr = cr_decode(A.code_cr[i]);
+    const unsigned icr = code_cr.index();
+    const CoCode code = co_decode(A.code_co ? A.code_co[i] : XSW_CODE_NAN, (unsigned)(L.n_w * L.n_phi));
     const double inc = ld<T>(A.inc, i);
     const T x = ((const T *)A.s)[i];
     const double s_db = to_db(x, A.is_db);
-    const double dsig = A.dsig_cr ? (double)((const T *)A.dsig_cr)[i] : (double)(T)(x * (T)0 + (T)A.dsig_cr_scalar);  // windspeed.py:122-123
-    const unsigned icr = code_cr & K_CODE_NO_INDEX;
-    const bool searched = code_cr != K_CODE_NAN_RE && icr != K_CODE_NO_INDEX && icr < (unsigned)L.n_wcr && inc == inc;
+    const double dsig = dsig_cr_at<T>(A.dsig_cr, i, x, A.dsig_cr_scalar);
+    const bool searched = cr_index_lenient(code_cr, (unsigned)L.n_wcr) && inc == inc;
     unsigned flag = XSW_UNC_NO_SOLUTION;
     double wspd_std = nan;
     if (searched) {
         flag = (icr == 0u || icr == (unsigned)L.n_wcr - 1u) ? XSW_UNC_WSPD_BORDER : 0u;
         if (!flag) {  // 1 <= icr <= n_wcr - 2
             const int i_inc_cr = nearest_index(L.inc_cr, L.n_inc_cr, inc, L.inc_cr_uniform != 0, L.inc_cr0, L.inv_inccrstep);
-            const unsigned plane = (unsigned)(L.n_w * L.n_phi), flat = code & 0x3FFFFFFFu;
-            const bool have_co = !(code & 0x80000000u) && flat < plane;  // (the incidence is not NaN here)
             double J[3], unused_sig = nan, unused_wind = nan, unused_res;
 #pragma unroll
             for (int k = 0; k < 3; ++k)
-                J[k] = cost_cr_at(L, i_inc_cr, icr + (unsigned)k - 1u, s_db, dsig, have_co, flat, true, true, unused_sig, unused_wind, unused_res);
+                J[k] = cost_cr_at(L, i_inc_cr, icr + (unsigned)k - 1u, s_db, dsig, code.grid(), code.flat(), true, true, unused_sig, unused_wind, unused_res);
             const double w0 = L.wcr[icr];
             const double Jww = unc_d2(J[0], J[1], J[2], w0 - L.wcr[icr - 1u], L.wcr[icr + 1u] - w0);
             if (Jww > 0.0) {
@@ -115,20 +111,8 @@ __global__ __launch_bounds__(256, 8) void k_unc_cr(DevTables L, UncArgs A)
             }
         }
     }
-    cost_store<TO>(A.out_wspd_std, i, wspd_std);
-    if (A.out_flag) A.out_flag[i] = (unsigned char)flag;
-}
-
-template <typename T, typename TO>
-static int launch_unc(xsw_ctx *c, const UncArgs &A, bool cr, hipStream_t stream, std::string &err)
-{
-    const long long nblocks = (A.n + 255) / 256;
-    if (nblocks > 0x7fffffffLL) return seterr(err, XSW_EINVAL, "raster too large for one launch");
-    if (cr) hipLaunchKernelGGL((k_unc_cr<T, TO>), dim3((unsigned)nblocks), dim3(256), 0, stream, c->T, A);
-    else hipLaunchKernelGGL((k_unc_co<T, TO>), dim3((unsigned)nblocks), dim3(256), 0, stream, c->T, A);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return seterr(err, XSW_EHIP, "launch failed: %s", hipGetErrorString(e));
-    return XSW_OK;
+    store_opt<TO>(A.out_wspd_std, i, wspd_std);
+    if (A.out_flag) ((unsigned char *)A.out_flag)[i] = (unsigned char)flag;
 }
 
 }  // namespace xsw
