@@ -358,6 +358,51 @@ int xsw_lut_eval(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, in
 int xsw_lut_eval_cr(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem, const void *inc,
                     const void *wspd, void *out_db, void *out_dwspd);
 
+/* ---- wind speed at a known direction: the inverse of xsw_lut_eval along the wind-speed axis.  Additive to XSW_VERSION 4.  The
+ * classical SAR scheme: the direction comes from elsewhere (wind streaks, a model), the speed is read off the table at that
+ * direction.  Per pixel s = sigma0 in dB, inc, phi; the direction is folded as xsw_lut_eval folds it (fold_phi).  Every input is
+ * up-cast to float64; only IEEE + - * / follow, without fused multiply-adds, every lerp in xsw_lut_eval's two statements:
+ *   gate     inc, phi or s NaN, inc or phi (after the fold) outside its axis, s not finite: outputs NaN, flag XSW_SOLVE_NAN;
+ *            such a pixel reads nothing of the table.
+ *   cells    (il, ih) on the incidence axis, (pl, ph) on the direction axis: xsw_lut_eval's.
+ *   c(k)     node value at speed node k: the lerp over direction of lerp_inc(T[il][k][pl], T[ih][k][pl]) and
+ *            lerp_inc(T[il][k][ph], T[ih][k][ph]) -- incidence FIRST, then direction; xsw_lut_eval orders its axes incidence,
+ *            speed, direction, so xsw_lut_eval(inc, out_wspd, phi) returns s to rounding (~1e-13 dB), not bit for bit.
+ *   bracket  M = min(mono_rows[il], mono_rows[ih]), the leading rows over which every column of both slices is non-decreasing.
+ *            M >= 2: lo = 0, hi = M - 1; while lo < hi: mid = (lo + hi) >> 1; c(mid) < s ? lo = mid + 1 : hi = mid.  j = lo.
+ *            c(j) >= s and j > 0: cell k = j - 1.  j == 0 and c(0) == s: k = 0.  Otherwise none in these rows.
+ *   tail     no bracket yet, or M < 2: k from max(M - 1, 0) to n_wspd - 2, the first with min(c(k), c(k+1)) <= s <= max(c(k), c(k+1));
+ *            found here: XSW_SOLVE_TAIL is set.  None: outputs NaN, flag XSW_SOLVE_BELOW where s < c(0), XSW_SOLVE_ABOVE where
+ *            s > c(0) (XSW_SOLVE_NAN where neither holds: a NaN in the table).
+ *   solution slope = (c(k+1) - c(k)) / (aw[k+1] - aw[k]); w = aw[k] + (s - c(k)) / slope, aw[k] in a flat cell (c(k+1) == c(k)),
+ *            clamped to [aw[k], aw[k+1]].
+ *   out_wspd w, m/s: the LOWEST speed that reproduces s; a table that turns over holds a second one higher up
+ *   out_sens 1 / slope, m/s per dB (+-inf in a flat cell): |out_sens| * dsig is the a-posteriori speed error
+ *   out_flag uint8, XSW_SOLVE_* bits; any of the low three set: the real outputs are NaN.  XSW_SOLVE_TAIL: the answer lies in
+ *            the rows past the monotone ones (CMOD5.N turns over below 41 degrees of incidence, from 23.6 m/s on).
+ * Real outputs are `lines x samples` rasters of out_dtype (XSW_F32: the float64 value rounded once), out_flag one of uint8; each
+ * may be NULL (never written), at least one must be given.
+ * Bytes per pixel, float32 rasters: 12 read; per c(k) four 8-byte LUT entries gathered as two adjacent pairs in two incidence
+ * planes, about ceil(log2(M)) + 1 of them in the leading rows; 4 or 8 written per real output and 1 for the flag.
+ * Before any launch, with a message in xsw_last_error: XSW_ENOLUT without a co-pol LUT; XSW_EINVAL for no output requested, a
+ * NULL input, a bad shape, dtype or mem, an axis of the LUT with fewer than two points, a raster too large for one launch.  An
+ * empty raster returns XSW_OK and launches nothing.  XSW_MEM_DEVICE: one kernel (k_wspd_solve_co), asynchronous on the context's
+ * stream; XSW_MEM_HOST: upload, kernel, download, returns with the outputs filled. */
+#define XSW_SOLVE_NAN   1u
+#define XSW_SOLVE_BELOW 2u
+#define XSW_SOLVE_ABOVE 4u
+#define XSW_SOLVE_TAIL  8u
+int xsw_wspd_solve(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem, int32_t fold_phi,
+                   const void *inc, const void *sigma0_db, const void *phi, void *out_wspd, void *out_sens, uint8_t *out_flag);
+
+/* Additive to XSW_VERSION 4.  The 1-D analogue on the cross-pol table cr[i][w]: c(k) = lerp_inc(cr[il][k], cr[ih][k]); no
+ * direction.  A table whose rows all rise on a uniform speed axis (the search's cr_monotone) is bisected over all its rows;
+ * any other is scanned from row 0, and a bracket the scan finds sets XSW_SOLVE_TAIL as above.  Bytes per pixel, float32
+ * rasters: 8 read, two LUT entries gathered per c(k), 4 or 8 + 1 written.  Refusals as xsw_wspd_solve, for the cross-pol LUT.
+ * One kernel (k_wspd_solve_cr). */
+int xsw_wspd_solve_cr(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem, const void *inc,
+                      const void *sigma0_db, void *out_wspd, void *out_sens, uint8_t *out_flag);
+
 /* Page-locked host memory for rasters a caller fills itself (XSW_MEM_HOST_PINNED); freed by xsw_host_free or with the context. */
 int xsw_host_alloc(xsw_ctx *ctx, size_t bytes, void **out);
 int xsw_host_free(xsw_ctx *ctx, void *p);

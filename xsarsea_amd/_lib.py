@@ -13,6 +13,7 @@ XSW_F32, XSW_F64 = 0, 1
 MEM_HOST, MEM_DEVICE, MEM_HOST_PINNED, MEM_DEVICE_SIGMA0_HOST = 0, 1, 2, 3
 CODE_NAN_RE, CODE_NAN, CODE_PICK_CO, CODE_NO_INDEX = 0xFFFFFFFF, 0xFFFFFFFE, 0x40000000, 0x3FFFFFFF
 UNC_NO_SOLUTION, UNC_WSPD_BORDER, UNC_PHI_BORDER, UNC_NOT_CONVEX = 1, 2, 4, 8  # XSW_UNC_*: the bits of an uncertainty flag raster
+SOLVE_NAN, SOLVE_BELOW, SOLVE_ABOVE, SOLVE_TAIL = 1, 2, 4, 8  # XSW_SOLVE_*: the bits of a `retrieve_wspd` flag raster
 ALGO_AUTO, ALGO_PRUNED, ALGO_EXHAUSTIVE, ALGO_EXACT, ALGO_EXHAUSTIVE_F64 = 0, 1, 2, 3, 4
 ALGOS = {"auto": ALGO_AUTO, "pruned": ALGO_PRUNED, "exhaustive": ALGO_EXHAUSTIVE, "exact": ALGO_EXACT,
          "exhaustive_f64": ALGO_EXHAUSTIVE_F64}
@@ -50,6 +51,7 @@ EXPORTS = (
     "xsw_cross_from_codes", "xsw_cost_from_codes", "xsw_cost_cr_from_codes",
     "xsw_uncertainty_from_codes", "xsw_uncertainty_cr_from_codes",
     "xsw_lut_eval", "xsw_lut_eval_cr",
+    "xsw_wspd_solve", "xsw_wspd_solve_cr",
     "xsw_dsig", "xsw_dsig_flat", "xsw_dsig_wspd",
 )
 
@@ -222,6 +224,8 @@ def load():
             [ctypes.c_double] + [ctypes.c_void_p] * 2
         lib.xsw_lut_eval.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 6
         lib.xsw_lut_eval_cr.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
+        lib.xsw_wspd_solve.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 6
+        lib.xsw_wspd_solve_cr.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 5
         lib.xsw_dsig.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_dsig_flat.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_dsig_wspd.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 3
@@ -513,6 +517,20 @@ class Context:
         """Thin call of xsw_lut_eval_cr: the same on the cross-pol table, which has no direction."""
         self._check(self._lib.xsw_lut_eval_cr(self._h, int(lines), int(samples), dtype, out_dtype, mem, inc, wspd, out_db, out_dwspd),
                     "xsw_lut_eval_cr")
+
+    @_locked
+    def wspd_solve_raw(self, lines, samples, dtype, out_dtype, mem, inc, sigma0_db, phi, out_wspd, out_sens=None, out_flag=None, fold_phi=True):
+        """Thin call of xsw_wspd_solve (pointers are ints or None): the lowest wind speed at which the context's co-pol table gives
+        sigma0_db (dB) at incidence inc and direction phi, its sensitivity in m/s per dB, each into a real raster of `out_dtype`,
+        and the uint8 SOLVE_* flags (None: not computed)."""
+        self._check(self._lib.xsw_wspd_solve(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(fold_phi)), inc, sigma0_db, phi,
+                                             out_wspd, out_sens, out_flag), "xsw_wspd_solve")
+
+    @_locked
+    def wspd_solve_cr_raw(self, lines, samples, dtype, out_dtype, mem, inc, sigma0_db, out_wspd, out_sens=None, out_flag=None):
+        """Thin call of xsw_wspd_solve_cr: the same on the cross-pol table, which has no direction."""
+        self._check(self._lib.xsw_wspd_solve_cr(self._h, int(lines), int(samples), dtype, out_dtype, mem, inc, sigma0_db, out_wspd, out_sens,
+                                                out_flag), "xsw_wspd_solve_cr")
 
     def expand_codes_on_stream(self, stream, n, out_dtype, code_co, code_cr, out_co, out_cr):
         """xsw_expand_codes_on_stream: device codes -> device winds on `stream` (a HIP stream handle as an int), the context's

@@ -766,6 +766,51 @@ extern "C" int xsw_lut_eval_cr(xsw_ctx *c, int64_t lines, int64_t samples, int32
     return lut_eval(c, "lut_eval_cr", true, lines, samples, dtype, out_dtype, mem, A);
 }
 
+// ---- wind speed at a known direction (xsw.h: xsw_wspd_solve, xsw_wspd_solve_cr; kernels: xsw_solve.hpp)
+// One body for the two entries: A holds the caller's pointers.
+static int wspd_solve(xsw_ctx *c, const char *who, bool cr, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                      SolveArgs A)
+{
+    if (int rc = check_raster_call(c, lines, samples, dtype, out_dtype, mem)) return rc;
+    if (!A.inc || !A.s || (!cr && !A.phi)) return fail(c, XSW_EINVAL, "%s: an input raster is NULL", who);
+    if (!A.out_wspd && !A.out_sens && !A.out_flag) return fail(c, XSW_EINVAL, "%s: no output requested", who);
+    if (cr ? !c->have_cr : !c->have_co) return fail(c, XSW_ENOLUT, "%s: no %s LUT installed", who, cr ? "cross-pol" : "co-pol");
+    if (cr ? (c->T.n_inc_cr < 2 || c->T.n_wcr < 2) : (c->T.n_inc < 2 || c->T.n_w < 2 || c->T.n_phi < 2))  // (no cell to solve in)
+        return fail(c, XSW_EINVAL, "%s: an axis of the %s LUT has fewer than two points", who, cr ? "cross-pol" : "co-pol");
+    size_t es, os;
+    if (int rc = pixel_count(c, who, lines, samples, dtype, out_dtype, A.n, es, os)) return rc;
+    if (A.n == 0) return XSW_OK;
+    const size_t px = (size_t)A.n;
+    Buf b[6] = {in_buf(A.inc, px * es), in_buf(A.s, px * es), in_buf(A.phi, px * es),
+                out_buf(A.out_wspd, px * os), out_buf(A.out_sens, px * os), out_buf(A.out_flag, px)};
+    return run(c, mem, b, [&](Buf (&x)[6]) {
+        A.inc = x[0].dev; A.s = x[1].dev; A.phi = x[2].dev;
+        A.out_wspd = x[3].dev; A.out_sens = x[4].dev; A.out_flag = x[5].dev;
+        return queue(c, dtype, out_dtype, &PairLaunch::solve, A, cr);
+    }, who);
+}
+
+extern "C" int xsw_wspd_solve(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem, int32_t fold_phi,
+                              const void *inc, const void *sigma0_db, const void *phi, void *out_wspd, void *out_sens, uint8_t *out_flag)
+{
+    if (!c) return XSW_EINVAL;
+    SolveArgs A{};
+    A.inc = inc; A.s = sigma0_db; A.phi = phi;
+    A.out_wspd = out_wspd; A.out_sens = out_sens; A.out_flag = out_flag;
+    A.fold_phi = fold_phi != 0;
+    return wspd_solve(c, "wspd_solve", false, lines, samples, dtype, out_dtype, mem, A);
+}
+
+extern "C" int xsw_wspd_solve_cr(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem, const void *inc,
+                                 const void *sigma0_db, void *out_wspd, void *out_sens, uint8_t *out_flag)
+{
+    if (!c) return XSW_EINVAL;
+    SolveArgs A{};
+    A.inc = inc; A.s = sigma0_db;
+    A.out_wspd = out_wspd; A.out_sens = out_sens; A.out_flag = out_flag;
+    return wspd_solve(c, "wspd_solve_cr", true, lines, samples, dtype, out_dtype, mem, A);
+}
+
 // ---- host-memory paths: chunks through a ring of workers (thread + stream + page-locked staging + device staging each)
 static int host_thread_count(const xsw_ctx *c)
 {

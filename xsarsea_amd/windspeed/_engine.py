@@ -538,9 +538,10 @@ def uncertainty_cr_from_codes(lut_co, lut_cr, plan, codes_co, codes_cr, inc, sig
     return outs
 
 
-def _lut_eval(lut, cross, plan, rasters, n_out, out_dtype, call):
-    """The host path of `lut_eval` / `lut_eval_cr`, in the manner of `_HostCodes` / `_DeviceCodes`: the rasters as the kernel reads
-    them (`plan.dtype`, contiguous), `n_out` outputs of `out_dtype`, the LUT installed in its slot, then
+def _lut_eval(lut, cross, plan, rasters, n_out, out_dtype, call, n_flag=0):
+    """The host path of `lut_eval` / `lut_eval_cr` / `wspd_solve` / `wspd_solve_cr`, in the manner of `_HostCodes` / `_DeviceCodes`:
+    the rasters as the kernel reads them (`plan.dtype`, contiguous), `n_out` outputs of `out_dtype` and after them `n_flag` uint8
+    ones, the LUT installed in its slot, then
     call(ctx, mem, input addresses, output addresses).  numpy rasters: host memory, synchronous, under the context's lock;
     device rasters: torch outputs, asynchronous on torch's current stream."""
     luts = (None, lut) if cross else (lut, None)
@@ -549,6 +550,7 @@ def _lut_eval(lut, cross, plan, rasters, n_out, out_dtype, call):
         dev = _device.device_of(*rasters)
         t = [_device.prep(_device.as_tensor(a, dev), plan.dtype, plan.shape) for a in rasters]
         outs = [torch.empty(plan.shape, dtype=_device.torch_dtype(out_dtype), device=dev) for _ in range(n_out)]
+        outs += [torch.empty(plan.shape, dtype=torch.uint8, device=dev) for _ in range(n_flag)]
         if plan.n:
             ctx = _device.context_of(dev)
             with _device.on_current_stream(ctx, dev):
@@ -557,7 +559,7 @@ def _lut_eval(lut, cross, plan, rasters, n_out, out_dtype, call):
                 _device.keep_alive(t, dev)
         return outs
     t = [np.ascontiguousarray(a, dtype=plan.dtype) for a in rasters]
-    outs = [np.empty(plan.shape, out_dtype) for _ in range(n_out)]
+    outs = [np.empty(plan.shape, out_dtype) for _ in range(n_out)] + [np.empty(plan.shape, np.uint8) for _ in range(n_flag)]
     if plan.n:
         ctx = _lib.default_context(options.device)
         with ctx.lock:
@@ -577,6 +579,20 @@ def lut_eval_cr(lut_cr, plan, inc, wspd, jacobian=False, out_dtype=np.float64):
     """[sigma0_db] or [sigma0_db, dwspd] of the cross-pol dB LUT `lut_cr`, which has no direction (xsw_lut_eval_cr)."""
     return _lut_eval(lut_cr, True, plan, (inc, wspd), 2 if jacobian else 1, out_dtype, lambda ctx, mem, ins, outs: ctx.lut_eval_cr_raw(
         plan.lines, plan.samples, plan.code, _real_code(out_dtype), mem, *ins, *outs))
+
+
+def wspd_solve(lut_co, plan, inc, sigma0_db, phi, fold_phi=True, details=False, out_dtype=np.float64):
+    """[wspd] or, details=True, [wspd, dwspd_dsigma0, flag] (`out_dtype`, the flag uint8 SOLVE_* bits; numpy, or torch for device
+    rasters): the lowest wind speed at which the co-pol dB LUT `lut_co` gives `sigma0_db` at `inc` and direction `phi`
+    (xsw_wspd_solve; `plan` a `_plan.ForwardPlan` of the three)."""
+    return _lut_eval(lut_co, False, plan, (inc, sigma0_db, phi), 2 if details else 1, out_dtype, lambda ctx, mem, ins, outs: ctx.wspd_solve_raw(
+        plan.lines, plan.samples, plan.code, _real_code(out_dtype), mem, *ins, *outs, fold_phi=fold_phi), n_flag=int(details))
+
+
+def wspd_solve_cr(lut_cr, plan, inc, sigma0_db, details=False, out_dtype=np.float64):
+    """The same on the cross-pol dB LUT `lut_cr`, which has no direction (xsw_wspd_solve_cr)."""
+    return _lut_eval(lut_cr, True, plan, (inc, sigma0_db), 2 if details else 1, out_dtype, lambda ctx, mem, ins, outs: ctx.wspd_solve_cr_raw(
+        plan.lines, plan.samples, plan.code, _real_code(out_dtype), mem, *ins, *outs), n_flag=int(details))
 
 
 def _uploaded_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc):
