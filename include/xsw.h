@@ -403,6 +403,50 @@ int xsw_wspd_solve(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, 
 int xsw_wspd_solve_cr(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem, const void *inc,
                       const void *sigma0_db, void *out_wspd, void *out_sens, uint8_t *out_flag);
 
+/* ---- wind direction at a known speed: the inverse of xsw_lut_eval along the direction axis.  Additive to XSW_VERSION 4.  What a
+ * dual-pol user needs once xsw_wspd_solve_cr has given a speed that needs no direction: at which directions does the co-pol table
+ * give the sigma0 observed?  Per pixel s = sigma0 in dB, inc, w = wind speed; optional `near`, a reference direction in degrees
+ * (antenna convention, any range).  Every input is up-cast to float64; only IEEE + - * / (and fmod) follow, without fused
+ * multiply-adds, every lerp in xsw_lut_eval's two statements:
+ *   gate     inc, w or s NaN, inc or w outside its axis, s not finite: real outputs NaN, count 0, flag XSW_DIR_NAN; such a pixel
+ *            reads nothing of the table.
+ *   cells    (il, ih) on the incidence axis, (wl, wh) on the speed axis: xsw_lut_eval's.
+ *   d(j)     node value at direction node j: lerp_w(lerp_inc(T[il][wl][j], T[ih][wl][j]), lerp_inc(T[il][wh][j], T[ih][wh][j])) --
+ *            incidence FIRST, then speed, xsw_lut_eval's order: d(pl), d(ph) are its two direction-cell values bit for bit.
+ *   scan     every cell k = 0 .. n_phi - 2 in ascending order.  Cell k holds a solution iff d(k) <= s < d(k+1), or
+ *            d(k) >= s > d(k+1), or k == n_phi - 2 and s == d(k+1): low node inclusive, high node exclusive but for the last; a flat
+ *            run at s counts once, at its end; a cell with a NaN node holds none.
+ *   solution slope = (d(k+1) - d(k)) / (p[k+1] - p[k]); phi = p[k] + (s - d(k)) / slope, p[k] in a flat cell, clamped to
+ *            [p[k], p[k+1]]; sens = 1 / slope, degrees per dB (+-inf in a flat cell).
+ *   out_phi1 / out_phi2, out_sens1 / out_sens2: the first and second solution in scan order and their sens; NaN where there is none.
+ *   out_count uint8: the number of cells holding a solution, saturating at 255.
+ *   out_flag  uint8, XSW_DIR_* bits: XSW_DIR_MORE where count > 2; where count == 0, XSW_DIR_BELOW if s < d(0), XSW_DIR_ABOVE if
+ *            s > d(0), else XSW_DIR_NAN (a NaN in the table).
+ *   out_phi_closest: for every gated pixel p[j] of the first node j that minimises |d(j) - s| among the nodes with a finite d: the
+ *            fallback for BELOW / ABOVE (crosswind, or up / downwind).
+ *   selection (near given): the candidates are, in scan order, every solution +phi and, with fold_phi, -phi right after it (the
+ *            mirror image by sigma0(phi) = sigma0(-phi)); r = fmod(c - near, 360); r < 0: r += 360; dist = r > 180 ? 360 - r : r;
+ *            out_phi_near is the candidate of the smallest dist (strict <: the earlier one on a tie), out_sens_near its sens,
+ *            negated for a mirrored candidate; over ALL solutions of the scan, not only the two stored.  NaN where near is NaN or
+ *            count == 0.
+ * Real outputs are `lines x samples` rasters of out_dtype (XSW_F32: the float64 value rounded once), out_count / out_flag of uint8;
+ * each may be NULL (never written), at least one must be given.
+ * Bytes per pixel, float32 rasters: 12 read (16 with near); the four rows T[il | ih][wl | wh][0 .. n_phi - 1] are walked from entry
+ * 0 as aligned 16-byte loads; 4 or 8 written per real output and 1 per uint8 one.  Three float64 divisions per node.
+ * Before any launch, with a message in xsw_last_error: XSW_ENOLUT without a co-pol LUT; XSW_EINVAL for no output requested, a
+ * NULL inc, sigma0_db or wspd, out_phi_near or out_sens_near without near, a bad shape, dtype or mem, an axis of the LUT with fewer
+ * than two points, a raster too large for one launch.  An empty raster returns XSW_OK and launches nothing.  XSW_MEM_DEVICE: one
+ * kernel (k_dir_solve_co), asynchronous on the context's stream; XSW_MEM_HOST: upload, kernel, download, returns with the outputs
+ * filled.  There is no cross-pol counterpart: that table has no direction axis. */
+#define XSW_DIR_NAN   1u
+#define XSW_DIR_BELOW 2u
+#define XSW_DIR_ABOVE 4u
+#define XSW_DIR_MORE  8u
+int xsw_dir_solve(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem, int32_t fold_phi,
+                  const void *inc, const void *sigma0_db, const void *wspd, const void *near, void *out_phi1, void *out_phi2,
+                  void *out_sens1, void *out_sens2, void *out_phi_near, void *out_sens_near, void *out_phi_closest, uint8_t *out_count,
+                  uint8_t *out_flag);
+
 /* Page-locked host memory for rasters a caller fills itself (XSW_MEM_HOST_PINNED); freed by xsw_host_free or with the context. */
 int xsw_host_alloc(xsw_ctx *ctx, size_t bytes, void **out);
 int xsw_host_free(xsw_ctx *ctx, void *p);

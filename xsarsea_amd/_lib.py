@@ -14,6 +14,7 @@ MEM_HOST, MEM_DEVICE, MEM_HOST_PINNED, MEM_DEVICE_SIGMA0_HOST = 0, 1, 2, 3
 CODE_NAN_RE, CODE_NAN, CODE_PICK_CO, CODE_NO_INDEX = 0xFFFFFFFF, 0xFFFFFFFE, 0x40000000, 0x3FFFFFFF
 UNC_NO_SOLUTION, UNC_WSPD_BORDER, UNC_PHI_BORDER, UNC_NOT_CONVEX = 1, 2, 4, 8  # XSW_UNC_*: the bits of an uncertainty flag raster
 SOLVE_NAN, SOLVE_BELOW, SOLVE_ABOVE, SOLVE_TAIL = 1, 2, 4, 8  # XSW_SOLVE_*: the bits of a `retrieve_wspd` flag raster
+DIR_NAN, DIR_BELOW, DIR_ABOVE, DIR_MORE = 1, 2, 4, 8  # XSW_DIR_*: the bits of a `retrieve_dir` flag raster
 ALGO_AUTO, ALGO_PRUNED, ALGO_EXHAUSTIVE, ALGO_EXACT, ALGO_EXHAUSTIVE_F64 = 0, 1, 2, 3, 4
 ALGOS = {"auto": ALGO_AUTO, "pruned": ALGO_PRUNED, "exhaustive": ALGO_EXHAUSTIVE, "exact": ALGO_EXACT,
          "exhaustive_f64": ALGO_EXHAUSTIVE_F64}
@@ -51,7 +52,7 @@ EXPORTS = (
     "xsw_cross_from_codes", "xsw_cost_from_codes", "xsw_cost_cr_from_codes",
     "xsw_uncertainty_from_codes", "xsw_uncertainty_cr_from_codes",
     "xsw_lut_eval", "xsw_lut_eval_cr",
-    "xsw_wspd_solve", "xsw_wspd_solve_cr",
+    "xsw_wspd_solve", "xsw_wspd_solve_cr", "xsw_dir_solve",
     "xsw_dsig", "xsw_dsig_flat", "xsw_dsig_wspd",
 )
 
@@ -226,6 +227,7 @@ def load():
         lib.xsw_lut_eval_cr.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_wspd_solve.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 6
         lib.xsw_wspd_solve_cr.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 5
+        lib.xsw_dir_solve.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 13
         lib.xsw_dsig.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_dsig_flat.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_dsig_wspd.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 3
@@ -531,6 +533,17 @@ class Context:
         """Thin call of xsw_wspd_solve_cr: the same on the cross-pol table, which has no direction."""
         self._check(self._lib.xsw_wspd_solve_cr(self._h, int(lines), int(samples), dtype, out_dtype, mem, inc, sigma0_db, out_wspd, out_sens,
                                                 out_flag), "xsw_wspd_solve_cr")
+
+    @_locked
+    def dir_solve_raw(self, lines, samples, dtype, out_dtype, mem, inc, sigma0_db, wspd, near=None, out_phi1=None, out_phi2=None, out_sens1=None,
+                      out_sens2=None, out_phi_near=None, out_sens_near=None, out_phi_closest=None, out_count=None, out_flag=None, fold_phi=True):
+        """Thin call of xsw_dir_solve (pointers are ints or None): the directions at which the context's co-pol table gives sigma0_db
+        (dB) at incidence inc and wind speed wspd -- the first two in scan order, their sensitivities in degrees per dB, the one
+        nearest to the reference direction `near` (None: no selection) and the closest node's direction, each into a real raster of
+        `out_dtype`; the uint8 number of solutions and the uint8 DIR_* flags (None: not computed)."""
+        self._check(self._lib.xsw_dir_solve(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(fold_phi)), inc, sigma0_db, wspd, near,
+                                            out_phi1, out_phi2, out_sens1, out_sens2, out_phi_near, out_sens_near, out_phi_closest, out_count,
+                                            out_flag), "xsw_dir_solve")
 
     def expand_codes_on_stream(self, stream, n, out_dtype, code_co, code_cr, out_co, out_cr):
         """xsw_expand_codes_on_stream: device codes -> device winds on `stream` (a HIP stream handle as an int), the context's

@@ -811,6 +811,41 @@ extern "C" int xsw_wspd_solve_cr(xsw_ctx *c, int64_t lines, int64_t samples, int
     return wspd_solve(c, "wspd_solve_cr", true, lines, samples, dtype, out_dtype, mem, A);
 }
 
+// ---- wind direction at a known speed (xsw.h: xsw_dir_solve; kernel: xsw_dirsolve.hpp)
+extern "C" int xsw_dir_solve(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem, int32_t fold_phi,
+                             const void *inc, const void *sigma0_db, const void *wspd, const void *near, void *out_phi1, void *out_phi2,
+                             void *out_sens1, void *out_sens2, void *out_phi_near, void *out_sens_near, void *out_phi_closest,
+                             uint8_t *out_count, uint8_t *out_flag)
+{
+    if (!c) return XSW_EINVAL;
+    const char *who = "dir_solve";
+    if (int rc = check_raster_call(c, lines, samples, dtype, out_dtype, mem)) return rc;
+    if (!inc || !sigma0_db || !wspd) return fail(c, XSW_EINVAL, "%s: an input raster is NULL", who);
+    if (!out_phi1 && !out_phi2 && !out_sens1 && !out_sens2 && !out_phi_near && !out_sens_near && !out_phi_closest && !out_count && !out_flag)
+        return fail(c, XSW_EINVAL, "%s: no output requested", who);
+    if (!near && (out_phi_near || out_sens_near)) return fail(c, XSW_EINVAL, "%s: out_phi_near / out_sens_near need the reference direction `near`", who);
+    if (!c->have_co) return fail(c, XSW_ENOLUT, "%s: no co-pol LUT installed", who);
+    if (c->T.n_inc < 2 || c->T.n_w < 2 || c->T.n_phi < 2)  // (no cell to solve in)
+        return fail(c, XSW_EINVAL, "%s: an axis of the co-pol LUT has fewer than two points", who);
+    DirArgs A{};
+    A.fold_phi = fold_phi != 0;
+    size_t es, os;
+    if (int rc = pixel_count(c, who, lines, samples, dtype, out_dtype, A.n, es, os)) return rc;
+    if (A.n == 0) return XSW_OK;
+    const size_t px = (size_t)A.n;
+    Buf b[13] = {in_buf(inc, px * es), in_buf(sigma0_db, px * es), in_buf(wspd, px * es), in_buf(near, px * es),
+                 out_buf(out_phi1, px * os), out_buf(out_phi2, px * os), out_buf(out_sens1, px * os), out_buf(out_sens2, px * os),
+                 out_buf(out_phi_near, px * os), out_buf(out_sens_near, px * os), out_buf(out_phi_closest, px * os),
+                 out_buf(out_count, px), out_buf(out_flag, px)};
+    return run(c, mem, b, [&](Buf (&x)[13]) {
+        A.inc = x[0].dev; A.s = x[1].dev; A.wspd = x[2].dev; A.near = x[3].dev;
+        A.out_phi1 = x[4].dev; A.out_phi2 = x[5].dev; A.out_sens1 = x[6].dev; A.out_sens2 = x[7].dev;
+        A.out_phi_near = x[8].dev; A.out_sens_near = x[9].dev; A.out_phi_closest = x[10].dev;
+        A.out_count = x[11].dev; A.out_flag = x[12].dev;
+        return queue(c, dtype, out_dtype, &PairLaunch::dir, A);
+    }, who);
+}
+
 // ---- host-memory paths: chunks through a ring of workers (thread + stream + page-locked staging + device staging each)
 static int host_thread_count(const xsw_ctx *c)
 {

@@ -256,9 +256,18 @@ struct SolveArgs {
     long long n;
     int fold_phi;
 };
+
+// The arguments of k_dir_solve_co (xsw_dirsolve.hpp; xsw.h: xsw_dir_solve).
+struct DirArgs {
+    const void *inc, *s, *wspd, *near;  // s: sigma0 in dB; near: nullable, the reference direction of the selection
+    void *out_phi1, *out_phi2, *out_sens1, *out_sens2, *out_phi_near, *out_sens_near, *out_phi_closest;  // each nullable: reals of the output dtype
+    void *out_count, *out_flag;         // each nullable: uint8, the number of solutions and the XSW_DIR_* bits
+    long long n;
+    int fold_phi;
+};
 }  // namespace xsw
 
-// The launch of every one-pixel-per-lane raster pass (k_cross_from_codes, k_cost_*, k_unc_*, k_lut_eval_*, k_wspd_solve_*): 256 lanes per block
+// The launch of every one-pixel-per-lane raster pass (k_cross_from_codes, k_cost_*, k_unc_*, k_lut_eval_*, k_wspd_solve_*, k_dir_solve_co): 256 lanes per block
 // over n pixels.  An XSW_* code and, with a non-zero one, its message in `err`.
 template <typename Kernel, typename Args>
 static int launch_pixels(Kernel kernel, const xsw::DevTables &tables, const Args &A, long long n, hipStream_t stream, std::string &err)
@@ -272,7 +281,7 @@ static int launch_pixels(Kernel kernel, const xsw::DevTables &tables, const Args
 }
 
 // The launches of one (input dtype, output dtype) pair: the inversion kernels, k_cross_from_codes, k_cost_co / k_cost_cr,
-// k_unc_co / k_unc_cr, k_lut_eval_co / k_lut_eval_cr and k_wspd_solve_co / k_wspd_solve_cr.
+// k_unc_co / k_unc_cr, k_lut_eval_co / k_lut_eval_cr, k_wspd_solve_co / k_wspd_solve_cr and k_dir_solve_co.
 // Each returns an XSW_* code and, with a non-zero one, its message in `err`.  One instance per translation unit
 // (xsw_invert_tu.hip, -DXSW_PAIR=0..3: f32->f32, f32->f64, f64->f32, f64->f64), so that the four sets of kernel
 // instantiations compile side by side; it sits behind a host function, which keeps it out of the device pass.
@@ -283,6 +292,7 @@ struct PairLaunch {
     int (*unc)(xsw_ctx *c, const xsw::UncArgs &A, bool cr, hipStream_t stream, std::string &err);
     int (*fwd)(xsw_ctx *c, const xsw::FwdArgs &A, bool cr, hipStream_t stream, std::string &err);
     int (*solve)(xsw_ctx *c, const xsw::SolveArgs &A, bool cr, hipStream_t stream, std::string &err);
+    int (*dir)(xsw_ctx *c, const xsw::DirArgs &A, hipStream_t stream, std::string &err);
 };
 const PairLaunch &xsw_pair_0(), &xsw_pair_1(), &xsw_pair_2(), &xsw_pair_3();
 

@@ -16,6 +16,7 @@
 #include "xsw_uncertainty.hpp"
 #include "xsw_forward.hpp"
 #include "xsw_solve.hpp"
+#include "xsw_dirsolve.hpp"
 
 using namespace xsw;
 
@@ -101,6 +102,7 @@ const PairLaunch &XSW_PAIR_NAME(XSW_PAIR)()
         [](xsw_ctx *c, const CostArgs &A, bool cr, hipStream_t s, std::string &e) { return launch_pixels(cr ? k_cost_cr<TIn, TOut> : k_cost_co<TIn, TOut>, c->T, A, A.n, s, e); },
         [](xsw_ctx *c, const UncArgs &A, bool cr, hipStream_t s, std::string &e) { return launch_pixels(cr ? k_unc_cr<TIn, TOut> : k_unc_co<TIn, TOut>, c->T, A, A.n, s, e); },
         [](xsw_ctx *c, const FwdArgs &A, bool cr, hipStream_t s, std::string &e) { return launch_pixels(cr ? k_lut_eval_cr<TIn, TOut> : k_lut_eval_co<TIn, TOut>, c->T, A, A.n, s, e); },
-        [](xsw_ctx *c, const SolveArgs &A, bool cr, hipStream_t s, std::string &e) { return launch_pixels(cr ? k_wspd_solve_cr<TIn, TOut> : k_wspd_solve_co<TIn, TOut>, c->T, A, A.n, s, e); }};
+        [](xsw_ctx *c, const SolveArgs &A, bool cr, hipStream_t s, std::string &e) { return launch_pixels(cr ? k_wspd_solve_cr<TIn, TOut> : k_wspd_solve_co<TIn, TOut>, c->T, A, A.n, s, e); },
+        [](xsw_ctx *c, const DirArgs &A, hipStream_t s, std::string &e) { return launch_pixels(k_dir_solve_co<TIn, TOut>, c->T, A, A.n, s, e); }};
     return pair;
 }

@@ -1,7 +1,8 @@
 """windspeed: wind retrieval from sigma0 and models (public names of `xsarsea.windspeed`)."""
 __all__ = ["invert_from_model", "available_models", "get_model", "register_cmod7", "register_pickle_luts", "register_nc_luts",
            "register_luts", "nesz_flattening", "GmfModel", "Model", "gmfs", "gmfs_impl", "get_dsig", "get_dsig_wspd", "dsig_from_nesz", "invert_copol_codes", "CopolCodes", "InversionCost", "InversionUncertainty",
-           "simulate_sigma0", "SimulatedSigma0", "retrieve_wspd", "RetrievedWspd"]
+           "simulate_sigma0", "SimulatedSigma0", "retrieve_wspd", "RetrievedWspd",
+           "retrieve_dir", "RetrievedDir", "retrieve_wind"]
 
 from . import gmfs, gmfs_impl
 from .cmod7 import register_cmod7
@@ -11,5 +12,6 @@ from .gmfs import GmfModel
 from .models import Model, available_models, get_model, register_luts, register_nc_luts
 from .pickle_luts import register_pickle_luts
 from .retrieve import RetrievedWspd, retrieve_wspd
+from .retrieve_dir import RetrievedDir, retrieve_dir, retrieve_wind
 from .utils import dsig_from_nesz, get_dsig, get_dsig_wspd, nesz_flattening
 from .windspeed import invert_from_model

@@ -539,8 +539,8 @@ def uncertainty_cr_from_codes(lut_co, lut_cr, plan, codes_co, codes_cr, inc, sig
 
 
 def _lut_eval(lut, cross, plan, rasters, n_out, out_dtype, call, n_flag=0):
-    """The host path of `lut_eval` / `lut_eval_cr` / `wspd_solve` / `wspd_solve_cr`, in the manner of `_HostCodes` / `_DeviceCodes`:
-    the rasters as the kernel reads them (`plan.dtype`, contiguous), `n_out` outputs of `out_dtype` and after them `n_flag` uint8
+    """The host path of `lut_eval` / `lut_eval_cr` / `wspd_solve` / `wspd_solve_cr` / `dir_solve`, in the manner of `_HostCodes` /
+    `_DeviceCodes`: the rasters as the kernel reads them (`plan.dtype`, contiguous), `n_out` outputs of `out_dtype` and after them `n_flag` uint8
     ones, the LUT installed in its slot, then
     call(ctx, mem, input addresses, output addresses).  numpy rasters: host memory, synchronous, under the context's lock;
     device rasters: torch outputs, asynchronous on torch's current stream."""
@@ -593,6 +593,27 @@ def wspd_solve_cr(lut_cr, plan, inc, sigma0_db, details=False, out_dtype=np.floa
     """The same on the cross-pol dB LUT `lut_cr`, which has no direction (xsw_wspd_solve_cr)."""
     return _lut_eval(lut_cr, True, plan, (inc, sigma0_db), 2 if details else 1, out_dtype, lambda ctx, mem, ins, outs: ctx.wspd_solve_cr_raw(
         plan.lines, plan.samples, plan.code, _real_code(out_dtype), mem, *ins, *outs), n_flag=int(details))
+
+
+DIR_REALS = ("phi1", "phi2", "sens1", "sens2", "phi_near", "sens_near", "phi_closest")  # xsw_dir_solve's outputs, in its order
+DIR_BYTES = ("count", "flag")
+
+
+def dir_solve(lut_co, plan, inc, sigma0_db, wspd, near=None, fold_phi=True, outputs=("phi1", "phi2"), out_dtype=np.float64):
+    """{name: raster} for the `outputs` asked for among DIR_REALS (`out_dtype`) and DIR_BYTES (uint8; numpy, or torch for device
+    rasters): the directions at which the co-pol dB LUT `lut_co` gives `sigma0_db` at `inc` and wind speed `wspd`, and with the
+    reference direction `near` the one nearest to it (xsw_dir_solve; `plan` a `_plan.ForwardPlan` of the rasters given)."""
+    reals, small = [k for k in DIR_REALS if k in outputs], [k for k in DIR_BYTES if k in outputs]
+    if set(outputs) - set(reals) - set(small) or not (reals or small):
+        raise ValueError(f"dir_solve: outputs {tuple(outputs)} are not among {DIR_REALS + DIR_BYTES}")
+
+    def call(ctx, mem, ins, outs):
+        at = dict(zip(reals + small, outs))
+        ctx.dir_solve_raw(plan.lines, plan.samples, plan.code, _real_code(out_dtype), mem, ins[0], ins[1], ins[2], ins[3] if near is not None else None,
+                          *(at.get(k) for k in DIR_REALS + DIR_BYTES), fold_phi=fold_phi)
+
+    rasters = (inc, sigma0_db, wspd) + ((near,) if near is not None else ())
+    return dict(zip(reals + small, _lut_eval(lut_co, False, plan, rasters, len(reals), out_dtype, call, n_flag=len(small))))
 
 
 def _uploaded_rasters(inc, sigma0_co, sigma0_cr, dsig_cr, anc):

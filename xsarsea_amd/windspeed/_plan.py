@@ -61,10 +61,11 @@ class CallPlan:
 
 class ForwardPlan:
     """One `xsw_lut_eval` / `xsw_lut_eval_cr` call from metadata only: inc, wspd, phi (None for a cross-pol table) as (shape, dtype),
-    all of one shape.  Every raster float32: the kernel reads them as such and widens in registers; else everything is float64."""
+    all of one shape; `more`: further rasters of a call that reads four (`xsw_dir_solve`), None for an absent one.  Every raster
+    float32: the kernel reads them as such and widens in registers; else everything is float64."""
 
-    def __init__(self, inc, wspd, phi=None):
-        rasters = [m for m in (inc, wspd, phi) if m is not None]
+    def __init__(self, inc, wspd, phi=None, *more):
+        rasters = [m for m in (inc, wspd, phi) + more if m is not None]
         shapes = {tuple(m[0]) for m in rasters}
         if len(shapes) != 1:
             raise ValueError(f"inc, wspd and phi must have one shape, not {sorted(shapes)}")
