@@ -326,6 +326,35 @@ int xsw_uncertainty_cr_from_codes(xsw_ctx *ctx, int64_t lines, int64_t samples, 
                                   const void *sigma0_cr, const void *dsig_cr, double dsig_cr_scalar, void *out_wspd_std,
                                   uint8_t *out_flag);
 
+/* ---- the joint dual-pol inversion.  Additive to XSW_VERSION 4.  The grid wind of the co-pol LUT that best explains BOTH
+ * observations and the a-priori wind: per pixel the arg-min over (iw, ip) of ONE cost
+ *     J(iw, ip) = (Jwind_co(iw, ip) + Jsig_co(iw, ip)) + Jsig_cr(iw)
+ * where the first two terms are xsw_cost_from_codes' and Jsig_cr(iw) = ((crw - sigma0_cr_db) / dsig_cr)^2 with crw the cross-pol
+ * table at the co-pol speed: x = min(max(w[iw], wcr[0]), wcr[n - 1]) (the table is held constant beyond its speed axis),
+ * k = clip(searchsorted(wcr, x), 1, n - 1), slope = (cr[i][k] - cr[i][k-1]) / (wcr[k] - wcr[k-1]), crw = slope * (x - wcr[k-1]) +
+ * cr[i][k-1], i the nearest cross-pol incidence row.  Float64, IEEE + - * / only; ties go to the smallest iw * n_phi + ip: the
+ * result is numpy.argmin of the dense array.  There is no Jwind_cr term: the a-priori speed enters through Jwind_co.
+ *   code_co      the co-pol codes of these pixels from the context's CURRENT co-pol LUT (xsw_invert's out_code_co): a real
+ *                candidate, hence an upper bound J_ub of the minimum, which confines the search to a window that provably holds
+ *                the arg-min.  Any grid code gives the same answer; a good one makes the pass cheap.
+ *   inc, sigma0_co, anc, dsig_co   as in xsw_cost_from_codes; sigma0_cr, dsig_cr, dsig_cr_scalar as in xsw_cross_from_codes.
+ *   out_code     the joint grid point in the co-pol code format (bit 30: the -phi choice of a 0..180 LUT, by the inversion's own
+ *                rule applied to the joint point): xsw_expand_codes reads it.
+ *   out_J, out_Jwind, out_Jsig_co, out_Jsig_cr   J and its three terms at the joint point, reals of out_dtype (XSW_F32: one
+ *                final rounding).  Every output may be NULL (not computed, never written); at least one must be given.
+ * Gates: XSW_CODE_NAN / XSW_CODE_NAN_RE keep their code; a code of no LUT and a NaN incidence give XSW_CODE_NAN_RE; in these the
+ * costs are NaN and no table is read.  A grid code next to a NaN sigma0_cr or dsig_cr (no cross-pol information): the input code,
+ * the co-pol terms and J = J_co at its point, Jsig_cr NaN.  Otherwise a J_ub that is not finite (NaN sigma0_co or a-priori wind,
+ * dsig_cr == 0) gives XSW_CODE_NAN and NaN costs.
+ * With xsw_stats_enable the call counts its work: xsw_stats_read's pixels_co = pixels searched, cand_co = candidates scored.
+ * XSW_ENOLUT without both LUTs; XSW_EINVAL, before any launch: a NULL input, no output, dsig_co NaN or 0, a bad dtype or mem, a
+ * raster too large for one launch, a LUT with a NaN or infinite entry.  An empty raster returns XSW_OK.  XSW_MEM_DEVICE: one
+ * kernel (k_joint_from_codes), asynchronous on the context's stream; XSW_MEM_HOST: upload, kernel, download. */
+int xsw_joint_from_codes(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                         int32_t sigma0_is_db, const void *inc, const uint32_t *code_co, const void *sigma0_co, const void *anc,
+                         double dsig_co, const void *sigma0_cr, const void *dsig_cr, double dsig_cr_scalar, uint32_t *out_code,
+                         void *out_J, void *out_Jwind, void *out_Jsig_co, void *out_Jsig_cr);
+
 /* ---- the forward operator on rasters.  Additive to XSW_VERSION 4.  sigma0 in dB that the context's CURRENT co-pol table
  * T[i][w][p] (axes ai, aw, ap) predicts for the wind (wspd, phi) at incidence inc, per pixel, and the derivatives of that
  * interpolant.  Every input is up-cast to float64; only IEEE + - * / follow, in this order, without fused multiply-adds:

@@ -50,7 +50,7 @@ EXPORTS = (
     "xsw_grad_hist_masked", "xsw_grad_keep_f64", "xsw_grad_keep_u8",
     "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary",
     "xsw_cross_from_codes", "xsw_cost_from_codes", "xsw_cost_cr_from_codes",
-    "xsw_uncertainty_from_codes", "xsw_uncertainty_cr_from_codes",
+    "xsw_uncertainty_from_codes", "xsw_uncertainty_cr_from_codes", "xsw_joint_from_codes",
     "xsw_lut_eval", "xsw_lut_eval_cr",
     "xsw_wspd_solve", "xsw_wspd_solve_cr", "xsw_dir_solve",
     "xsw_dsig", "xsw_dsig_flat", "xsw_dsig_wspd",
@@ -223,6 +223,8 @@ def load():
             [ctypes.c_double] + [ctypes.c_void_p] * 4
         lib.xsw_uncertainty_cr_from_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 5 + \
             [ctypes.c_double] + [ctypes.c_void_p] * 2
+        lib.xsw_joint_from_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 4 + \
+            [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double] + [ctypes.c_void_p] * 5
         lib.xsw_lut_eval.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 6
         lib.xsw_lut_eval_cr.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_wspd_solve.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 6
@@ -486,6 +488,16 @@ class Context:
         self._check(self._lib.xsw_cost_cr_from_codes(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(sigma0_is_db)), inc, code_co,
                                                      code_cr, sigma0_cr, dsig_cr, float(dsig_cr_scalar), out_J, out_Jsig, out_Jwind, out_residual),
                     "xsw_cost_cr_from_codes")
+
+    @_locked
+    def joint_from_codes_raw(self, lines, samples, dtype, out_dtype, mem, inc, code_co, sigma0_co, anc, sigma0_cr, dsig_cr, out_code, out_J=None,
+                             out_Jwind=None, out_Jsig_co=None, out_Jsig_cr=None, dsig_co=0.1, dsig_cr_scalar=0.1, sigma0_is_db=False):
+        """Thin call of xsw_joint_from_codes (pointers are ints or None): the grid point of the co-pol LUT that minimises
+        J = Jwind_co + Jsig_co + Jsig_cr, as uint32 co-pol codes, and J with its three terms there, each into a real raster of
+        `out_dtype` (None: not computed); dsig_cr None: the scalar broadcast."""
+        self._check(self._lib.xsw_joint_from_codes(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(sigma0_is_db)), inc, code_co,
+                                                   sigma0_co, anc, float(dsig_co), sigma0_cr, dsig_cr, float(dsig_cr_scalar), out_code, out_J,
+                                                   out_Jwind, out_Jsig_co, out_Jsig_cr), "xsw_joint_from_codes")
 
     @_locked
     def uncertainty_from_codes_raw(self, lines, samples, dtype, out_dtype, mem, inc, code_co, sigma0_co, anc, out_wspd_std, out_dir_std=None,

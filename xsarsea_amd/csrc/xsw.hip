@@ -391,6 +391,7 @@ static int install_co(xsw_ctx *c, const xsw_lut *l, const double *d_dense)
     T.co = d_co;
     T.co32 = d_co32;
     const bool lut_finite = h_flags[0] == 0;
+    c->co_finite = lut_finite;
     memcpy(&T.co_absmax, &h_flags[1], sizeof(double));
 
     // host-built tables: the axes as they are; the output-side tables are the caller's values, or the host libm's (see xsw.h)
@@ -719,6 +720,41 @@ extern "C" int xsw_uncertainty_cr_from_codes(xsw_ctx *c, int64_t lines, int64_t 
     A.out_wspd_std = out_wspd_std; A.out_flag = out_flag;
     A.dsig_cr_scalar = dsig_cr_scalar; A.is_db = sigma0_is_db;
     return pass_from_codes(c, "uncertainty_cr_from_codes", true, lines, samples, dtype, out_dtype, mem, A, unc_outs, 1, &PairLaunch::unc);
+}
+
+// ---- the joint dual-pol inversion from stored co-pol codes (xsw.h: xsw_joint_from_codes; kernel: xsw_joint.hpp)
+extern "C" int xsw_joint_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                                    int32_t sigma0_is_db, const void *inc, const uint32_t *code_co, const void *sigma0_co, const void *anc,
+                                    double dsig_co, const void *sigma0_cr, const void *dsig_cr, double dsig_cr_scalar, uint32_t *out_code,
+                                    void *out_J, void *out_Jwind, void *out_Jsig_co, void *out_Jsig_cr)
+{
+    if (!c) return XSW_EINVAL;
+    const char *who = "joint_from_codes";
+    if (int rc = check_raster_call(c, lines, samples, dtype, out_dtype, mem)) return rc;
+    if (!inc || !code_co || !sigma0_co || !anc || !sigma0_cr) return fail(c, XSW_EINVAL, "%s: an input raster is NULL", who);
+    if (!out_code && !out_J && !out_Jwind && !out_Jsig_co && !out_Jsig_cr) return fail(c, XSW_EINVAL, "%s: no output requested", who);
+    if (!c->have_co || !c->have_cr) return fail(c, XSW_ENOLUT, "%s: needs a co-pol and a cross-pol LUT on this context", who);
+    if (dsig_co != dsig_co || dsig_co == 0.0) return fail(c, XSW_EINVAL, "%s: dsig_co is NaN or 0", who);
+    if (!c->co_finite || !c->T.cr_finite) return fail(c, XSW_EINVAL, "%s: a LUT with a NaN or infinite entry", who);
+    JointArgs A{};
+    size_t es, os;
+    if (int rc = pixel_count(c, who, lines, samples, dtype, out_dtype, A.n, es, os)) return rc;
+    if (A.n == 0) return XSW_OK;
+    A.dsig_co = dsig_co; A.dsig_cr_scalar = dsig_cr_scalar; A.is_db = sigma0_is_db;
+    const size_t px = (size_t)A.n;
+    Buf b[11] = {in_buf(inc, px * es), in_buf(sigma0_co, px * es), in_buf(anc, px * es * 2), in_buf(sigma0_cr, px * es), in_buf(dsig_cr, px * es),
+                 in_buf(code_co, px * 4), out_buf(out_code, px * 4), out_buf(out_J, px * os), out_buf(out_Jwind, px * os),
+                 out_buf(out_Jsig_co, px * os), out_buf(out_Jsig_cr, px * os)};
+    return run(c, mem, b, [&](Buf (&x)[11]) {
+        A.inc = x[0].dev; A.s_co = x[1].dev; A.anc = x[2].dev; A.s_cr = x[3].dev; A.dsig_cr = x[4].dev;
+        A.code_co = (const unsigned *)x[5].dev; A.out_code = (unsigned *)x[6].dev;
+        A.out_J = x[7].dev; A.out_Jwind = x[8].dev; A.out_Jsig_co = x[9].dev; A.out_Jsig_cr = x[10].dev;
+        if (c->stats_on) {  // candidates scored per pixel (xsw_stats_read: pixels_co, cand_co), reset on the launch stream
+            if (hipMemsetAsync(c->d_stats, 0, 8 * sizeof(unsigned long long), c->stream) != hipSuccess) return fail(c, XSW_EHIP, "%s: statistics reset failed", who);
+            A.stats = c->d_stats;
+        }
+        return queue(c, dtype, out_dtype, &PairLaunch::joint, A);
+    }, who);
 }
 
 // ---- the forward operator on rasters (xsw.h: xsw_lut_eval, xsw_lut_eval_cr; kernels: xsw_forward.hpp)

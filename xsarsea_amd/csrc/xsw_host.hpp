@@ -26,6 +26,7 @@ struct xsw_ctx {
     xsw::DevTables T{};
     std::vector<void *> co_allocs, cr_allocs;
     bool have_co = false, have_cr = false;
+    bool co_finite = false;  // the installed co-pol table holds no NaN / inf (xsw_joint_from_codes refuses others; the cross-pol one: T.cr_finite)
     unsigned long long *d_stats = nullptr;
     bool stats_on = false;
     bool stats_chain = false;               // xsw_stats_enable(ctx, 2): the production chain keeps running, its kernels count what they score
@@ -241,6 +242,18 @@ struct CostArgs : CodesIn { void *out_J, *out_Jsig, *out_Jwind, *out_res; };
 // out_flag: nullable, uint8 XSW_UNC_* bits
 struct UncArgs : CodesIn { void *out_wspd_std, *out_dir_std, *out_corr, *out_flag; };
 
+// The arguments of k_joint_from_codes (xsw_joint.hpp; xsw.h: xsw_joint_from_codes).
+struct JointArgs {
+    const void *inc, *s_co, *anc, *s_cr, *dsig_cr;  // dsig_cr nullable: dsig_cr_scalar broadcast as in load_pixel
+    const unsigned *code_co;
+    unsigned *out_code;                                  // nullable, as every output
+    void *out_J, *out_Jwind, *out_Jsig_co, *out_Jsig_cr;  // reals of the output dtype
+    unsigned long long *stats;                           // nullable: [0] pixels searched, [1] candidates scored (xsw_stats_enable)
+    long long n;
+    double dsig_co, dsig_cr_scalar;
+    int is_db;
+};
+
 // The arguments of k_lut_eval_co / k_lut_eval_cr (xsw_forward.hpp; xsw.h: xsw_lut_eval, xsw_lut_eval_cr).
 struct FwdArgs {
     const void *inc, *wspd, *phi;          // phi: k_lut_eval_co only
@@ -267,7 +280,7 @@ struct DirArgs {
 };
 }  // namespace xsw
 
-// The launch of every one-pixel-per-lane raster pass (k_cross_from_codes, k_cost_*, k_unc_*, k_lut_eval_*, k_wspd_solve_*, k_dir_solve_co): 256 lanes per block
+// The launch of every one-pixel-per-lane raster pass (k_cross_from_codes, k_cost_*, k_unc_*, k_lut_eval_*, k_wspd_solve_*, k_dir_solve_co, k_joint_from_codes): 256 lanes per block
 // over n pixels.  An XSW_* code and, with a non-zero one, its message in `err`.
 template <typename Kernel, typename Args>
 static int launch_pixels(Kernel kernel, const xsw::DevTables &tables, const Args &A, long long n, hipStream_t stream, std::string &err)
@@ -281,7 +294,7 @@ static int launch_pixels(Kernel kernel, const xsw::DevTables &tables, const Args
 }
 
 // The launches of one (input dtype, output dtype) pair: the inversion kernels, k_cross_from_codes, k_cost_co / k_cost_cr,
-// k_unc_co / k_unc_cr, k_lut_eval_co / k_lut_eval_cr, k_wspd_solve_co / k_wspd_solve_cr and k_dir_solve_co.
+// k_unc_co / k_unc_cr, k_lut_eval_co / k_lut_eval_cr, k_wspd_solve_co / k_wspd_solve_cr, k_dir_solve_co and k_joint_from_codes.
 // Each returns an XSW_* code and, with a non-zero one, its message in `err`.  One instance per translation unit
 // (xsw_invert_tu.hip, -DXSW_PAIR=0..3: f32->f32, f32->f64, f64->f32, f64->f64), so that the four sets of kernel
 // instantiations compile side by side; it sits behind a host function, which keeps it out of the device pass.
@@ -293,6 +306,7 @@ struct PairLaunch {
     int (*fwd)(xsw_ctx *c, const xsw::FwdArgs &A, bool cr, hipStream_t stream, std::string &err);
     int (*solve)(xsw_ctx *c, const xsw::SolveArgs &A, bool cr, hipStream_t stream, std::string &err);
     int (*dir)(xsw_ctx *c, const xsw::DirArgs &A, hipStream_t stream, std::string &err);
+    int (*joint)(xsw_ctx *c, const xsw::JointArgs &A, hipStream_t stream, std::string &err);
 };
 const PairLaunch &xsw_pair_0(), &xsw_pair_1(), &xsw_pair_2(), &xsw_pair_3();
 

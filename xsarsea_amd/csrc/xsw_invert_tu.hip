@@ -17,6 +17,7 @@
 #include "xsw_forward.hpp"
 #include "xsw_solve.hpp"
 #include "xsw_dirsolve.hpp"
+#include "xsw_joint.hpp"
 
 using namespace xsw;
 
@@ -103,6 +104,7 @@ const PairLaunch &XSW_PAIR_NAME(XSW_PAIR)()
         [](xsw_ctx *c, const UncArgs &A, bool cr, hipStream_t s, std::string &e) { return launch_pixels(cr ? k_unc_cr<TIn, TOut> : k_unc_co<TIn, TOut>, c->T, A, A.n, s, e); },
         [](xsw_ctx *c, const FwdArgs &A, bool cr, hipStream_t s, std::string &e) { return launch_pixels(cr ? k_lut_eval_cr<TIn, TOut> : k_lut_eval_co<TIn, TOut>, c->T, A, A.n, s, e); },
         [](xsw_ctx *c, const SolveArgs &A, bool cr, hipStream_t s, std::string &e) { return launch_pixels(cr ? k_wspd_solve_cr<TIn, TOut> : k_wspd_solve_co<TIn, TOut>, c->T, A, A.n, s, e); },
-        [](xsw_ctx *c, const DirArgs &A, hipStream_t s, std::string &e) { return launch_pixels(k_dir_solve_co<TIn, TOut>, c->T, A, A.n, s, e); }};
+        [](xsw_ctx *c, const DirArgs &A, hipStream_t s, std::string &e) { return launch_pixels(k_dir_solve_co<TIn, TOut>, c->T, A, A.n, s, e); },
+        [](xsw_ctx *c, const JointArgs &A, hipStream_t s, std::string &e) { return launch_pixels(k_joint_from_codes<TIn, TOut>, c->T, A, A.n, s, e); }};
     return pair;
 }

@@ -415,13 +415,15 @@ class _HostCodes:
     the codes uint32.  `run` calls xsw_*_from_codes on host memory: synchronous, under the context's lock."""
     mem = _lib.MEM_HOST
 
-    def __init__(self, plan, inc, sigma0, dsig_cr, anc, *codes):
+    def __init__(self, plan, inc, sigma0, dsig_cr, anc, *codes, sigma0_too=None):
         cast = lambda a, t=plan.dtype: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a), plan.shape), dtype=t)
         sigma0 = np.asarray(sigma0)
         dsig = dsig_raster(sigma0, plan.dsig_fill) if plan.dsig == _plan.DSIG_FILL else (dsig_cr if plan.dsig == _plan.DSIG_RASTER else None)
         self.plan, self.ctx = plan, _lib.default_context(options.device)
         self.rasters = [cast(inc), cast(_to_db(sigma0) if plan.is_db else sigma0), cast(dsig), cast(anc, plan.cdtype)]
         self.rasters += [np.ascontiguousarray(c, dtype=np.uint32) for c in codes]
+        if sigma0_too is not None:  # a second sigma0 raster, after the codes, to dB as the first (`joint_from_codes`: the co-pol one)
+            self.rasters.append(cast(_to_db(np.asarray(sigma0_too)) if plan.is_db else sigma0_too))
 
     @staticmethod
     def at(a):
@@ -444,7 +446,7 @@ class _DeviceCodes:
     mem = _lib.MEM_DEVICE
     at = staticmethod(_device.at)
 
-    def __init__(self, plan, inc, sigma0, dsig_cr, anc, *codes):
+    def __init__(self, plan, inc, sigma0, dsig_cr, anc, *codes, sigma0_too=None):
         codes = [_code_tensor(c) for c in codes]
         dev = self.dev = codes[0].device
         t = [None if (a is None or np.isscalar(a)) else _device.as_tensor(a, dev) for a in (inc, sigma0, dsig_cr, anc)]
@@ -454,6 +456,9 @@ class _DeviceCodes:
             t[1] = _device.to_db(t[1])
         self.plan, self.ctx = plan, _device.context_of(dev)
         self.rasters = [_device.prep(x, plan.cdtype if k == 3 else plan.dtype, plan.shape) for k, x in enumerate(t)] + [c.contiguous() for c in codes]
+        if sigma0_too is not None:
+            x = _device.as_tensor(sigma0_too, dev)
+            self.rasters.append(_device.prep(_device.to_db(x) if plan.db_by == _plan.DB_TORCH else x, plan.dtype, plan.shape))
 
     def empty(self, dtype=None):  # None: grid codes; uint8: a flag raster
         import torch
@@ -468,9 +473,9 @@ class _DeviceCodes:
                 _device.keep_alive(self.rasters, self.dev)
 
 
-def _codes_call(plan, inc, sigma0, dsig_cr, anc, *codes):
+def _codes_call(plan, inc, sigma0, dsig_cr, anc, *codes, **more):
     """The inputs of a from-codes call where the co-pol codes are: `_DeviceCodes` or `_HostCodes`."""
-    return (_DeviceCodes if _device.is_device_array(codes[0]) else _HostCodes)(plan, inc, sigma0, dsig_cr, anc, *codes)
+    return (_DeviceCodes if _device.is_device_array(codes[0]) else _HostCodes)(plan, inc, sigma0, dsig_cr, anc, *codes, **more)
 
 
 def cross_from_codes(lut_co, lut_cr, plan, codes_co, inc, sigma0_cr, dsig_cr, dual_select=False, codes=False):
@@ -513,6 +518,19 @@ def cost_cr_from_codes(lut_co, lut_cr, plan, codes_co, codes_cr, inc, sigma0_cr,
     k.run(lut_co, lut_cr, lambda ctx, inc, s_cr, dsig, _, cc, ccr: ctx.cost_cr_from_codes_raw(
         plan.lines, plan.samples, plan.code, _real_code(out_dtype), k.mem, inc, cc, ccr, s_cr, dsig, *(k.at(o) for o in outs),
         dsig_cr_scalar=plan.dsig_scalar, sigma0_is_db=plan.is_db))
+    return outs
+
+
+def joint_from_codes(lut_co, lut_cr, plan, codes_co, inc, sigma0_co, anc, sigma0_cr, dsig_cr, dsig_co=0.1, details=False, out_dtype=np.float64):
+    """[codes, J, Jwind, Jsig_co, Jsig_cr] of the joint dual-pol inversion from the co-pol codes `codes_co` (xsw_joint_from_codes;
+    `plan` from `cross_plan`, so dtype, dB route and dsig_cr handling are the fused dual-pol call's): the grid codes of the wind
+    that minimises Jwind_co + Jsig_co + Jsig_cr (numpy: uint32; torch: int32) and, details=True, the cost and its terms there
+    (`out_dtype`; else None: not computed)."""
+    k = _codes_call(plan, inc, sigma0_cr, dsig_cr, anc, codes_co, sigma0_too=sigma0_co)
+    outs = [k.empty()] + [k.empty(out_dtype) if details else None for _ in range(4)]
+    k.run(lut_co, lut_cr, lambda ctx, inc, s_cr, dsig, anc, cc, s_co: ctx.joint_from_codes_raw(
+        plan.lines, plan.samples, plan.code, _real_code(out_dtype), k.mem, inc, cc, s_co, anc, s_cr, dsig, *(k.at(o) for o in outs),
+        dsig_co=dsig_co, dsig_cr_scalar=plan.dsig_scalar, sigma0_is_db=plan.is_db))
     return outs
 
 

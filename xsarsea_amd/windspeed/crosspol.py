@@ -7,6 +7,7 @@ another cross-pol GMF, another `dsig_cr` -- each time one pass of `xsw_cross_fro
     wind_dual = cc.dual(sigma0_vh, dsig_cr=dsig, model="gmf_s1_v2")  # == invert_from_model(inc, vv, vh, ...)[1]
     fit = cc.cost(sigma0_vv, anc)                                  # InversionCost: J at the minimum, its terms, the residual
     bars = cc.uncertainty(sigma0_vv, anc)                          # InversionUncertainty: wspd_std, dir_std, corr, flag
+    best = cc.joint(sigma0_vv, anc, sigma0_vh, dsig_cr=dsig, model="gmf_s1_v2")  # CopolCodes of ONE cost over VV, VH, a-priori
 
 numpy rasters (numpy out) and device rasters (torch CUDA tensors / `__cuda_array_interface__`; torch out, asynchronous on
 torch's current stream) only: xarray / dask containers are not handled here.  The bit equality with the fused call holds for
@@ -77,6 +78,19 @@ class InversionUncertainty:
 
     def __init__(self, wspd_std, dir_std=None, corr=None, flag=None):
         self.wspd_std, self.dir_std, self.corr, self.flag = wspd_std, dir_std, corr, flag
+
+    def __getitem__(self, name):
+        return getattr(self, name)
+
+
+class JointInversion:
+    """Result of `CopolCodes.joint(..., details=True)`: `codes`, the `CopolCodes` of the grid wind that minimises the joint cost
+    J = Jwind_co + Jsig_co + Jsig_cr, and one real raster each (numpy arrays, or torch tensors for device
+    rasters) for J and its three terms at that wind.  NaN where there is no joint solution; Jsig_cr alone is NaN (and J = Jwind +
+    Jsig_co) where the pixel has no cross-pol information and keeps its co-pol answer."""
+
+    def __init__(self, codes, J, Jwind, Jsig_co, Jsig_cr):
+        self.codes, self.J, self.Jwind, self.Jsig_co, self.Jsig_cr = codes, J, Jwind, Jsig_co, Jsig_cr
 
     def __getitem__(self, name):
         return getattr(self, name)
@@ -199,6 +213,26 @@ class CopolCodes:
         return InversionUncertainty(*_engine.uncertainty_from_codes(self.lut_co, plan, self.codes, self.inc, sigma0, ancillary_wind,
                                                                     dsig_co=dsig_co, out_dtype=_real_dtype(out_dtype)))
 
+    def joint(self, sigma0, ancillary_wind, sigma0_dual, dsig_cr=0.1, model=None, dsig_co=None, details=False, out_dtype=None, **kwargs):
+        """The joint dual-pol inversion: a new `CopolCodes`, on the same tables, of the grid wind that minimises ONE cost over
+        both observations and the a-priori wind, J = Jwind_co + Jsig_co + Jsig_cr, where Jsig_cr reads the cross-pol table at the
+        co-pol speed -- instead of the two-step answer of `.dual` and its hard switch at 5 m/s.  `.wind()`,
+        `.cost` and `.uncertainty` work on the result (`.uncertainty`: the co-pol curvature only).  sigma0 / ancillary_wind: the
+        rasters `invert_copol_codes` was given; sigma0_dual, dsig_cr (scalar or raster, e.g. `dsig_from_nesz`), model (the
+        cross-pol one; **kwargs to its `to_lut`) as `.dual`.  These codes serve as the upper bound that confines the search: the
+        answer does not depend on them, the cost of the pass does.  A pixel without cross-pol information (NaN sigma0_dual or
+        dsig_cr) keeps its co-pol answer.  details=True: `JointInversion(codes, J, Jwind, Jsig_co, Jsig_cr)` with real rasters of
+        out_dtype (float64, or float32).  The refusals of `.cost` and `.dual`, before any device call."""
+        _, dsig_co = self._co_step("CopolCodes.joint", sigma0, ancillary_wind, dsig_co)
+        _, lut_cr = self._cross_step("CopolCodes.joint", sigma0_dual, dsig_cr, model, kwargs)
+        dsig = None if np.isscalar(dsig_cr) else dsig_cr
+        plan = _engine.cross_plan(self.shape, self.inc_meta, _meta(sigma0), _meta(ancillary_wind), _meta(sigma0_dual),
+                                  dsig_cr if dsig is None else _meta(dsig), device=self.on_device)
+        out = _engine.joint_from_codes(self.lut_co, lut_cr, plan, self.codes, self.inc, sigma0, ancillary_wind, sigma0_dual, dsig_cr,
+                                       dsig_co=dsig_co, details=details, out_dtype=_real_dtype(out_dtype))
+        codes = CopolCodes(self.inc, out[0], self.lut_co, sigma0_meta=self.sigma0_meta, ancillary_meta=self.ancillary_meta, dsig_co=dsig_co)
+        return JointInversion(codes, *out[1:]) if details else codes
+
     def cost_dual(self, sigma0_dual, codes_cr, dsig_cr=0.1, model=None, parts=True, out_dtype=None, **kwargs):
         """The cost the cross-pol search of `.dual(sigma0_dual, dsig_cr=..., model=..., **kwargs)` minimised, at its minimum:
         `InversionCost` with J = Jsig_cr [+ Jwind_cr] of windspeed.py:257-264 (Jwind NaN and J = Jsig where there is no co-pol
@@ -239,3 +273,15 @@ def invert_copol_codes(inc, sigma0, /, ancillary_wind=None, dsig_co=0.1, model=N
         inc, sigma0, ancillary_wind = np.asarray(inc), np.asarray(sigma0), np.asarray(ancillary_wind)
         codes, _ = _engine.invert_numpy(lut_co, None, inc, sigma0, None, None, ancillary_wind, dsig_co=dsig_co, codes=True)
     return CopolCodes(inc, codes, lut_co, sigma0_meta=_meta(sigma0), ancillary_meta=_meta(ancillary_wind), dsig_co=dsig_co)
+
+
+def invert_joint(inc, sigma0, sigma0_dual, /, ancillary_wind=None, dsig_co=0.1, dsig_cr=0.1, model=None, details=False, **kwargs):
+    """The dual-pol wind as the minimum of ONE cost over sigma0 (co-pol), sigma0_dual (cross-pol) and the a-priori wind (DESIGN.md
+    section 19): `invert_copol_codes(inc, sigma0, ...)` followed by `.joint(sigma0, ancillary_wind, sigma0_dual, ...)`; returns its
+    `.wind()` (complex, antenna convention) or, details=True, (wind, `JointInversion`).  model: (co-pol, cross-pol), as
+    `invert_from_model` takes it for a dual-pol call; **kwargs go to both models' `to_lut`.  numpy or device rasters."""
+    if not isinstance(model, (tuple, list)) or len(model) != 2:
+        raise ValueError("invert_joint needs model=(co-pol model, cross-pol model)")
+    cc = invert_copol_codes(inc, sigma0, ancillary_wind=ancillary_wind, dsig_co=dsig_co, model=model[0], **kwargs)
+    res = cc.joint(sigma0, ancillary_wind, sigma0_dual, dsig_cr=dsig_cr, model=model[1], dsig_co=dsig_co, details=details, **kwargs)
+    return (res.codes.wind(), res) if details else res.wind()
