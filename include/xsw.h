@@ -355,6 +355,45 @@ int xsw_joint_from_codes(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t d
                          double dsig_co, const void *sigma0_cr, const void *dsig_cr, double dsig_cr_scalar, uint32_t *out_code,
                          void *out_J, void *out_Jwind, void *out_Jsig_co, void *out_Jsig_cr);
 
+/* ---- the error bars of the joint solution.  Additive to XSW_VERSION 4.  xsw_uncertainty_from_codes on a code that
+ * xsw_joint_from_codes returned gives the curvature of the CO-POL cost at the joint point, which is not the function that point
+ * minimises.  This entry takes the 3 x 3 stencil of the joint cost itself,
+ *     J[k][l] = (Jwind_co + Jsig_co)(iw + k, ip + l) + Jsig_cr(iw + k),
+ * every element evaluated exactly as xsw_joint_from_codes scores it (bit for bit an element of the dense joint cost), and from
+ * it, with the second differences, determinant and convexity test of xsw_uncertainty_from_codes:
+ *   out_wspd_std, out_dir_std, out_corr   as xsw_uncertainty_from_codes (m/s, degrees, correlation)
+ *   out_u_std, out_v_std, out_corr_uv     the same covariance 2 H^-1 in the components of the complex wind xsw_expand_codes returns
+ *                for the code (u = Re, v = Im, antenna convention).  With Sww = 2 Jpp / det, Spp = 2 Jww / det, Swp = -2 Jwp / det,
+ *                w = w[iw], c = cos_phi[ip], s = sin_phi[ip] of the installed LUT, r = 0.017453292519943295 -- and, when bit 30 of
+ *                the code is set (the wind points along -phi), s and Swp negated: the direction whose covariance with the speed
+ *                enters is the wind's own -- tu = -(w s) r, tv = (w c) r (du and dv per degree of that direction):
+ *                    var_u  = (c c) Sww + 2 (c tu) Swp + (tu tu) Spp
+ *                    var_v  = (s s) Sww + 2 (s tv) Swp + (tv tv) Spp
+ *                    cov_uv = (c s) Sww + (c tv + s tu) Swp + (tu tv) Spp
+ *                out_u_std sqrt(var_u), out_v_std sqrt(var_v), m/s; out_corr_uv cov_uv / sqrt(var_u var_v).  No clamp: a variance
+ *                that rounding makes negative gives NaN.
+ *   out_flag     uint8.  XSW_UNC_NO_SOLUTION, XSW_UNC_WSPD_BORDER, XSW_UNC_PHI_BORDER, XSW_UNC_NOT_CONVEX as in
+ *                xsw_uncertainty_from_codes, tested in its order: any of them means NaN in all six real outputs, and for the first
+ *                three no table is read.  XSW_UNC_NO_CROSSPOL: sigma0_cr or dsig_cr of the pixel is NaN (set whatever the other
+ *                bits are).  The joint inversion kept the co-pol answer there; the stencil leaves Jsig_cr out and the real outputs
+ *                are xsw_uncertainty_from_codes' bit for bit.  This bit alone does not mean NaN.
+ * code: any grid code of the context's CURRENT co-pol LUT, from xsw_joint_from_codes or from the co-pol search.  The other inputs
+ * are xsw_joint_from_codes'.  dsig_cr = +inf gives Jsig_cr = 0: xsw_uncertainty_from_codes' outputs, XSW_UNC_NO_CROSSPOL clear.
+ * A dsig_cr of 0, an infinite sigma0_cr or a non-finite table entry makes the stencil non-finite and ends in XSW_UNC_NOT_CONVEX
+ * (unlike the joint search, a table with such an entry is not refused: nothing here is an arg-min).
+ * Every output may be NULL (not computed, never written); at least one must be given.  Bytes per pixel, float32 rasters: 24 read
+ * (+ 4 with a dsig_cr raster), three 24-byte runs of the co-pol table and up to three cells of the cross-pol one gathered, 4 or 8
+ * written per real output and 1 for the flag.
+ * XSW_ENOLUT without both LUTs; XSW_EINVAL, before any launch: a NULL input, no output, dsig_co NaN or 0, a bad dtype or mem, a
+ * raster too large for one launch.  An empty raster returns XSW_OK.  XSW_MEM_DEVICE: one kernel (k_unc_joint), asynchronous on
+ * the context's stream; XSW_MEM_HOST: upload, kernel, download, one synchronisation. */
+#define XSW_UNC_NO_CROSSPOL 16u
+int xsw_uncertainty_joint_from_codes(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                                     int32_t sigma0_is_db, const void *inc, const uint32_t *code, const void *sigma0_co,
+                                     const void *anc, double dsig_co, const void *sigma0_cr, const void *dsig_cr,
+                                     double dsig_cr_scalar, void *out_wspd_std, void *out_dir_std, void *out_corr, void *out_u_std,
+                                     void *out_v_std, void *out_corr_uv, uint8_t *out_flag);
+
 /* ---- the forward operator on rasters.  Additive to XSW_VERSION 4.  sigma0 in dB that the context's CURRENT co-pol table
  * T[i][w][p] (axes ai, aw, ap) predicts for the wind (wspd, phi) at incidence inc, per pixel, and the derivatives of that
  * interpolant.  Every input is up-cast to float64; only IEEE + - * / follow, in this order, without fused multiply-adds:

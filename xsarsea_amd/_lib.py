@@ -13,6 +13,7 @@ XSW_F32, XSW_F64 = 0, 1
 MEM_HOST, MEM_DEVICE, MEM_HOST_PINNED, MEM_DEVICE_SIGMA0_HOST = 0, 1, 2, 3
 CODE_NAN_RE, CODE_NAN, CODE_PICK_CO, CODE_NO_INDEX = 0xFFFFFFFF, 0xFFFFFFFE, 0x40000000, 0x3FFFFFFF
 UNC_NO_SOLUTION, UNC_WSPD_BORDER, UNC_PHI_BORDER, UNC_NOT_CONVEX = 1, 2, 4, 8  # XSW_UNC_*: the bits of an uncertainty flag raster
+UNC_NO_CROSSPOL = 16  # XSW_UNC_NO_CROSSPOL (xsw_uncertainty_joint_from_codes): no cross-pol information, the co-pol stencil; not a NaN by itself
 SOLVE_NAN, SOLVE_BELOW, SOLVE_ABOVE, SOLVE_TAIL = 1, 2, 4, 8  # XSW_SOLVE_*: the bits of a `retrieve_wspd` flag raster
 DIR_NAN, DIR_BELOW, DIR_ABOVE, DIR_MORE = 1, 2, 4, 8  # XSW_DIR_*: the bits of a `retrieve_dir` flag raster
 ALGO_AUTO, ALGO_PRUNED, ALGO_EXHAUSTIVE, ALGO_EXACT, ALGO_EXHAUSTIVE_F64 = 0, 1, 2, 3, 4
@@ -51,6 +52,7 @@ EXPORTS = (
     "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary",
     "xsw_cross_from_codes", "xsw_cost_from_codes", "xsw_cost_cr_from_codes",
     "xsw_uncertainty_from_codes", "xsw_uncertainty_cr_from_codes", "xsw_joint_from_codes",
+    "xsw_uncertainty_joint_from_codes",
     "xsw_lut_eval", "xsw_lut_eval_cr",
     "xsw_wspd_solve", "xsw_wspd_solve_cr", "xsw_dir_solve",
     "xsw_dsig", "xsw_dsig_flat", "xsw_dsig_wspd",
@@ -225,6 +227,8 @@ def load():
             [ctypes.c_double] + [ctypes.c_void_p] * 2
         lib.xsw_joint_from_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 4 + \
             [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double] + [ctypes.c_void_p] * 5
+        lib.xsw_uncertainty_joint_from_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 4 + \
+            [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double] + [ctypes.c_void_p] * 7
         lib.xsw_lut_eval.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 6
         lib.xsw_lut_eval_cr.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_wspd_solve.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 4 + [ctypes.c_void_p] * 6
@@ -498,6 +502,20 @@ class Context:
         self._check(self._lib.xsw_joint_from_codes(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(sigma0_is_db)), inc, code_co,
                                                    sigma0_co, anc, float(dsig_co), sigma0_cr, dsig_cr, float(dsig_cr_scalar), out_code, out_J,
                                                    out_Jwind, out_Jsig_co, out_Jsig_cr), "xsw_joint_from_codes")
+
+    @_locked
+    def uncertainty_joint_from_codes_raw(self, lines, samples, dtype, out_dtype, mem, inc, code, sigma0_co, anc, sigma0_cr, dsig_cr, out_wspd_std,
+                                         out_dir_std=None, out_corr=None, out_u_std=None, out_v_std=None, out_corr_uv=None, out_flag=None,
+                                         dsig_co=0.1, dsig_cr_scalar=0.1, sigma0_is_db=False):
+        """Thin call of xsw_uncertainty_joint_from_codes (pointers are ints or None): the error bars of the joint dual-pol solution
+        from the curvature of J = Jwind_co + Jsig_co + Jsig_cr around the grid point of every code -- wspd_std (m/s), dir_std
+        (degrees), their correlation, and the same covariance in the components of the complex wind (u_std, v_std in m/s,
+        corr_uv) -- each into a real raster of `out_dtype`, and the uint8 UNC_* flags (None: not computed); dsig_cr None: the
+        scalar broadcast."""
+        self._check(self._lib.xsw_uncertainty_joint_from_codes(self._h, int(lines), int(samples), dtype, out_dtype, mem, int(bool(sigma0_is_db)),
+                                                               inc, code, sigma0_co, anc, float(dsig_co), sigma0_cr, dsig_cr,
+                                                               float(dsig_cr_scalar), out_wspd_std, out_dir_std, out_corr, out_u_std,
+                                                               out_v_std, out_corr_uv, out_flag), "xsw_uncertainty_joint_from_codes")
 
     @_locked
     def uncertainty_from_codes_raw(self, lines, samples, dtype, out_dtype, mem, inc, code_co, sigma0_co, anc, out_wspd_std, out_dir_std=None,

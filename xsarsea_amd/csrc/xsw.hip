@@ -757,6 +757,40 @@ extern "C" int xsw_joint_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, 
     }, who);
 }
 
+// ---- the error bars of the joint solution (xsw.h: xsw_uncertainty_joint_from_codes; kernel: xsw_uncertainty_joint.hpp).  The refusals are
+// xsw_joint_from_codes', except that a non-finite table entry is none: nothing here is an arg-min, such a stencil ends in NOT_CONVEX.
+extern "C" int xsw_uncertainty_joint_from_codes(xsw_ctx *c, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,
+                                                int32_t sigma0_is_db, const void *inc, const uint32_t *code, const void *sigma0_co,
+                                                const void *anc, double dsig_co, const void *sigma0_cr, const void *dsig_cr,
+                                                double dsig_cr_scalar, void *out_wspd_std, void *out_dir_std, void *out_corr,
+                                                void *out_u_std, void *out_v_std, void *out_corr_uv, uint8_t *out_flag)
+{
+    if (!c) return XSW_EINVAL;
+    const char *who = "uncertainty_joint_from_codes";
+    if (int rc = check_raster_call(c, lines, samples, dtype, out_dtype, mem)) return rc;
+    if (!inc || !code || !sigma0_co || !anc || !sigma0_cr) return fail(c, XSW_EINVAL, "%s: an input raster is NULL", who);
+    if (!out_wspd_std && !out_dir_std && !out_corr && !out_u_std && !out_v_std && !out_corr_uv && !out_flag)
+        return fail(c, XSW_EINVAL, "%s: no output requested", who);
+    if (!c->have_co || !c->have_cr) return fail(c, XSW_ENOLUT, "%s: needs a co-pol and a cross-pol LUT on this context", who);
+    if (dsig_co != dsig_co || dsig_co == 0.0) return fail(c, XSW_EINVAL, "%s: dsig_co is NaN or 0", who);
+    UncJointArgs A{};
+    size_t es, os;
+    if (int rc = pixel_count(c, who, lines, samples, dtype, out_dtype, A.n, es, os)) return rc;
+    if (A.n == 0) return XSW_OK;
+    A.dsig_co = dsig_co; A.dsig_cr_scalar = dsig_cr_scalar; A.is_db = sigma0_is_db;
+    const size_t px = (size_t)A.n;
+    Buf b[13] = {in_buf(inc, px * es), in_buf(sigma0_co, px * es), in_buf(anc, px * es * 2), in_buf(sigma0_cr, px * es), in_buf(dsig_cr, px * es),
+                 in_buf(code, px * 4), out_buf(out_wspd_std, px * os), out_buf(out_dir_std, px * os), out_buf(out_corr, px * os),
+                 out_buf(out_u_std, px * os), out_buf(out_v_std, px * os), out_buf(out_corr_uv, px * os), out_buf(out_flag, px)};
+    return run(c, mem, b, [&](Buf (&x)[13]) {
+        A.inc = x[0].dev; A.s_co = x[1].dev; A.anc = x[2].dev; A.s_cr = x[3].dev; A.dsig_cr = x[4].dev;
+        A.code_co = (const unsigned *)x[5].dev;
+        A.out_wspd_std = x[6].dev; A.out_dir_std = x[7].dev; A.out_corr = x[8].dev;
+        A.out_u_std = x[9].dev; A.out_v_std = x[10].dev; A.out_corr_uv = x[11].dev; A.out_flag = x[12].dev;
+        return queue(c, dtype, out_dtype, &PairLaunch::unc_joint, A);
+    }, who);
+}
+
 // ---- the forward operator on rasters (xsw.h: xsw_lut_eval, xsw_lut_eval_cr; kernels: xsw_forward.hpp)
 // One body for the two entries: A holds the caller's pointers.
 static int lut_eval(xsw_ctx *c, const char *who, bool cr, int64_t lines, int64_t samples, int32_t dtype, int32_t out_dtype, int32_t mem,

@@ -254,6 +254,17 @@ struct JointArgs {
     int is_db;
 };
 
+// The arguments of k_unc_joint (xsw_uncertainty_joint.hpp; xsw.h: xsw_uncertainty_joint_from_codes): JointArgs' inputs, each output nullable.
+struct UncJointArgs {
+    const void *inc, *s_co, *anc, *s_cr, *dsig_cr;  // dsig_cr nullable: dsig_cr_scalar broadcast as in load_pixel
+    const unsigned *code_co;
+    void *out_wspd_std, *out_dir_std, *out_corr, *out_u_std, *out_v_std, *out_corr_uv;  // reals of the output dtype
+    void *out_flag;                                                                     // uint8 XSW_UNC_* bits
+    long long n;
+    double dsig_co, dsig_cr_scalar;
+    int is_db;
+};
+
 // The arguments of k_lut_eval_co / k_lut_eval_cr (xsw_forward.hpp; xsw.h: xsw_lut_eval, xsw_lut_eval_cr).
 struct FwdArgs {
     const void *inc, *wspd, *phi;          // phi: k_lut_eval_co only
@@ -280,7 +291,7 @@ struct DirArgs {
 };
 }  // namespace xsw
 
-// The launch of every one-pixel-per-lane raster pass (k_cross_from_codes, k_cost_*, k_unc_*, k_lut_eval_*, k_wspd_solve_*, k_dir_solve_co, k_joint_from_codes): 256 lanes per block
+// The launch of every one-pixel-per-lane raster pass (k_cross_from_codes, k_cost_*, k_unc_*, k_lut_eval_*, k_wspd_solve_*, k_dir_solve_co, k_joint_from_codes, k_unc_joint): 256 lanes per block
 // over n pixels.  An XSW_* code and, with a non-zero one, its message in `err`.
 template <typename Kernel, typename Args>
 static int launch_pixels(Kernel kernel, const xsw::DevTables &tables, const Args &A, long long n, hipStream_t stream, std::string &err)
@@ -294,7 +305,7 @@ static int launch_pixels(Kernel kernel, const xsw::DevTables &tables, const Args
 }
 
 // The launches of one (input dtype, output dtype) pair: the inversion kernels, k_cross_from_codes, k_cost_co / k_cost_cr,
-// k_unc_co / k_unc_cr, k_lut_eval_co / k_lut_eval_cr, k_wspd_solve_co / k_wspd_solve_cr, k_dir_solve_co and k_joint_from_codes.
+// k_unc_co / k_unc_cr, k_lut_eval_co / k_lut_eval_cr, k_wspd_solve_co / k_wspd_solve_cr, k_dir_solve_co, k_joint_from_codes and k_unc_joint.
 // Each returns an XSW_* code and, with a non-zero one, its message in `err`.  One instance per translation unit
 // (xsw_invert_tu.hip, -DXSW_PAIR=0..3: f32->f32, f32->f64, f64->f32, f64->f64), so that the four sets of kernel
 // instantiations compile side by side; it sits behind a host function, which keeps it out of the device pass.
@@ -307,6 +318,7 @@ struct PairLaunch {
     int (*solve)(xsw_ctx *c, const xsw::SolveArgs &A, bool cr, hipStream_t stream, std::string &err);
     int (*dir)(xsw_ctx *c, const xsw::DirArgs &A, hipStream_t stream, std::string &err);
     int (*joint)(xsw_ctx *c, const xsw::JointArgs &A, hipStream_t stream, std::string &err);
+    int (*unc_joint)(xsw_ctx *c, const xsw::UncJointArgs &A, hipStream_t stream, std::string &err);
 };
 const PairLaunch &xsw_pair_0(), &xsw_pair_1(), &xsw_pair_2(), &xsw_pair_3();
 

@@ -18,6 +18,7 @@
 #include "xsw_solve.hpp"
 #include "xsw_dirsolve.hpp"
 #include "xsw_joint.hpp"
+#include "xsw_uncertainty_joint.hpp"
 
 using namespace xsw;
 
@@ -105,6 +106,7 @@ const PairLaunch &XSW_PAIR_NAME(XSW_PAIR)()
         [](xsw_ctx *c, const FwdArgs &A, bool cr, hipStream_t s, std::string &e) { return launch_pixels(cr ? k_lut_eval_cr<TIn, TOut> : k_lut_eval_co<TIn, TOut>, c->T, A, A.n, s, e); },
         [](xsw_ctx *c, const SolveArgs &A, bool cr, hipStream_t s, std::string &e) { return launch_pixels(cr ? k_wspd_solve_cr<TIn, TOut> : k_wspd_solve_co<TIn, TOut>, c->T, A, A.n, s, e); },
         [](xsw_ctx *c, const DirArgs &A, hipStream_t s, std::string &e) { return launch_pixels(k_dir_solve_co<TIn, TOut>, c->T, A, A.n, s, e); },
-        [](xsw_ctx *c, const JointArgs &A, hipStream_t s, std::string &e) { return launch_pixels(k_joint_from_codes<TIn, TOut>, c->T, A, A.n, s, e); }};
+        [](xsw_ctx *c, const JointArgs &A, hipStream_t s, std::string &e) { return launch_pixels(k_joint_from_codes<TIn, TOut>, c->T, A, A.n, s, e); },
+        [](xsw_ctx *c, const UncJointArgs &A, hipStream_t s, std::string &e) { return launch_pixels(k_unc_joint<TIn, TOut>, c->T, A, A.n, s, e); }};
     return pair;
 }

@@ -556,6 +556,18 @@ def uncertainty_cr_from_codes(lut_co, lut_cr, plan, codes_co, codes_cr, inc, sig
     return outs
 
 
+def uncertainty_joint_from_codes(lut_co, lut_cr, plan, codes, inc, sigma0_co, anc, sigma0_cr, dsig_cr, dsig_co=0.1, out_dtype=np.float64):
+    """[wspd_std, dir_std, corr, u_std, v_std, corr_uv] (`out_dtype`) and the uint8 flag raster of the grid codes `codes` from the
+    curvature of the joint cost (xsw_uncertainty_joint_from_codes): the inputs formed as `joint_from_codes` forms them (`plan` from
+    `cross_plan`), the outputs as `uncertainty_from_codes` returns them."""
+    k = _codes_call(plan, inc, sigma0_cr, dsig_cr, anc, codes, sigma0_too=sigma0_co)
+    outs = [k.empty(out_dtype) for _ in range(6)] + [k.empty(np.uint8)]
+    k.run(lut_co, lut_cr, lambda ctx, inc, s_cr, dsig, anc, cc, s_co: ctx.uncertainty_joint_from_codes_raw(
+        plan.lines, plan.samples, plan.code, _real_code(out_dtype), k.mem, inc, cc, s_co, anc, s_cr, dsig, *(k.at(o) for o in outs),
+        dsig_co=dsig_co, dsig_cr_scalar=plan.dsig_scalar, sigma0_is_db=plan.is_db))
+    return outs
+
+
 def _lut_eval(lut, cross, plan, rasters, n_out, out_dtype, call, n_flag=0):
     """The host path of `lut_eval` / `lut_eval_cr` / `wspd_solve` / `wspd_solve_cr` / `dir_solve`, in the manner of `_HostCodes` /
     `_DeviceCodes`: the rasters as the kernel reads them (`plan.dtype`, contiguous), `n_out` outputs of `out_dtype` and after them `n_flag` uint8

@@ -8,6 +8,7 @@ another cross-pol GMF, another `dsig_cr` -- each time one pass of `xsw_cross_fro
     fit = cc.cost(sigma0_vv, anc)                                  # InversionCost: J at the minimum, its terms, the residual
     bars = cc.uncertainty(sigma0_vv, anc)                          # InversionUncertainty: wspd_std, dir_std, corr, flag
     best = cc.joint(sigma0_vv, anc, sigma0_vh, dsig_cr=dsig, model="gmf_s1_v2")  # CopolCodes of ONE cost over VV, VH, a-priori
+    bars = best.uncertainty_joint(sigma0_vv, anc, sigma0_vh, dsig_cr=dsig, model="gmf_s1_v2")  # JointUncertainty: + u_std, v_std, corr_uv
 
 numpy rasters (numpy out) and device rasters (torch CUDA tensors / `__cuda_array_interface__`; torch out, asynchronous on
 torch's current stream) only: xarray / dask containers are not handled here.  The bit equality with the fused call holds for
@@ -91,6 +92,24 @@ class JointInversion:
 
     def __init__(self, codes, J, Jwind, Jsig_co, Jsig_cr):
         self.codes, self.J, self.Jwind, self.Jsig_co, self.Jsig_cr = codes, J, Jwind, Jsig_co, Jsig_cr
+
+    def __getitem__(self, name):
+        return getattr(self, name)
+
+
+class JointUncertainty:
+    """Result of `CopolCodes.uncertainty_joint`: the error bars of the joint dual-pol wind, from the curvature of the cost that wind
+    minimises, J = Jwind_co + Jsig_co + Jsig_cr, around the stored grid point.  wspd_std (m/s), dir_std
+    (degrees) and corr as in `InversionUncertainty`; u_std, v_std (m/s) and corr_uv are the same covariance in the components of
+    the complex wind `.wind()` returns (u its real, v its imaginary part: antenna convention), the form a merge or an assimilation
+    reads.  One real raster each (numpy arrays, or torch tensors for device rasters) and flag, a uint8 raster of bits (`FLAGS`):
+    1, 2, 4, 8 as in `InversionUncertainty` -- any of them: NaN in all six real rasters -- and 16, no cross-pol information
+    (NaN sigma0_dual or dsig_cr): the joint inversion kept the co-pol answer there and the rasters hold the co-pol error bars,
+    those of `.uncertainty`; 16 alone does not mean NaN."""
+    FLAGS = {"no_solution": 1, "wspd_border": 2, "phi_border": 4, "not_convex": 8, "no_crosspol": 16}
+
+    def __init__(self, wspd_std, dir_std, corr, u_std, v_std, corr_uv, flag):
+        self.wspd_std, self.dir_std, self.corr, self.u_std, self.v_std, self.corr_uv, self.flag = wspd_std, dir_std, corr, u_std, v_std, corr_uv, flag
 
     def __getitem__(self, name):
         return getattr(self, name)
@@ -208,7 +227,9 @@ class CopolCodes:
         """The error bars of the co-pol wind: `InversionUncertainty` with wspd_std (m/s), dir_std (degrees), their correlation
         and a uint8 flag raster, from the second differences of J_co (windspeed.py:216-225) over the 3 x 3 grid points around the
         stored one (include/xsw.h: xsw_uncertainty_from_codes).  Arguments and refusals as `cost`.  A solution on the first or
-        last index of an axis has no estimate (flag 2 / 4): a 0..360 direction axis is not wrapped, a 0..180 one not mirrored."""
+        last index of an axis has no estimate (flag 2 / 4): a 0..360 direction axis is not wrapped, a 0..180 one not mirrored.
+        On codes returned by `.joint` this is the curvature of the co-pol cost only, not of the cost those codes minimise:
+        `.uncertainty_joint` gives the error bars of the joint wind."""
         plan, dsig_co = self._co_step("CopolCodes.uncertainty", sigma0, ancillary_wind, dsig_co)
         return InversionUncertainty(*_engine.uncertainty_from_codes(self.lut_co, plan, self.codes, self.inc, sigma0, ancillary_wind,
                                                                     dsig_co=dsig_co, out_dtype=_real_dtype(out_dtype)))
@@ -232,6 +253,21 @@ class CopolCodes:
                                        dsig_co=dsig_co, details=details, out_dtype=_real_dtype(out_dtype))
         codes = CopolCodes(self.inc, out[0], self.lut_co, sigma0_meta=self.sigma0_meta, ancillary_meta=self.ancillary_meta, dsig_co=dsig_co)
         return JointInversion(codes, *out[1:]) if details else codes
+
+    def uncertainty_joint(self, sigma0, ancillary_wind, sigma0_dual, dsig_cr=0.1, model=None, dsig_co=None, out_dtype=None, **kwargs):
+        """The error bars of the joint dual-pol wind: `JointUncertainty(wspd_std, dir_std, corr, u_std, v_std, corr_uv, flag)` from
+        the second differences of the JOINT cost J = Jwind_co + Jsig_co + Jsig_cr over the 3 x 3 grid points around the stored one
+        (include/xsw.h: xsw_uncertainty_joint_from_codes), with the covariance also in the (u, v) components
+        of `.wind()`.  Meant for the codes `.joint` returned, with the arguments it was given; any grid codes of the same tables
+        do.  A pixel without cross-pol information (NaN sigma0_dual or dsig_cr) gets the co-pol error bars of `.uncertainty` and
+        flag bit 16.  out_dtype: float64 (default) or float32.  The refusals of `.joint`, before any device call."""
+        _, dsig_co = self._co_step("CopolCodes.uncertainty_joint", sigma0, ancillary_wind, dsig_co)
+        _, lut_cr = self._cross_step("CopolCodes.uncertainty_joint", sigma0_dual, dsig_cr, model, kwargs)
+        dsig = None if np.isscalar(dsig_cr) else dsig_cr
+        plan = _engine.cross_plan(self.shape, self.inc_meta, _meta(sigma0), _meta(ancillary_wind), _meta(sigma0_dual),
+                                  dsig_cr if dsig is None else _meta(dsig), device=self.on_device)
+        return JointUncertainty(*_engine.uncertainty_joint_from_codes(self.lut_co, lut_cr, plan, self.codes, self.inc, sigma0, ancillary_wind,
+                                                                      sigma0_dual, dsig_cr, dsig_co=dsig_co, out_dtype=_real_dtype(out_dtype)))
 
     def cost_dual(self, sigma0_dual, codes_cr, dsig_cr=0.1, model=None, parts=True, out_dtype=None, **kwargs):
         """The cost the cross-pol search of `.dual(sigma0_dual, dsig_cr=..., model=..., **kwargs)` minimised, at its minimum:
