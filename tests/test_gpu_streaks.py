@@ -9,6 +9,7 @@ import pytest
 
 import gradients_ref as ref
 import streaks_ref as sref
+import strip_shapes
 from test_gpu_gradients import LINE, SAMPLE, scene
 from test_gpu_kernel import synthetic_scene
 from test_gpu_streams import ASYNC, _held_back, _in_flight, _read_back
@@ -210,7 +211,7 @@ def check_ancillary(got, want, anc, what):
     return int(fallback.sum())
 
 
-@pytest.mark.parametrize("case", ["odd", "one_row", "one_window", "irregular", "dense", "wide"])
+@pytest.mark.parametrize("case", ["odd", "one_row", "one_window", "irregular", "dense", "wide", "dense_blocks"])
 def test_ancillary_from_streaks_matches_the_restatement(case):
     rng = np.random.default_rng(40)
     if case == "odd":  # odd sizes, regular centres that start inside the raster and end outside
@@ -231,6 +232,21 @@ def test_ancillary_from_streaks_matches_the_restatement(case):
     elif case == "dense":  # more centres than lines: the line bracket changes on every line
         shape, wl, ws = (33, 300), np.arange(80) * 0.5, np.arange(40) * 8.0
         line, sample = np.arange(33.0), np.arange(300.0)
+    elif case == "dense_blocks":
+        # nine lines per workgroup (tests/strip_shapes.py: two groups of XSW_STREAKS_LINES and one more line, two lines in the
+        # last workgroup).  Centres every 2.5 lines over the first third: the line bracket changes after 3, 2, 3, 2, ... lines,
+        # which against blocks of nine lines is at every position of every group; every 37 lines over the second third: blocks
+        # that keep their corners throughout, blocks that change them once; one bracket over the rest
+        shape = strip_shapes.shape("streaks")
+        rpb = strip_shapes.SHAPES["streaks"].grid[2]
+        line, sample = np.arange(float(shape[0])), np.arange(float(shape[1]))
+        third = shape[0] // 3
+        wl = np.concatenate([np.arange(0, third, 2.5), np.arange(third, 2 * third, 37.0), [shape[0] - 1.0]])
+        ws = np.arange(9) * 251.0 + 17
+        first = np.searchsorted(wl, line, side="right") - 1  # the bracket's first centre, as sref.bracket finds it
+        changes = np.flatnonzero(np.diff(first)) + 1
+        assert rpb > 8 and {int(p) for p in changes % rpb} == set(range(rpb))  # at every line of a block, its first included
+        assert not np.diff(first[2 * third:-1]).any() and first[-1] == len(wl) - 1  # (the last line sits on the last centre)
     else:  # several 256-sample column strips and line blocks
         shape, wl, ws = (1031, 1237), np.arange(6) * 200.0, np.arange(7) * 200.0
         line, sample = np.arange(1031.0), np.arange(1237.0)

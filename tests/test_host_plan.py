@@ -299,3 +299,42 @@ def test_strip_grid_is_the_grid_of_detrend_and_of_the_nesz_write_pass(ask):
         assert d8 == parent_detrend_grid(lines, samples, 8), (lines, samples)
         assert e == parent_nesz_write_grid(lines, samples), (lines, samples)
         assert d[1] <= 65535 and e[1] <= 65535 and d[1] * d[2] >= lines and e[1] * e[2] >= lines
+
+
+def source_define(name):
+    """The integer a kernel source #defines `name` as (the kernels' own constants are not in the header under test)."""
+    import re
+    found = []
+    for fn in sorted(os.listdir(CSRC)):
+        with open(os.path.join(CSRC, fn)) as f:
+            found += re.findall(r"^\s*#\s*define\s+" + name + r"\s+(\d+)\s*(?://.*)?$", f.read(), re.M)
+    assert len(set(found)) == 1, (name, found)
+    return int(found[0])
+
+
+def test_strip_shapes_stay_multi_line(ask):
+    """Every raster of tests/strip_shapes.py, through the compiled strip_grid with its kernel's column divisor and workgroups per
+    CU: at least two column strips, more than four lines per workgroup and no whole number of four-line groups, a shorter last
+    workgroup that is no whole number of groups either -- and the grid the GPU tests place their special values by.  A change of
+    strip_grid, XSW_DETREND_WG_PER_CU or XSW_NESZ_EV that sends these rasters back to one line per workgroup fails here, on the
+    CPU, instead of silently emptying the GPU tests."""
+    import strip_shapes
+    assert NESZ_EV == source_define("XSW_NESZ_EV")
+    wg_per_cu = {"detrend": source_define("XSW_DETREND_WG_PER_CU"), "dsig_flat": 0, "streaks": 0}  # 0: strip_grid's default
+    col_div = {"detrend": 4, "dsig_flat": NESZ_EV, "streaks": 1}
+    assert len(strip_shapes.SHAPES) == 5 and {e.kernel for e in strip_shapes.SHAPES.values()} == set(col_div)
+    for key, e in sorted(strip_shapes.SHAPES.items()):
+        assert e.col_div == col_div[e.kernel], key
+        ((gx, gy, rpb),) = ask(("grid", e.lines, ceil_div(e.samples, e.col_div), wg_per_cu[e.kernel]))
+        last = e.lines - (gy - 1) * rpb
+        print(key, (e.lines, e.samples), "->", (gx, gy, rpb, last))
+        assert gx >= 2, key
+        assert rpb >= 5 and rpb % 4 != 0, key
+        assert 0 < last < rpb and last % 4 != 0, key
+        assert (gx, gy, rpb, last) == e.grid, key
+        assert strip_shapes.block_lines(key, -1) == list(range(e.lines - last, e.lines)), key
+    assert strip_shapes.SHAPES["streaks"].grid[2] > 8  # the streaks pass: a second unrolled group in every workgroup
+    # the vector and the element-wise raster of a kernel differ in the sample count's divisibility alone
+    for a, b, q in (("detrend_vec", "detrend_elem", 4), ("dsig_flat_vec", "dsig_flat_elem", 2)):
+        assert strip_shapes.SHAPES[a].samples % q == 0 and strip_shapes.SHAPES[b].samples % q != 0
+        assert strip_shapes.SHAPES[a].grid == strip_shapes.SHAPES[b].grid
