@@ -585,6 +585,32 @@ int xsw_lut_build(xsw_ctx *ctx, int32_t gmf_id, const double *inc_raw, int32_t n
  * (windspeed/models.py:186-230) for a LUT that was built on the device.  Synchronous. */
 int xsw_lut_read(xsw_ctx *ctx, int32_t cross, double *out_db);
 
+/* DIAGNOSTIC, no caller needs it: copies one of the tables a co-pol install derived on the device back to the host, whole,
+ * pads and slack included (they are part of what the kernels read unmasked), for the tests that hold every table to a host
+ * restatement.  Additive to XSW_VERSION 4.  With ppad = n_phi rounded up to 4, wpad = n_wspd rounded up to 4, nbr = ceil(n_wspd /
+ * 4), nbc = ceil(n_phi / 16), nbc4 = ceil(n_phi / 4), ncr = ceil(nbr / 8), ncc = ceil(nbc / 2), blk_g = max(1, 64 / nbc) and
+ * nbands = ceil(nbr / blk_g) (csrc/xsw_lutplan.hpp: CoGeometry), the tables and their sizes are:
+ *   XSW_TAB_CO         double  [n_inc * n_wspd + 260][ppad]          the phi-padded table, 260 slack rows
+ *   XSW_TAB_CO32       float   the same layout
+ *   XSW_TAB_COT        double  [n_inc][n_phi][wpad] + 512 elements   the transposed slices
+ *   XSW_TAB_MONO_ROWS  int32   [n_inc]
+ *   XSW_TAB_TAIL_MIN   double  [n_inc][8][ppad]                      optional
+ *   XSW_TAB_INV_GRID   double  [n_inc][3]                            optional (with XSW_TAB_INV_ROWS)
+ *   XSW_TAB_INV_ROWS   uint16  [n_inc][2048][ppad]                   optional
+ *   XSW_TAB_BLK        float   [n_inc][nbr][nbc][2]   {min, max}     optional (with XSW_TAB_CELLMM, XSW_TAB_BANDMM)
+ *   XSW_TAB_BLK4       float   [n_inc][nbr][nbc4][2]                 optional
+ *   XSW_TAB_CELLMM     float   [n_inc][ncr][ncc][2]                  optional
+ *   XSW_TAB_BANDMM     float   [n_inc][nbands][2]                    optional
+ *   XSW_TAB_SCALARS    double  [3]: 1.0 when the table holds no NaN / inf else 0.0, the largest finite |dB|, `prunable` (0 or 1)
+ * Synchronises the context's stream, then copies; launches nothing.  Returns XSW_OK, or XSW_TAB_ABSENT (> 0, no message, `out`
+ * untouched) for an optional table the current install did not build -- its gate failed, an environment switch, an allocation
+ * that was refused -- whatever `bytes` says.  XSW_ENOLUT without a co-pol LUT; XSW_EINVAL, `out` untouched, for an unknown id or
+ * a `bytes` that is not the table's size. */
+enum { XSW_TAB_CO = 0, XSW_TAB_CO32 = 1, XSW_TAB_COT = 2, XSW_TAB_MONO_ROWS = 3, XSW_TAB_TAIL_MIN = 4, XSW_TAB_INV_GRID = 5,
+       XSW_TAB_INV_ROWS = 6, XSW_TAB_BLK = 7, XSW_TAB_BLK4 = 8, XSW_TAB_CELLMM = 9, XSW_TAB_BANDMM = 10, XSW_TAB_SCALARS = 11 };
+#define XSW_TAB_ABSENT 1
+int xsw_lut_table_read(xsw_ctx *ctx, int32_t which, void *out, size_t bytes);
+
 /* Built-in analytic GMFs on the device: out[i] = gmf(inc[i], wspd[i], phi[i]) over n already-broadcast float64
  * elements (phi may be NULL for cross-pol models).  Replaces the numba-vectorised forward GMF of
  * GmfModel.__call__(..., broadcast=True) (windspeed/gmfs.py:202-214, :293-316) for the models of gmfs_impl.py.

@@ -25,6 +25,10 @@ observed sigma0 in dB, c = w*(cos phi, sin phi) a candidate and L its LUT value:
 """
 import numpy as np
 
+# the correctly rounded thresholds of the inverse-row table are formed in ONE place for model and restatement, so comparing the two
+# cannot see a fault in that function: tests/test_lut_tables_cpu.py::test_fused_threshold_arithmetic holds it on its own
+from lut_tables_ref import thresholds
+
 
 def screening_eps(gmin, m2):
     return 1e-9 * (1.0 + abs(gmin) + m2)
@@ -252,10 +256,10 @@ def band_pruned_argmin(slice_wp, wspd, phi, cphi, sphi, phi_180, s, a, b, dsig, 
 def inverse_rows(col, mono, t0, width, bins):
     """The table of one column: numpy restatement of k_inv_rows."""
     out = np.zeros(bins, dtype=np.int64)
+    thr = thresholds(t0, width, bins=bins)  # b * width + t0 rounded once, as the kernel's fma; formed once per grid, not per column
     r = 0
     for b in range(1, bins):
-        thr = b * width + t0  # the kernel uses fma; the rounding difference is what the in-kernel checks absorb either way
-        while r < mono and col[r] < thr:
+        while r < mono and col[r] < thr[b]:
             r += 1
         out[b] = r
     return out

@@ -45,7 +45,7 @@ GMF_IDS = {"gmf_cmod5": 0, "gmf_cmod5n": 1, "gmf_cmod5n_pr_zhangA": 2, "gmf_cmod
 EXPORTS = (
     "xsw_version", "xsw_device_count", "xsw_ctx_create", "xsw_ctx_destroy", "xsw_last_error", "xsw_set_stream", "xsw_use_own_stream",
     "xsw_synchronize", "xsw_lut_upload", "xsw_invert", "xsw_stats_enable", "xsw_stats_read", "xsw_stats_read_chain", "xsw_detrend", "xsw_lut_interp", "xsw_gmf_eval",
-    "xsw_nesz_flatten", "xsw_lut_build", "xsw_lut_read", "xsw_timing_enable", "xsw_timing_read", "xsw_expand_codes", "xsw_expand_codes_on_stream",
+    "xsw_nesz_flatten", "xsw_lut_build", "xsw_lut_read", "xsw_lut_table_read", "xsw_timing_enable", "xsw_timing_read", "xsw_expand_codes", "xsw_expand_codes_on_stream",
     "xsw_host_alloc", "xsw_host_free", "xsw_set_host_threads", "xsw_grad_area", "xsw_grad_r2", "xsw_grad_local", "xsw_grad_hist",
     "xsw_grad_r2_sqrt", "xsw_grad_local_sqrt", "xsw_grad_smooth", "xsw_grad_mean", "xsw_grad_filter",
     "xsw_grad_hist_masked", "xsw_grad_keep_f64", "xsw_grad_keep_u8",
@@ -107,6 +107,29 @@ _SIG = {"l": (ctypes.c_int64, int), "i": (ctypes.c_int32, int), "d": (ctypes.c_d
 
 class XswError(RuntimeError):
     pass
+
+
+TAB_ABSENT = 1  # XSW_TAB_ABSENT: what xsw_lut_table_read answers for an optional table the install did not build
+
+
+def co_table_layouts(n_inc, n_w, n_phi):
+    """name -> (XSW_TAB_* id, dtype, shape) of every table `xsw_lut_table_read` copies, for a co-pol LUT of this shape: the
+    element counts of CoGeometry (csrc/xsw_lutplan.hpp).  `co`, `co32` and `coT` are flat (their slack follows the body)."""
+    def up(a, b):
+        return -(-a // b)
+
+    ppad, wpad = up(n_phi, 4) * 4, up(n_w, 4) * 4
+    nbr, nbc, nbc4 = up(n_w, 4), up(n_phi, 16), up(n_phi, 4)
+    ncr, ncc = up(nbr, 8), up(nbc, 2)
+    nbands = up(nbr, max(1, 64 // nbc))
+    n_pad = (n_inc * n_w + 260) * ppad
+    return {
+        "co": (0, np.float64, (n_pad,)), "co32": (1, np.float32, (n_pad,)), "coT": (2, np.float64, (n_inc * n_phi * wpad + 512,)),
+        "mono_rows": (3, np.int32, (n_inc,)), "tail_min": (4, np.float64, (n_inc, 8, ppad)), "inv_grid": (5, np.float64, (n_inc, 3)),
+        "inv_rows": (6, np.uint16, (n_inc, 2048, ppad)), "blk": (7, np.float32, (n_inc, nbr, nbc, 2)),
+        "blk4": (8, np.float32, (n_inc, nbr, nbc4, 2)), "cellmm": (9, np.float32, (n_inc, ncr, ncc, 2)),
+        "bandmm": (10, np.float32, (n_inc, nbands, 2)), "scalars": (11, np.float64, (3,)),
+    }
 
 
 class LutStruct(ctypes.Structure):
@@ -211,6 +234,7 @@ def load():
         lib.xsw_lut_build.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                       ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(LutStruct)]
         lib.xsw_lut_read.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+        lib.xsw_lut_table_read.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t]
         lib.xsw_timing_enable.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.xsw_timing_read.argtypes = [ctypes.c_void_p, ctypes.POINTER(Timing)]
         lib.xsw_expand_codes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 4
@@ -372,6 +396,18 @@ class Context:
         """xsw_lut_read: the context's current dB table as a host array of `shape` (the caller knows the axes)."""
         out = np.empty(shape, dtype=np.float64)
         self._check(self._lib.xsw_lut_read(self._h, int(bool(cross)), _ptr(out)), "xsw_lut_read")
+        return out
+
+    @_locked
+    def read_lut_table(self, name, lut_shape):
+        """xsw_lut_table_read (a diagnostic: the tests' view of what a co-pol install derived): table `name` of
+        `co_table_layouts(*lut_shape)` as a host array, or None when the install did not build it."""
+        which, dtype, shape = co_table_layouts(*lut_shape)[name]
+        out = np.empty(shape, dtype=dtype)
+        rc = self._lib.xsw_lut_table_read(self._h, which, _ptr(out), out.nbytes)
+        if rc == TAB_ABSENT:
+            return None
+        self._check(rc, "xsw_lut_table_read")
         return out
 
     @_locked

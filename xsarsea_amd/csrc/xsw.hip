@@ -479,6 +479,44 @@ extern "C" int xsw_lut_read(xsw_ctx *c, int32_t cross, double *out_db)
     return XSW_OK;
 }
 
+// Diagnostic: one derived table of the current co-pol install, whole (pads and slack included), or the install's scalars.
+// Element counts from CoGeometry, as install_co allocated them.  Read-only, no kernel.
+extern "C" int xsw_lut_table_read(xsw_ctx *c, int32_t which, void *out, size_t bytes)
+{
+    if (!c || !out) return XSW_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->have_co) return fail(c, XSW_ENOLUT, "lut_table_read: no co-pol LUT on this context");
+    const DevTables &T = c->T;
+    const CoGeometry g{T.n_inc, T.n_w, T.n_phi};
+    const void *src = nullptr;
+    size_t want = 0;
+    switch (which) {
+    case XSW_TAB_CO: src = T.co; want = g.n_pad * sizeof(double); break;
+    case XSW_TAB_CO32: src = T.co32; want = g.n_pad * sizeof(float); break;
+    case XSW_TAB_COT: src = T.coT; want = g.coT_n * sizeof(double); break;
+    case XSW_TAB_MONO_ROWS: src = T.mono_rows; want = (size_t)g.n_inc * sizeof(int); break;
+    case XSW_TAB_TAIL_MIN: src = T.tail_min; want = g.tail_n * sizeof(double); break;
+    case XSW_TAB_INV_GRID: src = T.inv_grid; want = g.inv_grid_n * sizeof(double); break;
+    case XSW_TAB_INV_ROWS: src = T.inv_rows; want = g.inv_n * sizeof(unsigned short); break;
+    case XSW_TAB_BLK: src = T.blk; want = (size_t)g.nblk * sizeof(float2); break;
+    case XSW_TAB_BLK4: src = T.blk4; want = (size_t)g.nblk4 * sizeof(float2); break;
+    case XSW_TAB_CELLMM: src = T.cellmm; want = (size_t)g.ncell * sizeof(float2); break;
+    case XSW_TAB_BANDMM: src = T.bandmm; want = (size_t)g.nband * sizeof(float2); break;
+    case XSW_TAB_SCALARS: want = 3 * sizeof(double); break;
+    default: return fail(c, XSW_EINVAL, "lut_table_read: unknown table id %d", (int)which);
+    }
+    if (which != XSW_TAB_SCALARS && !src) return XSW_TAB_ABSENT;  // an optional table this install did not build
+    if (bytes != want) return fail(c, XSW_EINVAL, "lut_table_read: table %d holds %zu bytes, the buffer %zu", (int)which, want, bytes);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (which == XSW_TAB_SCALARS) {
+        const double s[3] = {c->co_finite ? 1.0 : 0.0, T.co_absmax, (double)T.prunable};
+        memcpy(out, s, sizeof s);
+        return XSW_OK;
+    }
+    HIPCHK(c, hipMemcpy(out, src, want, hipMemcpyDeviceToHost));
+    return XSW_OK;
+}
+
 // ---------------------------------------------------------------------------------------- invert
 static int dispatch_invert(xsw_ctx *c, const KArgs &A, int dtype, int out_dtype, int algo, const LaunchCtl &lc, std::string &err)
 {
