@@ -43,23 +43,75 @@ def test_r2_and_ampl(dtype, shape):
     assert_close(gradients._r2(s0, True), np.sqrt(r), 1e-12)
 
 
+def assert_local_close(G2, G3, C, g2, g3, c):
+    """(G2, G3, c) of the device against the restatement's.  R2(grad**2) sums signed values: the scale of an error is the magnitude
+    of what was summed, G3; G2 is its square root, whose error grows where |R2(grad**2)| << G3, so G2 is compared through its
+    square and, where c is not tiny, its angle."""
+    scale = 1e-12 * np.nan_to_num(g3)
+    assert_close((G2 ** 2).real, (g2 ** 2).real, 1e-12, scale)
+    assert_close((G2 ** 2).imag, (g2 ** 2).imag, 1e-12, scale)
+    np.testing.assert_array_equal(np.isnan(G2.real), np.isnan(g2.real))
+    m = c > 1e-6
+    if m.any():
+        d = np.angle(G2[m]) - np.angle(g2[m])
+        assert np.abs((d + np.pi / 2) % np.pi - np.pi / 2).max() < 1e-9  # modulo pi: +-pi/2 is one direction
+    assert_close(G3, g3, 1e-12)
+    assert_close(C, c, 1e-12, 1e-12)
+
+
 @pytest.mark.parametrize("shape", [(203, 317), (66, 31)])
 def test_local_gradients(shape):
     ampl = np.sqrt(ref.R2(scene((2 * shape[0] + 1, 2 * shape[1]), np.float64, 2)))
     g2, g3, c = ref.local_gradients(ampl)
     lg = gradients.local_gradients(ampl)
-    # R2(grad**2) sums signed values: the scale of an error is the magnitude of what was summed, G3; G2 is its square root, whose
-    # error grows where |R2(grad**2)| << G3, so G2 is compared through its square and, where c is not tiny, its angle
-    scale = 1e-12 * np.nan_to_num(g3)
-    assert_close((lg.G2 ** 2).real, (g2 ** 2).real, 1e-12, scale)
-    assert_close((lg.G2 ** 2).imag, (g2 ** 2).imag, 1e-12, scale)
-    np.testing.assert_array_equal(np.isnan(lg.G2.real), np.isnan(g2.real))
-    m = c > 1e-6
-    d = np.angle(lg.G2[m]) - np.angle(g2[m])
-    assert np.abs((d + np.pi / 2) % np.pi - np.pi / 2).max() < 1e-9  # modulo pi: +-pi/2 is one direction
-    assert_close(lg.G3, g3, 1e-12)
-    assert_close(lg.c, c, 1e-12, 1e-12)
+    assert (c > 1e-6).any()
+    assert_local_close(lg.G2, lg.G3, lg.c, g2, g3, c)
     np.testing.assert_array_equal(lg.line, ref.coarsen_coords(np.arange(ampl.shape[0]), 2))
+
+
+# fine shapes whose coarse grids lie on the seams of the 16 x 16 tiles of k_grad_r2 / k_grad_local or are thinner than a tile's
+# halo: coarse 1 x 1, 1 x 350 and 350 x 1 (thin strips across 22 tiles), 15 (16k - 1: the reflected halo source is the tile's
+# last real row), 17 and 33 (16k + 1: the last tile holds one row and the halo cells past it are clamped), 16 x 1 and 2 x 33
+THIN_SHAPES = [(2, 2), (2, 3), (3, 2), (3, 3), (2, 700), (700, 3), (30, 31), (34, 35), (66, 67), (33, 2), (4, 66)]
+THIN_CASES = [(s, False) for s in THIN_SHAPES] + [((34, 35), True), ((66, 67), True)]
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("shape,nan_edges", THIN_CASES, ids=lambda v: "nan_edges" if v is True else "" if v is False else f"{v[0]}x{v[1]}")
+def test_tile_kernels_on_seams_and_thin_rasters(shape, nan_edges, dtype):
+    """R2, sqrt(R2), local_gradients and the two raw entry points that root sigma0 on load (xsw_grad_r2_sqrt,
+    xsw_grad_local_sqrt) against the restatement at this file's tolerances (1e-12; G2 through its square and its angle), on
+    rasters of one tile or less, of one coarse row or column across many tiles, and with a coarse axis of 16k - 1 and 16k + 1.
+    nan_edges: NaN at the four corners and once on each edge, so that the reflected halos carry NaN; the NaN positions must be
+    the restatement's.  No +-inf: the restatement convolves grad**2 as complex numbers and the kernel as two real planes, which
+    differ on inf * 0, and an infinite sigma0 is no input this module defines."""
+    from xsarsea_amd._raster import _Call
+    L, S = shape
+    s0 = scene(shape, dtype, 14 + L + S, land=False)
+    if nan_edges:
+        for y, x in ((0, 0), (0, S - 1), (L - 1, 0), (L - 1, S - 1), (0, S // 2), (L - 1, S // 3), (L // 2, 0), (L // 3, S - 1)):
+            s0[y, x] = np.nan
+    assert np.isnan(s0).sum() == (8 if nan_edges else 0) and not np.isinf(s0).any()
+    r = ref.R2(s0)
+    assert r.shape == (L // 2, S // 2) and np.isfinite(r).any()
+    assert_close(gradients.R2(s0), r, 1e-12)
+    assert_close(gradients._r2(s0, True), np.sqrt(r), 1e-12)
+    root = np.sqrt(s0)                                                    # in the input's dtype, widened afterwards
+    assert root.dtype == dtype
+    ampl = root.astype(np.float64)
+    g2, g3, c = ref.local_gradients(ampl)
+    lg = gradients.local_gradients(ampl)
+    assert_local_close(lg.G2, lg.G3, lg.c, g2, g3, c)
+    call = _Call(s0)
+    x = call.prep(s0)
+    r2_sq, G3, C = (call.empty(r.shape, np.float64) for _ in range(3))
+    G2 = call.empty(r.shape, np.complex128)
+    call.launch("grad_r2_sqrt_raw", L, S, call.xsw_dtype(x), call.mem, x, r2_sq)
+    call.launch("grad_local_sqrt_raw", L, S, call.xsw_dtype(x), call.mem, x, G2, G3, C)
+    assert_close(r2_sq, ref.R2(ampl), 1e-12)
+    assert_local_close(G2, G3, C, g2, g3, c)
+    if nan_edges:
+        assert np.isnan(r).any() and np.isnan(g3).any() and np.isfinite(g3).any()
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])

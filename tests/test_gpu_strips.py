@@ -5,7 +5,9 @@ unrolled loop and a short last block; at the small rasters of the other modules 
 tail loop runs there, once.  The rasters of tests/strip_shapes.py give each workgroup six lines (one unrolled group + two
 tail lines; the last workgroup fewer), with 16-byte / pair accesses and element-wise; tests/test_host_plan.py keeps them
 there.  k_gmf_eval and k_dsig_wspd are capped at 4096 workgroups of 256 threads: n = 2 * 4096 * 256 + 257 sends every thread
-through its loop twice and the first 257 a third time.
+through its loop twice and the first 257 a third time; so does k_expand (256 * 16 workgroups) on as many grid codes, and
+k_grad_area (65 536 workgroups) at 16 797 700 outputs.  k_grad_keep is a strip kernel on the OUTPUT grid: the keep entries of
+tests/strip_shapes.py give each workgroup five or six output rows (three in the last), one entry per instantiation.
 
 References and bounds:
   k_detrend     numpy's IEEE quotient sigma0.astype(float64) / ratio[None, :], rounded once with .astype(float32) for float32
@@ -15,12 +17,16 @@ References and bounds:
                 exponent, as tests/test_gpu_dsig.py::test_fused_against_the_reference.
   k_gmf_eval    the same inputs in slices of at most 4096 * 256 elements (one pass per thread): no tolerance; the oracle's
                 formulas to 1e-13 relative as tests/test_gpu_api.py::test_forward_gmf_device.
-  k_dsig_wspd   the host function, 1e-12 absolute (values in [0, 1]) as tests/test_gpu_dsig.py."""
+  k_dsig_wspd   the host function, 1e-12 absolute (values in [0, 1]) as tests/test_gpu_dsig.py.
+  k_grad_keep   masked_ref.keep_blocks on the inputs of tests/keep_cases.py: no tolerance (uint8 masks).
+  k_expand      the same codes in slices of at most 4096 * 256, and the host expansion (expand_host): no tolerance, on the bits.
+  k_grad_area   gradients_ref.area: array_equal, as tests/test_gpu_gradients.py::test_area."""
 import functools
 
 import numpy as np
 import pytest
 
+import keep_cases
 import strip_shapes
 from test_gpu_dsig import NAMES, WSPD_NAMES, _assert_close, _host, _rasters
 
@@ -311,3 +317,232 @@ def test_get_dsig_wspd_beyond_one_pass_per_thread(gpu_ctx, name):
     assert isinstance(got, torch.Tensor) and got.is_cuda
     worst = _assert_close(got.cpu().numpy(), want, name, atol=1e-12)
     print(f"get_dsig_wspd {name}: max abs diff over {N_STRIDE} elements {worst:.3e} (bound 1e-12)")
+
+
+# ---------------------------------------------------------------------------------------------------------- k_grad_keep
+def _rows_of(bad, key):
+    """For a failure message: the output rows that differ, as (row, workgroup row, row within it)."""
+    rpb = strip_shapes.SHAPES[key].grid[2]
+    rows = np.flatnonzero(np.asarray(bad).any(axis=1))
+    return f"{int(np.asarray(bad).sum())} outputs differ, first rows (row, workgroup row, u) {[(int(y), int(y) // rpb, int(y) % rpb) for y in rows[:12]]}"
+
+
+@pytest.mark.parametrize("key", keep_cases.KEYS)
+def test_keep_mask_with_several_rows_per_block(gpu_ctx, key):
+    """gradients.keep_mask at five or six output rows per workgroup (three in the last), one entry of tests/strip_shapes.py per
+    instantiation of k_grad_keep, with and without and_with, numpy in -> numpy out and tensor in -> tensor out: bit-equal to
+    masked_ref.keep_blocks.  The inputs are tests/keep_cases.py's: in every row of the second workgroup row and of the last one
+    single elements decide blocks, at every row, lane and byte of a block in turn (NaN, -inf, one ulp below the threshold, the
+    threshold itself; a lone 0x00 among 0x01, 0x80, 0xFF), and and_with holds lone zeros there.  Before each tensor call the
+    allocator's free block of the output's size is filled with 7, so an output row that is never stored shows.  keep_f64_b2 runs
+    once more as a device view whose base is 8 bytes off a 16-byte boundary, the other way into <double, 8, 0>."""
+    import masked_ref as mr
+    from xsarsea_amd import gradients
+    torch, dev = _torch()
+    e = strip_shapes.SHAPES[key]
+    c = keep_cases.case(key)
+    gx, gy, rpb, last = e.grid
+    Lo, So = e.lines // c.block, e.samples // c.block
+    assert rpb > 4 and Lo == (gy - 1) * rpb + last
+    probes = strip_shapes.probe_lines(key)
+    print(f"{key}: k_grad_keep<{e.inst[0]}, {e.inst[1]}, {e.inst[2]}> on {Lo} x {So} outputs, (gx, gy, rpb, last) = {e.grid}; probe rows "
+          f"{probes[0]}..{probes[rpb - 1]} (workgroup row 1, u = 0..{rpb - 1}) and {probes[rpb]}..{probes[-1]} (workgroup row {gy - 1}); "
+          f"{len(c.bad)} blocks decided by one element, {len(c.holes)} lone zeros of and_with")
+    wants = {False: mr.keep_blocks(c.src, c.block, c.threshold), True: mr.keep_blocks(c.src, c.block, c.threshold, and_with=c.and_with)}
+    for with_aw in (False, True):
+        got = gradients.keep_mask(c.src, threshold=c.threshold, block=c.block, and_with=c.and_with if with_aw else None)
+        assert isinstance(got, np.ndarray) and got.dtype == np.uint8 and got.shape == (Lo, So)
+        bad = got != wants[with_aw]
+        print(f"{key} numpy route, and_with {with_aw}: {int(bad.sum())} outputs differ, {int(bad[probes].sum())} of them in the probe rows")
+        assert not bad.any(), f"{key} numpy route, and_with {with_aw}: " + _rows_of(bad, key)
+    t_src, t_aw = _up(c.src.copy(), c.and_with.copy())   # (the case's own arrays are read-only)
+    for with_aw in (False, True):
+        poison = torch.full((Lo, So), 7, dtype=torch.uint8, device=dev)
+        del poison
+        out = gradients.keep_mask(t_src, threshold=c.threshold, block=c.block, and_with=t_aw if with_aw else None)
+        assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (Lo, So)
+        got = out.cpu().numpy()
+        del out
+        bad = got != wants[with_aw]
+        print(f"{key} tensor route, and_with {with_aw}: {int(bad.sum())} outputs differ, {int(bad[probes].sum())} of them in the probe rows")
+        assert not bad.any(), f"{key} tensor route, and_with {with_aw}: " + _rows_of(bad, key)
+    if key == "keep_f64_b2":
+        # the same raster as a view that starts 8 bytes off a 16-byte boundary: grad_keep falls back to <double, 8, 0>, here with
+        # 2 x 2 blocks and two column strips
+        room = torch.empty(t_src.numel() + 1, dtype=t_src.dtype, device=dev)
+        view = room[1:].view(t_src.shape)
+        view.copy_(t_src)
+        assert view.data_ptr() % 16 == 8 and view.is_contiguous()
+        got = gradients.keep_mask(view, threshold=c.threshold, block=c.block, and_with=t_aw).cpu().numpy()
+        bad = got != wants[True]
+        print(f"{key} tensor route, base 8 bytes off, and_with True: {int(bad.sum())} outputs differ")
+        assert not bad.any(), f"{key} tensor route, base 8 bytes off: " + _rows_of(bad, key)
+        del room, view
+    del t_src, t_aw
+    torch.cuda.empty_cache()
+
+
+# ------------------------------------------------------------------------------------------------------------- k_expand
+EXPAND_ROUTES = ["co", "co+cross", "cross, no co output", "cross alone"]  # which of (code_co, code_cr, out_co, out_cr) a call is given
+EXPAND_SENTINEL = complex(-7.0, -7.0)
+
+
+def _expand_tables(request, which):
+    """(co, cr) table dicts: the low-resolution pair (directions 0..180), or the small golden whose directions run 0..360."""
+    from conftest import golden
+    from util import lut_dicts, small_luts
+    if which == "lowres":
+        return lut_dicts(*request.getfixturevalue("lowres_luts"))
+    return lut_dicts(*small_luts(golden("kernel_small_phi360_f64.npz")))
+
+
+def _expand_codes(plane, n_wcr):
+    """N_STRIDE co-pol and cross-pol codes made by hand, no inversion: uniformly random grid points of the table with the -phi
+    bit on half of them, uniformly random cross-pol indices with XSW_CODE_PICK_CO on a quarter; then, at the start of each of
+    the three passes, every special kind beside ordinary partners and beside each other (the co-pol wind a cross-pol code picks
+    or scales may itself be NaN, (nan, 0) or foreign)."""
+    from xsarsea_amd import _lib
+    rng = np.random.default_rng(54)
+    cc = rng.integers(0, plane, N_STRIDE).astype(np.uint32) | (rng.integers(0, 2, N_STRIDE).astype(np.uint32) << 30)
+    ccr = rng.integers(0, n_wcr, N_STRIDE).astype(np.uint32) | np.where(rng.random(N_STRIDE) < 0.25, _lib.CODE_PICK_CO, 0).astype(np.uint32)
+    sp_co = np.array([_lib.CODE_NAN, _lib.CODE_NAN_RE, plane, 0x3FFFFFFF, 0x40000000 | plane, 0x80000000, plane - 1, 0x40000000 | (plane - 1)], np.uint32)
+    sp_cr = np.array([_lib.CODE_NAN_RE, _lib.CODE_NO_INDEX, n_wcr, _lib.CODE_PICK_CO | 5, _lib.CODE_PICK_CO | _lib.CODE_NO_INDEX, 0x80000001, _lib.CODE_NAN,
+                      n_wcr - 1], np.uint32)
+    starts = (100, ONE_PASS + 3, 2 * ONE_PASS + 1)
+    for at in starts:
+        cc[at:at + 8] = sp_co                       # each special co-pol code with a random cross-pol partner
+        ccr[at + 8:at + 16] = sp_cr                 # each special cross-pol code with a random co-pol partner
+        cc[at + 16:at + 24], ccr[at + 16:at + 24] = sp_co, sp_cr
+        cc[at + 24:at + 32], ccr[at + 24:at + 32] = sp_co, np.roll(sp_cr, 3)
+    assert starts[2] + 32 <= N_STRIDE
+    return cc, ccr, starts
+
+
+def _cbits(a):
+    """The bits of a complex vector, one row per element."""
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64).reshape(a.size, -1)
+
+
+@pytest.mark.parametrize("out_c", [np.complex64, np.complex128])
+@pytest.mark.parametrize("tables", ["lowres", "phi360"])
+def test_expand_codes_beyond_one_pass_per_thread(gpu_ctx, request, tables, out_c):
+    """k_expand is capped at 256 * 16 workgroups of 256 threads: N_STRIDE codes send every thread through its grid-stride loop
+    twice and the first 257 a third time.  On the bits: the device expansion of the whole array == the device expansion of the
+    same codes in slices of at most one pass == the host expansion (which test_gpu_codes.py pins to the stored winds), for
+    co-pol codes alone, co + cross, cross without a co-pol output and cross-pol codes alone, and co + cross once more through
+    xsw_expand_codes_on_stream on a side stream.  Outputs start as a sentinel."""
+    from test_host_plan import grid_cap
+    from xsarsea_amd import _lib
+    torch, dev = _torch()
+    assert ONE_PASS == grid_cap("expand_codes_on", "expand") * 256 and N_STRIDE > 2 * ONE_PASS
+    co, cr = _expand_tables(request, tables)
+    gpu_ctx.upload_luts(co=co, cr=cr)
+    plane, n_wcr = len(co["wspd"]) * len(co["phi"]), len(cr["wspd"])
+    assert (co["phi"][-1] > 180.0) == (tables == "phi360") and n_wcr > 5
+    cc, ccr, starts = _expand_codes(plane, n_wcr)
+    t_cc, t_ccr = _up(cc.view(np.int32), ccr.view(np.int32))
+    od = _lib.XSW_F32 if out_c == np.complex64 else _lib.XSW_F64
+    cdt = torch.complex64 if out_c == np.complex64 else torch.complex128
+    item = np.dtype(out_c).itemsize
+    fresh = lambda: torch.full((N_STRIDE,), EXPAND_SENTINEL, dtype=cdt, device=dev)
+    at = lambda t, a, size: None if t is None else t.data_ptr() + a * size
+    hp = lambda a: None if a is None else a.ctypes.data
+    side = torch.cuda.Stream(device=dev)
+    for route in EXPAND_ROUTES + ["co+cross on a side stream"]:
+        has_cc, has_cr = route != "cross alone", route != "co"
+        want_co = route in ("co", "co+cross", "co+cross on a side stream")
+        d_cc, d_cr = (t_cc if has_cc else None), (t_ccr if has_cr else None)
+        whole = [fresh() if want_co else None, fresh() if has_cr else None]
+        sliced = [fresh() if want_co else None, fresh() if has_cr else None]
+        torch.cuda.synchronize()
+        if route.endswith("side stream"):
+            gpu_ctx.expand_codes_on_stream(side.cuda_stream, N_STRIDE, od, at(d_cc, 0, 4), at(d_cr, 0, 4), at(whole[0], 0, item), at(whole[1], 0, item))
+            side.synchronize()
+        else:
+            gpu_ctx.expand_codes_raw(N_STRIDE, _lib.MEM_DEVICE, od, at(d_cc, 0, 4), at(d_cr, 0, 4), at(whole[0], 0, item), at(whole[1], 0, item))
+        lengths = []
+        for a in range(0, N_STRIDE, ONE_PASS):
+            lengths.append(min(ONE_PASS, N_STRIDE - a))
+            gpu_ctx.expand_codes_raw(lengths[-1], _lib.MEM_DEVICE, od, at(d_cc, a, 4), at(d_cr, a, 4), at(sliced[0], a, item), at(sliced[1], a, item))
+        gpu_ctx.synchronize()
+        assert lengths == [ONE_PASS, ONE_PASS, 257]
+        host = [np.full(N_STRIDE, EXPAND_SENTINEL, out_c) if want_co else None, np.full(N_STRIDE, EXPAND_SENTINEL, out_c) if has_cr else None]
+        gpu_ctx.expand_codes_raw(N_STRIDE, _lib.MEM_HOST, od, hp(cc if has_cc else None), hp(ccr if has_cr else None), hp(host[0]), hp(host[1]))
+        for name, w, s, h in zip(("co", "cr"), whole, sliced, host):
+            if w is None:
+                continue
+            w, s = w.cpu().numpy(), s.cpu().numpy()
+            what = f"{tables} {np.dtype(out_c).name} {route}, {name}"
+            for other, x in (("one-pass slices", s), ("the host expansion", h)):
+                differ = np.flatnonzero((_cbits(w) != _cbits(x)).any(axis=1))
+                print(f"{what}: {differ.size} of {N_STRIDE} elements differ from {other}")
+                assert differ.size == 0, f"{what} against {other}: first {differ[:8].tolist()} (pass {(differ[:8] // ONE_PASS).tolist()})"
+            assert not (h == EXPAND_SENTINEL).any(), what + ": an element was never written"
+            for k, a in enumerate(starts):     # every pass holds winds, (nan, nan) and (nan, 0)
+                seg = h[a:a + 4096]
+                assert np.isfinite(seg.real).any() and (np.isnan(seg.real) & np.isnan(seg.imag)).any() and (np.isnan(seg.real) & (seg.imag == 0)).any(), (what, k)
+        if route == "co+cross":
+            picked = (ccr & _lib.CODE_PICK_CO) != 0
+            assert picked[2 * ONE_PASS:].any() and (~picked[2 * ONE_PASS:]).any() and ((cc >> 30) == 1)[ONE_PASS:].any()
+        del whole, sliced
+    del t_cc, t_ccr
+    torch.cuda.empty_cache()
+
+
+# ---------------------------------------------------------------------------------------------------------- k_grad_area
+AREA_ONE_PASS = 65536 * 256  # outputs k_grad_area covers with one pass per thread
+
+
+def _area_scene(shape, factor, dtype, out_probes):
+    """A small random block tiled over `shape` (cheap to build), then made unlike itself where it counts: the f x f inputs of
+    every output of `out_probes` (flat output indices) get values found nowhere else, 1000 and up, and one input of the outputs
+    next to the first, the middle and the last probe is NaN.  Returns (scene, flat indices of the outputs that are NaN)."""
+    rng = np.random.default_rng(55)
+    L, S = shape
+    So = S // factor
+    tile = rng.uniform(0.01, 1.0, (61, 67)).astype(dtype)
+    s0 = np.tile(tile, (L // 61 + 1, S // 67 + 1))[:L, :S].copy()
+    for k, o in enumerate(out_probes):
+        Y, X = divmod(o, So)
+        s0[Y * factor:(Y + 1) * factor, X * factor:(X + 1) * factor] = 1000.0 + 8.0 * k + np.arange(factor * factor).reshape(factor, factor)
+    nan_at = [out_probes[0] + 5, out_probes[len(out_probes) // 2] + 5, out_probes[-1] - 5]
+    for o in nan_at:
+        Y, X = divmod(o, So)
+        s0[Y * factor + factor - 1, X * factor] = np.nan
+    return s0, nan_at
+
+
+@pytest.mark.parametrize("factor", [2, 1])
+def test_area_beyond_one_pass_per_thread(gpu_ctx, factor):
+    """k_grad_area is capped at 65 536 workgroups of 256 threads.  factor 2: 8195 x 8201 float32 -> 4097 x 4100 = 16 797 700
+    outputs, a remainder trimmed on both axes, 20 484 of them in the second pass.  factor 1 (the raw entry accepts it): 3 x
+    5 592 491 = 65536 * 256 + 257 elements, the pure index walk.  array_equal with gradients_ref.area (the same float64 order,
+    the same rounding), as test_gpu_gradients.py::test_area.  The scene is a tiled block, so the outputs around the end of the
+    first pass, the last output and some inside the second pass hold values found nowhere else: no earlier stretch of the
+    output equals the second pass, which a wrong stride would store.  One NaN before, one inside and one at the end of it."""
+    import gradients_ref as ref
+    from test_host_plan import grid_cap
+    from xsarsea_amd import gradients
+    assert AREA_ONE_PASS == grid_cap("xsw_grad_area", "grad_area") * 256
+    shape = (8195, 8201) if factor == 2 else (3, 5592491)
+    Lo, So = shape[0] // factor, shape[1] // factor
+    n = Lo * So
+    assert n == (16797700 if factor == 2 else AREA_ONE_PASS + 257) and n > AREA_ONE_PASS
+    assert factor == 1 or (shape[0] % factor and shape[1] % factor)
+    probes = [AREA_ONE_PASS - 4100, AREA_ONE_PASS - 1, AREA_ONE_PASS, AREA_ONE_PASS + 1] + [AREA_ONE_PASS + 17 + 37 * k for k in range(5)] + [n - 1]
+    s0, nan_at = _area_scene(shape, factor, np.float32, probes)
+    want = ref.area(s0, factor)
+    flat = want.reshape(-1)
+    assert want.shape == (Lo, So) and want.dtype == np.float32
+    assert np.isnan(flat[nan_at]).all() and np.isnan(flat).sum() == 3 and nan_at[0] < AREA_ONE_PASS <= nan_at[1] < nan_at[2]
+    for o in probes:  # found nowhere else: the second pass equals no earlier stretch of the output
+        assert flat[o] >= 1000.0 and (flat == flat[o]).sum() == 1, o
+    assert sum(o >= AREA_ONE_PASS for o in probes) >= 7
+    out = gradients._area(s0, factor)
+    assert out.dtype == np.float32 and out.shape == (Lo, So)
+    differ = np.flatnonzero(~((out.reshape(-1) == flat) | (np.isnan(out.reshape(-1)) & np.isnan(flat))))
+    print(f"k_grad_area factor {factor}: {n} outputs, {n - AREA_ONE_PASS} in the second pass; {differ.size} differ from gradients_ref.area, "
+          f"{int((differ >= AREA_ONE_PASS).sum())} of them in the second pass")
+    assert differ.size == 0, f"first {differ[:8].tolist()}"
+    np.testing.assert_array_equal(out, want)

@@ -312,27 +312,91 @@ def source_define(name):
     return int(found[0])
 
 
+def grid_cap(fn, kernel):
+    """The largest grid, in workgroups of 256 threads, that `fn` of csrc launches the grid-stride `kernel` with: the second
+    argument of the std::min<long long>((n + 255) / 256, CAP) in that function, a product of integers.  The GPU tests that run
+    such a kernel beyond one pass per thread size themselves by it and fail when the launch no longer reads so."""
+    import re
+    hits = []
+    for name in sorted(os.listdir(CSRC)):
+        with open(os.path.join(CSRC, name)) as f:
+            text = f.read()
+        for m in re.finditer(r"\b" + fn + r"\([^;{]*\)\s*\{", text):
+            body = text[m.end():]
+            body = body[:body.index("\n}\n")]
+            if "k_" + kernel in body:
+                hits += re.findall(r"std::min<long long>\(\([^;]*?\+ 255\) / 256, ([0-9* ]+)\)", body)
+    assert len(hits) == 1, (fn, kernel, hits)
+    cap = 1
+    for v in hits[0].split("*"):
+        cap *= int(v)
+    return cap
+
+
+def test_grid_stride_caps():
+    assert grid_cap("expand_codes_on", "expand") == 256 * 16 and grid_cap("xsw_grad_area", "grad_area") == 65536
+
+
+def keep_instantiation(dtype, block, samples, base=0):
+    """(T, W, B) of the k_grad_keep<T, W, B> that grad_keep launches (xsw_gradients.hip, the loop over w and XSW_KEEP_LAUNCH):
+    the widest W among 16, 8, 4 above the element size that divides the block's row bytes and the raster's row bytes and to
+    which the base address is aligned, else the element size; B = 2 only for float64 at W = 16 and 2 x 2 blocks."""
+    es = {"float64": 8, "uint8": 1}[dtype]
+    W = next((w for w in (16, 8, 4) if w > es and (block * es) % w == 0 and (samples * es) % w == 0 and base % w == 0), es)
+    return {"float64": "double", "uint8": "uint8_t"}[dtype], W, 2 if es == 8 and W == 16 and block == 2 else 0
+
+
+KEEP_INSTANTIATIONS = {("double", 16, 2), ("double", 16, 0), ("double", 8, 0), ("uint8_t", 16, 0), ("uint8_t", 8, 0), ("uint8_t", 4, 0),
+                       ("uint8_t", 1, 0)}  # XSW_KEEP_LAUNCH's seven
+
+
 def test_strip_shapes_stay_multi_line(ask):
     """Every raster of tests/strip_shapes.py, through the compiled strip_grid with its kernel's column divisor and workgroups per
     CU: at least two column strips, more than four lines per workgroup and no whole number of four-line groups, a shorter last
     workgroup that is no whole number of groups either -- and the grid the GPU tests place their special values by.  A change of
     strip_grid, XSW_DETREND_WG_PER_CU or XSW_NESZ_EV that sends these rasters back to one line per workgroup fails here, on the
-    CPU, instead of silently emptying the GPU tests."""
+    CPU, instead of silently emptying the GPU tests.
+    The keep entries (k_grad_keep: strip_grid on the OUTPUT grid, one column per thread) hold to the same rules, but that with
+    blocks wider than 2 x 2 they take ONE column strip, which must end in a partial wave; each selects, by grad_keep's width
+    rule restated above, the instantiation it claims, all seven are claimed, and one entry at least trims a remainder row and
+    a remainder column."""
     import strip_shapes
     assert NESZ_EV == source_define("XSW_NESZ_EV")
-    wg_per_cu = {"detrend": source_define("XSW_DETREND_WG_PER_CU"), "dsig_flat": 0, "streaks": 0}  # 0: strip_grid's default
-    col_div = {"detrend": 4, "dsig_flat": NESZ_EV, "streaks": 1}
-    assert len(strip_shapes.SHAPES) == 5 and {e.kernel for e in strip_shapes.SHAPES.values()} == set(col_div)
+    wg_per_cu = {"detrend": source_define("XSW_DETREND_WG_PER_CU"), "dsig_flat": 0, "streaks": 0, "keep": 0}  # 0: strip_grid's default
+    col_div = {"detrend": 4, "dsig_flat": NESZ_EV, "streaks": 1, "keep": 1}
+    assert len(strip_shapes.SHAPES) == 12 and {e.kernel for e in strip_shapes.SHAPES.values()} == set(col_div)
     for key, e in sorted(strip_shapes.SHAPES.items()):
         assert e.col_div == col_div[e.kernel], key
-        ((gx, gy, rpb),) = ask(("grid", e.lines, ceil_div(e.samples, e.col_div), wg_per_cu[e.kernel]))
-        last = e.lines - (gy - 1) * rpb
+        assert e.reduce >= 1 and (e.reduce == 1 or e.kernel == "keep"), key
+        rows, cols = e.lines // e.reduce, e.samples // e.reduce
+        assert rows == strip_shapes.grid_rows(key), key
+        ((gx, gy, rpb),) = ask(("grid", rows, ceil_div(cols, e.col_div), wg_per_cu[e.kernel]))
+        last = rows - (gy - 1) * rpb
         print(key, (e.lines, e.samples), "->", (gx, gy, rpb, last))
-        assert gx >= 2, key
+        if e.kernel == "keep" and e.reduce > 2:
+            assert gx == 1 and cols % 64 != 0, key
+        else:
+            assert gx >= 2, key
         assert rpb >= 5 and rpb % 4 != 0, key
         assert 0 < last < rpb and last % 4 != 0, key
         assert (gx, gy, rpb, last) == e.grid, key
-        assert strip_shapes.block_lines(key, -1) == list(range(e.lines - last, e.lines)), key
+        assert strip_shapes.block_lines(key, -1) == list(range(rows - last, rows)), key
+        assert strip_shapes.block_lines(key, 1) == list(range(rpb, 2 * rpb)), key
+        if e.kernel == "keep":
+            inst = keep_instantiation(e.dtype, e.reduce, e.samples)  # a whole allocation: the base is aligned to 16 bytes and more
+            print(key, "-> k_grad_keep<%s, %d, %d>" % inst)
+            assert inst == e.inst, key
+            assert e.lines * e.samples * {"float64": 8, "uint8": 1}[e.dtype] < 70e6, key
+        else:
+            assert e.dtype is None and e.inst is None, key
+    keep = [e for e in strip_shapes.SHAPES.values() if e.kernel == "keep"]
+    assert len(keep) == 7 and {e.inst for e in keep} == KEEP_INSTANTIATIONS
+    assert any(e.lines % e.reduce and e.samples % e.reduce for e in keep)
+    assert any(e.reduce <= 2 for e in keep) and any(e.reduce > 2 for e in keep)
+    # the width rule at what the entries do not vary: a base 8 bytes off a 16-byte boundary, rows of 8 and 4 bytes, bytes alone
+    assert keep_instantiation("float64", 2, 516, base=8) == ("double", 8, 0) and keep_instantiation("float64", 1, 516) == ("double", 8, 0)
+    assert keep_instantiation("uint8", 16, 144, base=8) == ("uint8_t", 8, 0) and keep_instantiation("uint8", 16, 152) == ("uint8_t", 8, 0)
+    assert keep_instantiation("uint8", 16, 148) == ("uint8_t", 4, 0) and keep_instantiation("uint8", 1, 144) == ("uint8_t", 1, 0)
     assert strip_shapes.SHAPES["streaks"].grid[2] > 8  # the streaks pass: a second unrolled group in every workgroup
     # the vector and the element-wise raster of a kernel differ in the sample count's divisibility alone
     for a, b, q in (("detrend_vec", "detrend_elem", 4), ("dsig_flat_vec", "dsig_flat_elem", 2)):

@@ -6,7 +6,9 @@ import pytest
 
 import filtering_ref as fr
 import gradients_ref as ref
+import keep_cases
 import masked_ref as mr
+import strip_shapes
 from xsarsea_amd import gradients
 
 BINS = ref.angles_bins(72)
@@ -148,3 +150,50 @@ def test_chain_scene_separates_the_blob_windows():
     for i, j in blobs:
         assert below[i, j] and R0[i, j] == 1.0
     assert (R0[above] > r + gap / 2).all()
+
+
+@pytest.mark.parametrize("key", keep_cases.KEYS)
+def test_keep_cases_tell_a_one_row_kernel_from_a_right_one(key):
+    """The premise of tests/test_gpu_strips.py's keep-mask tests, on the restatement alone, with and without and_with.  The
+    probe blocks are what tests/keep_cases.py says: one element makes a block unusable, at every row and every column of the
+    block in turn, and the blocks left usable are kept.  The expected mask, restricted to the output rows that are NOT the
+    first of their workgroup, holds both values and differs from the mask that repeats each workgroup's first row -- also on
+    every probe row by itself -- so a kernel that stopped after one row, or read row y0 again, cannot pass."""
+    c = keep_cases.case(key)
+    e = strip_shapes.SHAPES[key]
+    b, (gx, gy, rpb, last) = c.block, e.grid
+    Lo, So = e.lines // b, e.samples // b
+    assert c.src.shape == (e.lines, e.samples) and str(c.src.dtype) == e.dtype and c.and_with.shape == (Lo, So)
+    assert c.src.nbytes < 70e6
+    assert (Lo * b < e.lines or So * b < e.samples) and Lo == (gy - 1) * rpb + last
+    later = np.arange(Lo) % rpb != 0
+    probes = strip_shapes.probe_lines(key)
+    assert probes == list(range(rpb, 2 * rpb)) + list(range(Lo - last, Lo)) and len(c.holes) == len(probes)
+    plain, anded = mr.keep_blocks(c.src, b, c.threshold), mr.keep_blocks(c.src, b, c.threshold, and_with=c.and_with)
+    for Y, X in c.bad:
+        assert plain[Y, X] == 0
+        blk = np.array(c.src[Y * b:(Y + 1) * b, X * b:(X + 1) * b])
+        with np.errstate(invalid="ignore"):
+            unusable = ~(blk >= c.threshold) if c.threshold is not None else blk == 0
+        assert unusable.sum() == 1                                       # a single element decides the block
+    assert all(plain[Y, X] == 1 for Y, X in c.good)
+    assert sorted(c.bad + c.good) == [(Y, X) for Y in sorted(probes) for X in range(So)]
+    n = len(c.at)
+    assert n >= b and {i for i, _ in c.at} == set(range(b)) and {j for _, j in c.at} == set(range(b))
+    assert len(set(c.at)) == min(n, b * b)                               # every (i, j) of the block while n < b * b
+    if c.threshold is not None:
+        kinds = [c.src[Y * b + i, X * b + j] for (Y, X), (i, j) in zip(c.bad, c.at)]
+        assert any(np.isnan(v) for v in kinds) and -np.inf in kinds and keep_cases.BELOW in kinds
+        assert (c.src == c.threshold).any() and (c.src == np.inf).any()
+    else:
+        assert {int(v) for Y, X in c.good for v in np.unique(c.src[Y * b:(Y + 1) * b, X * b:(X + 1) * b])} == {0x01, 0x80, 0xFF}
+    for Y, X in c.holes:                                                  # and_with's lone zero takes a usable block out
+        assert plain[Y, X] == 1 and anded[Y, X] == 0 and (c.and_with[Y] == 0).sum() == 1
+    assert {Y % rpb for Y, _ in c.holes} >= set(range(min(rpb, 5)))       # u = 0..3 of an unrolled group and a tail row
+    for want in (plain, anded):
+        assert want[later].min() == 0 and want[later].max() == 1
+        stuck = keep_cases.repeat_first_rows(want, key)
+        assert (want != stuck)[later].any()
+        assert all((want[Y] != stuck[Y]).any() for Y in probes if Y % rpb)
+        print(key, (gx, gy, rpb, last), f"kept share {want.mean():.3f}, rows that differ from their workgroup's first row "
+              f"{int((want != stuck).any(axis=1).sum())} of {int(later.sum())}")
