@@ -49,7 +49,7 @@ EXPORTS = (
     "xsw_host_alloc", "xsw_host_free", "xsw_set_host_threads", "xsw_grad_area", "xsw_grad_r2", "xsw_grad_local", "xsw_grad_hist",
     "xsw_grad_r2_sqrt", "xsw_grad_local_sqrt", "xsw_grad_smooth", "xsw_grad_mean", "xsw_grad_filter",
     "xsw_grad_hist_masked", "xsw_grad_keep_f64", "xsw_grad_keep_u8",
-    "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary",
+    "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary", "xsw_ancillary_model",
     "xsw_cross_from_codes", "xsw_cost_from_codes", "xsw_cost_cr_from_codes",
     "xsw_uncertainty_from_codes", "xsw_uncertainty_cr_from_codes", "xsw_joint_from_codes",
     "xsw_uncertainty_joint_from_codes",
@@ -59,7 +59,7 @@ EXPORTS = (
 )
 
 
-# The raster entries behind xsarsea_amd.gradients and xsarsea_amd.streaks: their C signature after the context, one letter per
+# The raster entries behind xsarsea_amd.gradients, xsarsea_amd.streaks and xsarsea_amd.ancillary: their C signature after the context, one letter per
 # argument (l int64, i int32, d double, p pointer: an int address, device or host per `mem`, or None).  `load` sets the argtypes
 # from it and every row becomes a Context method, e.g. `grad_area_raw(lines, samples, factor, dtype, mem, in_ptr, out_ptr)`.
 RASTER_ENTRIES = {
@@ -99,8 +99,12 @@ RASTER_ENTRIES = {
     # (lines, samples, mem, anc, n_rows, n_cols, dirs, line_first, line_t, sample_first, sample_t, out): the complex128 a-priori
     # raster from the resolved window directions
     "xsw_streaks_ancillary": "llipiipppppp",
+    # (lines, samples, mem, dtype, u, v, n_lat, n_lon, lon0, dlon, periodic, lat0, dlat, n_tie_lines, n_tie_samples, tie_lon, tie_lat,
+    # tie_cos, tie_sin, line_first, line_t, sample_first, sample_t, out): the complex128 a-priori raster from the model wind on its
+    # uniform grid and the scene's tie points
+    "xsw_ancillary_model": "lliippiiddiddiippppppppp",
 }
-assert list(RASTER_ENTRIES) == [n for n in EXPORTS if n.startswith(("xsw_grad_", "xsw_streaks_"))]
+assert list(RASTER_ENTRIES) == [n for n in EXPORTS if n.startswith(("xsw_grad_", "xsw_streaks_", "xsw_ancillary_"))]
 # letter -> (ctypes type, conversion the wrapper applies: ctypes alone refuses numpy scalars)
 _SIG = {"l": (ctypes.c_int64, int), "i": (ctypes.c_int32, int), "d": (ctypes.c_double, float), "p": (ctypes.c_void_p, lambda a: a)}
 
