@@ -839,6 +839,57 @@ int xsw_ancillary_model(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t me
                         int32_t n_tie_samples, const double *tie_lon, const double *tie_lat, const double *tie_cos, const double *tie_sin,
                         const int32_t *line_first, const double *line_t, const int32_t *sample_first, const double *sample_t, double *out);
 
+/* ---- wind product cells: block statistics of a raster on a product grid (xsarsea_amd.cells), the way out of device memory:
+ * kilobytes instead of the raster.  Additive to XSW_VERSION 4; conventions as above.
+ *
+ * The lines x samples raster is tiled from pixel (0, 0) by cells of cell_lines x cell_samples pixels: nLc = ceil(lines /
+ * cell_lines) by nSc = ceil(samples / cell_samples) cells, the last cell of an axis clipped to the raster.  Every output is
+ * [nLc][nSc].  A cell's pixels are numbered p = r * w + c, r the row and c the column inside the cell, w the cell's actual
+ * (clipped) width.
+ *
+ * Validity.  A pixel is valid iff its keep byte is non-zero (keep NULL: all are) and
+ *   XSW_CELLS_C128 / XSW_CELLS_C64 (interleaved (re, im) float64 / float32 pairs): neither part is NaN;
+ *   XSW_CELLS_CODES (co-pol grid codes, out_code_co above): the code names a grid point of the context's CURRENT co-pol LUT
+ *     (bit 31 clear and the flat index below n_wspd * n_phi); its (re, im) is the `sol` entry xsw_expand_codes reads, so codes
+ *     give bit for bit what the expanded complex128 raster gives;
+ *   a real raster: the value is not NaN.
+ * Invalid pixels contribute nothing to any sum.
+ *
+ * Order of every sum.  All arithmetic is float64 (float32 inputs are widened first), every operation rounded once:
+ *   pixel p goes to accumulator p mod 256; each of the 256 accumulators starts at +0.0 and adds its pixels in ascending p;
+ *   then a[i] += a[i + h] for i < h, for h = 128, 64, 32, 16, 8, 4, 2, 1; a[0] is the sum.
+ * The order does not depend on how the launch maps lanes to pixels (one wave or one workgroup per cell: csrc/xsw_cells.hip),
+ * no atomic is used, and tests/cells_ref.py restates it in numpy bit for bit.  It lies within (N - 1) * 2**-53 * sum|x| of the
+ * exact sum.
+ *
+ * Sums per cell.  Wind: per valid pixel q = re * re + im * im, s = sqrt(q); n, Sre, Sim, Ss, Sq.  Real: n, Sx, Sxx (x * x).
+ * Per cell from the sums, n used as a double:
+ *   count      = n (int32)
+ *   wind       = Sre / n + 1j * Sim / n                      the vector mean, antenna convention (interleaved pair)
+ *   wspd       = Ss / n                                      the scalar mean
+ *   wspd_std   = NaN for n < 2, else sqrt(var < 0 ? 0 : var) with var = (Sq - (Ss * Ss) / n) / (n - 1)
+ *   steadiness = sqrt(mre * mre + mim * mim) / wspd          (mre, mim the parts of wind; NaN where wspd is 0)
+ *   mean = Sx / n, std from Sxx, Sx, n by the expression of wspd_std
+ * n = 0 gives NaN everywhere (0 / 0) with count 0; there is no minimum count: the caller masks on count.
+ *
+ * With tie points (tie_lon != NULL; tie grids, tie_cos / tie_sin and the brackets as for xsw_ancillary_model, the brackets being
+ * those of the cells' CENTRE coordinates: line_first / line_t [nLc], sample_first / sample_t [nSc]): lon, lat, ch, sh at the centre
+ * by exactly the first two steps of xsw_ancillary_model (the same device code), then
+ *   u = -(mre * ch + mim * sh),  v = -(mim * ch - mre * sh)
+ * the east / north components ("blowing to", the inverse of xsw_ancillary_model's last step), and longitude / latitude of the
+ * centre (the tie points' continuous longitude, not wrapped).  tie_lon == NULL: no geolocation; the four geographic outputs must
+ * then be NULL.  Every output pointer may be NULL: it is not computed and never written. */
+enum { XSW_CELLS_C128 = 0, XSW_CELLS_C64 = 1, XSW_CELLS_CODES = 2 };
+int xsw_wind_cells(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, int32_t src_kind, const void *src, const uint8_t *keep,
+                   int32_t cell_lines, int32_t cell_samples, int32_t n_tie_lines, int32_t n_tie_samples, const double *tie_lon,
+                   const double *tie_lat, const double *tie_cos, const double *tie_sin, const int32_t *line_first, const double *line_t,
+                   const int32_t *sample_first, const double *sample_t, int32_t *out_count, double *out_wind, double *out_wspd,
+                   double *out_wspd_std, double *out_steadiness, double *out_longitude, double *out_latitude, double *out_u, double *out_v);
+
+/* The same for a real raster x (dtype XSW_F32 or XSW_F64): count, mean and std per cell. */
+int xsw_raster_cells(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, int32_t dtype, const void *x, const uint8_t *keep,
+                     int32_t cell_lines, int32_t cell_samples, int32_t *out_count, double *out_mean, double *out_std);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,7 @@ EXPORTS = (
     "xsw_grad_r2_sqrt", "xsw_grad_local_sqrt", "xsw_grad_smooth", "xsw_grad_mean", "xsw_grad_filter",
     "xsw_grad_hist_masked", "xsw_grad_keep_f64", "xsw_grad_keep_u8",
     "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary", "xsw_ancillary_model",
+    "xsw_wind_cells", "xsw_raster_cells",
     "xsw_cross_from_codes", "xsw_cost_from_codes", "xsw_cost_cr_from_codes",
     "xsw_uncertainty_from_codes", "xsw_uncertainty_cr_from_codes", "xsw_joint_from_codes",
     "xsw_uncertainty_joint_from_codes",
@@ -59,7 +60,7 @@ EXPORTS = (
 )
 
 
-# The raster entries behind xsarsea_amd.gradients, xsarsea_amd.streaks and xsarsea_amd.ancillary: their C signature after the context, one letter per
+# The raster entries behind xsarsea_amd.gradients, xsarsea_amd.streaks, xsarsea_amd.ancillary and xsarsea_amd.cells: their C signature after the context, one letter per
 # argument (l int64, i int32, d double, p pointer: an int address, device or host per `mem`, or None).  `load` sets the argtypes
 # from it and every row becomes a Context method, e.g. `grad_area_raw(lines, samples, factor, dtype, mem, in_ptr, out_ptr)`.
 RASTER_ENTRIES = {
@@ -103,8 +104,15 @@ RASTER_ENTRIES = {
     # tie_cos, tie_sin, line_first, line_t, sample_first, sample_t, out): the complex128 a-priori raster from the model wind on its
     # uniform grid and the scene's tie points
     "xsw_ancillary_model": "lliippiiddiddiippppppppp",
+    # (lines, samples, mem, src_kind, src, keep, cell_lines, cell_samples, n_tie_lines, n_tie_samples, tie_lon, tie_lat, tie_cos, tie_sin,
+    # line_first, line_t, sample_first, sample_t, count, wind, wspd, wspd_std, steadiness, longitude, latitude, u, v): per cell of the
+    # product grid, from a complex wind raster or co-pol codes (CELLS_*); keep, the tie points and every output may be None
+    "xsw_wind_cells": "lliippiiiipppppppp" + "p" * 9,
+    # (lines, samples, mem, dtype, x, keep, cell_lines, cell_samples, count, mean, std): the same for a float32 / float64 raster
+    "xsw_raster_cells": "lliippiippp",
 }
-assert list(RASTER_ENTRIES) == [n for n in EXPORTS if n.startswith(("xsw_grad_", "xsw_streaks_", "xsw_ancillary_"))]
+assert list(RASTER_ENTRIES) == [n for n in EXPORTS if n.startswith(("xsw_grad_", "xsw_streaks_", "xsw_ancillary_")) or n.endswith("_cells")]
+CELLS_C128, CELLS_C64, CELLS_CODES = 0, 1, 2  # XSW_CELLS_* (include/xsw.h): the source kinds of xsw_wind_cells
 # letter -> (ctypes type, conversion the wrapper applies: ctypes alone refuses numpy scalars)
 _SIG = {"l": (ctypes.c_int64, int), "i": (ctypes.c_int32, int), "d": (ctypes.c_double, float), "p": (ctypes.c_void_p, lambda a: a)}
 

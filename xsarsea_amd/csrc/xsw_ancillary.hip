@@ -19,22 +19,13 @@
 
 #include "xsw_host.hpp"
 #include "xsw_run.hpp"
+#include "xsw_tie.hpp"
 
 namespace {
 
 #ifndef XSW_ANC_LINES
 #define XSW_ANC_LINES 4
 #endif
-
-// One tie-grid field blended along the sample axis at the two tie lines of the current line bracket.
-struct TieRows {
-    double lon0, lon1, lat0, lat1, c0, c1, s0, s1;
-};
-
-__device__ inline double along(const double *__restrict__ f, int i, int j0, int j1, int ns, double ws0, double ws1)
-{
-    return ws0 * f[(long long)i * ns + j0] + ws1 * f[(long long)i * ns + j1];
-}
 
 // The cell of coordinate x on an axis of n nodes (n >= 2): lower node i, upper node i1, weight t of the upper one.  Periodic: x
 // is reduced into [0, n) and node n - 1 is followed by node 0.  Otherwise the pixel is inside iff 0 <= x <= n - 1, the last node
@@ -105,19 +96,13 @@ __global__ __launch_bounds__(256) void k_ancillary_model(double2 *__restrict__ o
             const int i0 = min(max(li0[l + k], 0), nl - 1);
             const double tl = lt[l + k], wl0 = 1.0 - tl, wl1 = tl;
             if (i0 != cur) {
-                const int i1 = min(i0 + 1, nl - 1);
-                q.lon0 = along(tlon, i0, j0, j1, ns, ws0, ws1); q.lon1 = along(tlon, i1, j0, j1, ns, ws0, ws1);
-                q.lat0 = along(tlat, i0, j0, j1, ns, ws0, ws1); q.lat1 = along(tlat, i1, j0, j1, ns, ws0, ws1);
-                q.c0 = along(tcos, i0, j0, j1, ns, ws0, ws1); q.c1 = along(tcos, i1, j0, j1, ns, ws0, ws1);
-                q.s0 = along(tsin, i0, j0, j1, ns, ws0, ws1); q.s1 = along(tsin, i1, j0, j1, ns, ws0, ws1);
+                q = tie_rows(tlon, tlat, tcos, tsin, i0, min(i0 + 1, nl - 1), j0, j1, ns, ws0, ws1);
                 cur = i0;
             }
-            const double lon = wl0 * q.lon0 + wl1 * q.lon1, lat = wl0 * q.lat0 + wl1 * q.lat1;
-            const double c = wl0 * q.c0 + wl1 * q.c1, s = wl0 * q.s0 + wl1 * q.s1;
-            const double nh = xsw::hypot_glibc(c, s);
-            ch[k] = c / nh;  // nh == 0 (the headings cancel): 0 / 0, the pixel is NaN
-            sh[k] = s / nh;
-            const Cell cx = cell_of((lon - lon0) / dlon, n_lon, periodic != 0), cy = cell_of((lat - lat0) / dlat, n_lat, false);
+            const TiePoint g = tie_point(q, wl0, wl1);  // the headings cancel: ch, sh NaN, the pixel is NaN
+            ch[k] = g.ch;
+            sh[k] = g.sh;
+            const Cell cx = cell_of((g.lon - lon0) / dlon, n_lon, periodic != 0), cy = cell_of((g.lat - lat0) / dlat, n_lat, false);
             inside[k] = cx.inside && cy.inside;
             tx[k] = cx.t;
             ty[k] = cy.t;

@@ -1,0 +1,335 @@
+// Block statistics of a raster on a product grid: the kernels behind xsarsea_amd.cells and its C ABI (xsw_wind_cells,
+// xsw_raster_cells; include/xsw.h has the statement).  The raster is tiled from pixel (0, 0) by cells of cell_lines x cell_samples
+// pixels, the last cell of an axis clipped; every cell gets its valid count, its float64 sums in ONE stated order and what
+// follows from them -- vector and scalar mean wind, its scatter and steadiness, with tie points the centre's position and the
+// east / north components; or mean and scatter of a real raster.
+//
+//   k_cells<Src, MAP>   Src: complex128 / complex64 winds, co-pol grid codes (read through `sol`, as k_expand reads them: 4 B per
+//                       pixel, nothing expanded), float32 / float64 rasters.  MAP: one wave per cell, or one 256-thread
+//                       workgroup per cell.  A cell has exactly one owner and there is no atomic: the result does not depend
+//                       on the launch.
+//
+// The order of every sum: pixel p = r * w + c of a cell (w its clipped width) goes to accumulator p mod 256; each accumulator
+// starts at +0.0 and adds its pixels in ascending p, an invalid pixel adding +0.0 (which changes no accumulator: none is ever
+// -0.0); then a[i] += a[i + h] for i < h, h = 128 .. 1.  A wave owns the 256 accumulators four per lane (t, t + 64, t + 128,
+// t + 192): the folds at 128 and 64 are lane-local, the rest is an xor butterfly (IEEE addition commutes, so both partners of
+// an exchange hold the same bits).  A workgroup owns them one per thread: the folds at 128 and 64 go through LDS, wave 0 does
+// the butterfly.  Both give the bits of tests/cells_ref.py.  -ffp-contract=off (xsarsea_amd/_build.py) keeps q = re * re +
+// im * im free of contractions.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+
+#include "xsw_codes.hpp"
+#include "xsw_host.hpp"
+#include "xsw_run.hpp"
+#include "xsw_tie.hpp"
+
+namespace {
+
+#ifndef XSW_CELLS_WG_AREA
+#define XSW_CELLS_WG_AREA 4096  // cells of at least this many pixels (cell_lines * cell_samples) get a workgroup each, smaller ones a wave.
+                                // Measured on 20000 x 20000 (profiles/cells_bench.json; ms wave / workgroup, complex128 | codes | float32), cells of
+                                // 20 x 20: 1.81 / 2.76 | 1.81 / 2.74 | 0.85 / 1.65, 32 x 32: 1.32 / 1.38 | 1.34 / 1.32 | 0.61 / 0.84,
+                                // 50 x 50: 1.25 / 1.23 | 1.26 / 1.20 | 0.56 / 0.69, 70 x 70: 1.23 / 1.08 | 1.26 / 1.11 | 0.55 / 0.59,
+                                // 100 x 100: 1.23 / 1.06 | 1.34 / 1.19 | 0.55 / 0.56, 300 x 300: 1.36 / 1.14 | 1.64 / 1.32 | 0.87 / 0.63,
+                                // 1000 x 1000: 8.92 / 2.59 | 10.1 / 2.85 | 7.74 / 2.07.  The wind sources cross near 50 x 50, float32 near 100 x 100.
+#endif
+// The mapping of a call: a function of the cell's nominal area alone.  Environment XSW_CELLS_MAPPING = wave | workgroup forces
+// one (tests, measurements); it is read on the host at every call, so that one process can compare the two.
+enum { MAP_WAVE = 0, MAP_WORKGROUP = 1 };
+static int cells_mapping(long long area, bool &bad_env)
+{
+    bad_env = false;
+    if (const char *v = getenv("XSW_CELLS_MAPPING")) {
+        if (!strcmp(v, "wave")) return MAP_WAVE;
+        if (!strcmp(v, "workgroup")) return MAP_WORKGROUP;
+        bad_env = true;
+    }
+    return area >= XSW_CELLS_WG_AREA ? MAP_WORKGROUP : MAP_WAVE;
+}
+
+struct CellGrid {
+    long long lines, samples, n_sc, ncells;  // the raster, cells per cell row, cells in all
+    int cl, cs;
+};
+
+// One pixel as fetched: a wind's two parts or a real value in `a`, and whether the source itself calls it valid.
+struct Px {
+    double a, b;
+    bool ok;
+};
+
+// ---- sources.  fetch(i): pixel i of the raster.  NS sums per cell; terms(): what a valid pixel adds to them.
+struct WindSums {
+    static constexpr int NS = 4;  // re, im, s, q
+    __device__ static void terms(const Px &x, double (&v)[NS])
+    {
+        const double q = x.a * x.a + x.b * x.b;
+        v[0] = x.a; v[1] = x.b; v[2] = sqrt(q); v[3] = q;
+    }
+};
+struct RealSums {
+    static constexpr int NS = 2;  // x, x * x
+    __device__ static void terms(const Px &x, double (&v)[NS]) { v[0] = x.a; v[1] = x.a * x.a; }
+};
+
+struct SrcC128 : WindSums {
+    const double2 *p;
+    __device__ Px fetch(long long i) const { const double2 z = p[i]; return Px{z.x, z.y, !(z.x != z.x) && !(z.y != z.y)}; }
+};
+struct SrcC64 : WindSums {
+    const float2 *p;
+    __device__ Px fetch(long long i) const { const float2 z = p[i]; return Px{(double)z.x, (double)z.y, !(z.x != z.x) && !(z.y != z.y)}; }
+};
+struct SrcCodes : WindSums {
+    const unsigned *p;
+    const double *sol;
+    long long plane;
+    __device__ Px fetch(long long i) const
+    {
+        const auto read = [](const double *table, long long k) { const double2 z = ((const double2 *)table)[k]; return xsw::Wind{z.x, z.y}; };
+        xsw::Wind co;
+        const xsw::CoPoint g = xsw::expand_co(p[i], plane, sol, read, co);  // valid iff co_decode(code, plane).grid()
+        return Px{co.re, co.im, g.have};
+    }
+};
+template <typename T>
+struct SrcReal : RealSums {
+    const T *p;
+    __device__ Px fetch(long long i) const { const T x = p[i]; return Px{(double)x, 0.0, !(x != x)}; }
+};
+
+// ---- what is written per cell, by the one lane that holds the folded sums.  Every pointer may be null: not computed, not written.
+__device__ inline double scatter(double sq, double s, double nd, int n)
+{
+    const double var = (sq - (s * s) / nd) / (nd - 1.0);
+    return n < 2 ? __builtin_nan("") : sqrt(var < 0.0 ? 0.0 : var);  // not fmax: n == 1 must stay NaN
+}
+
+struct WindOuts {
+    int *count;
+    double2 *wind;
+    double *wspd, *wspd_std, *steadiness, *lon, *lat, *u, *v;
+    const double *tlon, *tlat, *tcos, *tsin;  // tlon null: no geolocation
+    const int *li0, *sj0;                     // per cell row / cell column: the bracket of the centre between tie points
+    const double *lt, *st;
+    int nl, ns;
+    __device__ void write(long long cell, long long ci, long long cj, int n, const double (&s)[4]) const
+    {
+        const double nd = (double)n;
+        const double mre = s[0] / nd, mim = s[1] / nd, ws = s[2] / nd;
+        if (count) count[cell] = n;
+        if (wind) wind[cell] = make_double2(mre, mim);
+        if (wspd) wspd[cell] = ws;
+        if (wspd_std) wspd_std[cell] = scatter(s[3], s[2], nd, n);
+        if (steadiness) steadiness[cell] = sqrt(mre * mre + mim * mim) / ws;
+        if (!tlon) return;
+        const int i0 = min(max(li0[ci], 0), nl - 1), j0 = min(max(sj0[cj], 0), ns - 1);
+        const double tl = lt[ci], ts = st[cj];
+        const TieRows q = tie_rows(tlon, tlat, tcos, tsin, i0, min(i0 + 1, nl - 1), j0, min(j0 + 1, ns - 1), ns, 1.0 - ts, ts);
+        const TiePoint g = tie_point(q, 1.0 - tl, tl);
+        if (lon) lon[cell] = g.lon;
+        if (lat) lat[cell] = g.lat;
+        if (u) u[cell] = -(mre * g.ch + mim * g.sh);
+        if (v) v[cell] = -(mim * g.ch - mre * g.sh);
+    }
+};
+
+struct RealOuts {
+    int *count;
+    double *mean, *std;
+    __device__ void write(long long cell, long long, long long, int n, const double (&s)[2]) const
+    {
+        const double nd = (double)n;
+        if (count) count[cell] = n;
+        if (mean) mean[cell] = s[0] / nd;
+        if (std) std[cell] = scatter(s[1], s[0], nd, n);
+    }
+};
+
+// A thread walks its cell in steps of STRIDE pixels (64: a wave's lane, 256: a workgroup's thread), STEPS = 4 steps per trip,
+// whose four loads (and keep bytes) are issued before the first is used.  Wave: step j of a trip feeds accumulator t + 64 j.
+// Workgroup: the four steps feed the thread's one accumulator in ascending p (eight steps per trip measured no better: 2.71
+// against 2.59 ms at 1000 x 1000, 1.15 against 1.05 ms at 100 x 100).  (r, c) follow p without a division per pixel.
+template <typename Src, int MAP, typename Outs>
+__global__ __launch_bounds__(256) void k_cells(const Src src, const unsigned char *__restrict__ keep, const CellGrid g, const Outs o)
+{
+    constexpr int NS = Src::NS, STRIDE = MAP == MAP_WAVE ? 64 : 256, NACC = MAP == MAP_WAVE ? 4 : 1, STEPS = 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int t = MAP == MAP_WAVE ? lane : (int)threadIdx.x;
+    const long long cell = MAP == MAP_WAVE ? (long long)blockIdx.x * 4 + wave : (long long)blockIdx.x;
+    if (cell >= g.ncells) return;  // whole waves of the last workgroup (wave mapping only: no barrier follows there)
+    const long long ci = cell / g.n_sc, cj = cell - ci * g.n_sc;
+    const long long row0 = ci * g.cl, col0 = cj * g.cs;
+    const long long h = min((long long)g.cl, g.lines - row0);
+    const int w = (int)min((long long)g.cs, g.samples - col0);
+    const long long N = h * w, first = row0 * g.samples + col0;
+    const int dq = STRIDE / w, dr = STRIDE % w;
+    long long r = t / w;
+    int c = t % w;
+
+    double acc[NACC][NS];
+#pragma unroll
+    for (int j = 0; j < NACC; ++j)
+#pragma unroll
+        for (int k = 0; k < NS; ++k) acc[j][k] = 0.0;
+    int n = 0;
+    for (long long b = t; b - t < N; b += STEPS * STRIDE) {
+        Px x[STEPS];
+#pragma unroll
+        for (int j = 0; j < STEPS; ++j) {
+            x[j] = Px{0.0, 0.0, false};
+            if (b + j * STRIDE < N) {
+                const long long i = first + r * g.samples + c;
+                x[j] = src.fetch(i);
+                if (keep) x[j].ok = x[j].ok && keep[i] != 0;
+            }
+            c += dr;
+            r += dq;
+            if (c >= w) { c -= w; ++r; }
+        }
+#pragma unroll
+        for (int j = 0; j < STEPS; ++j) {
+            double v[NS];
+            Src::terms(x[j], v);
+            n += x[j].ok ? 1 : 0;
+#pragma unroll
+            for (int k = 0; k < NS; ++k) acc[MAP == MAP_WAVE ? j : 0][k] += x[j].ok ? v[k] : 0.0;
+        }
+    }
+
+    double s[NS];
+    if constexpr (MAP == MAP_WAVE) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            acc[0][k] += acc[2][k];  // h = 128
+            acc[1][k] += acc[3][k];
+            s[k] = acc[0][k] + acc[1][k];  // h = 64
+        }
+    } else {
+        __shared__ double part[NS][256];
+        __shared__ int part_n[4];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) part[k][t] = acc[0][k];
+        __syncthreads();
+        if (t < 128)  // h = 128
+#pragma unroll
+            for (int k = 0; k < NS; ++k) part[k][t] += part[k][t + 128];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] = t < 64 ? part[k][t] + part[k][t + 64] : 0.0;  // h = 64
+#pragma unroll
+        for (int hh = 32; hh >= 1; hh >>= 1) n += __shfl_xor(n, hh);
+        if (lane == 0) part_n[wave] = n;
+        __syncthreads();
+        if (wave != 0) return;
+        n = part_n[0] + part_n[1] + part_n[2] + part_n[3];
+    }
+#pragma unroll
+    for (int hh = 32; hh >= 1; hh >>= 1) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) s[k] += __shfl_xor(s[k], hh);
+        if constexpr (MAP == MAP_WAVE) n += __shfl_xor(n, hh);
+    }
+    if (lane == 0) o.write(cell, ci, cj, n, s);
+}
+
+template <typename Src, typename Outs>
+static void launch_cells(hipStream_t stream, int map, const Src &src, const void *keep, const CellGrid &g, const Outs &o)
+{
+    if (map == MAP_WAVE)
+        hipLaunchKernelGGL((k_cells<Src, MAP_WAVE, Outs>), dim3((unsigned)((g.ncells + 3) / 4)), dim3(256), 0, stream, src, (const unsigned char *)keep, g, o);
+    else
+        hipLaunchKernelGGL((k_cells<Src, MAP_WORKGROUP, Outs>), dim3((unsigned)g.ncells), dim3(256), 0, stream, src, (const unsigned char *)keep, g, o);
+}
+
+// The refusals the two entries share, the cell grid and the mapping.
+static int plan_cells(xsw_ctx *c, const char *who, int64_t lines, int64_t samples, int32_t mem, int32_t cell_lines, int32_t cell_samples, CellGrid &g,
+                      int &map)
+{
+    if (lines < 1 || samples < 1) return fail(c, XSW_EINVAL, "%s: the raster must have one line and one sample or more", who);
+    if (cell_lines < 1 || cell_samples < 1) return fail(c, XSW_EINVAL, "%s: cells must be 1 x 1 pixels or more, not %d x %d", who, (int)cell_lines, (int)cell_samples);
+    if (int rc = check_dims(c, who, lines, samples + 256)) return rc;  // the kernel's column index runs up to 256 past a cell's width
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
+    g.lines = lines; g.samples = samples;
+    g.cl = (int)std::min<int64_t>(cell_lines, lines);  // a larger cell is clipped to the raster anyway
+    g.cs = (int)std::min<int64_t>(cell_samples, samples);
+    const long long n_lc = (lines + g.cl - 1) / g.cl;
+    g.n_sc = (samples + g.cs - 1) / g.cs;
+    g.ncells = n_lc * g.n_sc;
+    bool bad_env;
+    map = cells_mapping((long long)cell_lines * cell_samples, bad_env);
+    if (bad_env) return fail(c, XSW_EINVAL, "%s: XSW_CELLS_MAPPING must be wave or workgroup", who);
+    if ((map == MAP_WAVE ? (g.ncells + 3) / 4 : g.ncells) > 0x7fffffffLL) return fail(c, XSW_EINVAL, "%s: too many cells for one launch", who);
+    return XSW_OK;
+}
+
+}  // namespace
+
+extern "C" int xsw_wind_cells(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, int32_t src_kind, const void *src, const uint8_t *keep,
+                              int32_t cell_lines, int32_t cell_samples, int32_t n_tie_lines, int32_t n_tie_samples, const double *tie_lon,
+                              const double *tie_lat, const double *tie_cos, const double *tie_sin, const int32_t *line_first, const double *line_t,
+                              const int32_t *sample_first, const double *sample_t, int32_t *out_count, double *out_wind, double *out_wspd,
+                              double *out_wspd_std, double *out_steadiness, double *out_longitude, double *out_latitude, double *out_u, double *out_v)
+{
+    if (!c) return XSW_EINVAL;
+    if (!src) return fail(c, XSW_EINVAL, "wind_cells: no source");
+    if (src_kind != XSW_CELLS_C128 && src_kind != XSW_CELLS_C64 && src_kind != XSW_CELLS_CODES)
+        return fail(c, XSW_EINVAL, "wind_cells: src_kind must be XSW_CELLS_C128, XSW_CELLS_C64 or XSW_CELLS_CODES");
+    if (src_kind == XSW_CELLS_CODES && !c->have_co) return fail(c, XSW_ENOLUT, "wind_cells: co-pol codes given but no co-pol LUT on this context");
+    if (!tie_lon && (out_longitude || out_latitude || out_u || out_v))
+        return fail(c, XSW_EINVAL, "wind_cells: longitude, latitude, u and v need tie points");
+    if (tie_lon && (!tie_lat || !tie_cos || !tie_sin || !line_first || !line_t || !sample_first || !sample_t || n_tie_lines < 1 || n_tie_samples < 1))
+        return fail(c, XSW_EINVAL, "wind_cells: tie points need their four grids, both brackets and one point or more per axis");
+    CellGrid g;
+    int map;
+    if (int rc = plan_cells(c, "wind_cells", lines, samples, mem, cell_lines, cell_samples, g, map)) return rc;
+    const size_t npx = (size_t)lines * samples, nc = (size_t)g.ncells, n_lc = nc / (size_t)g.n_sc, n_sc = (size_t)g.n_sc;
+    const size_t ties = tie_lon ? (size_t)n_tie_lines * n_tie_samples * 8 : 0;
+    const size_t elem = src_kind == XSW_CELLS_C128 ? 16 : src_kind == XSW_CELLS_C64 ? 8 : 4;
+    Buf b[19] = {{src, nullptr, npx * elem}, in_buf(keep, npx), in_buf(tie_lon, ties), in_buf(tie_lat, ties), in_buf(tie_cos, ties), in_buf(tie_sin, ties),
+                 in_buf(tie_lon ? line_first : nullptr, n_lc * 4), in_buf(tie_lon ? line_t : nullptr, n_lc * 8),
+                 in_buf(tie_lon ? sample_first : nullptr, n_sc * 4), in_buf(tie_lon ? sample_t : nullptr, n_sc * 8),
+                 out_buf(out_count, nc * 4), out_buf(out_wind, nc * 16), out_buf(out_wspd, nc * 8), out_buf(out_wspd_std, nc * 8),
+                 out_buf(out_steadiness, nc * 8), out_buf(out_longitude, nc * 8), out_buf(out_latitude, nc * 8), out_buf(out_u, nc * 8),
+                 out_buf(out_v, nc * 8)};
+    return run(c, mem, b, [&](Buf (&x)[19]) {
+        WindOuts o;
+        o.count = (int *)x[10].dev; o.wind = (double2 *)x[11].dev; o.wspd = (double *)x[12].dev; o.wspd_std = (double *)x[13].dev;
+        o.steadiness = (double *)x[14].dev; o.lon = (double *)x[15].dev; o.lat = (double *)x[16].dev; o.u = (double *)x[17].dev; o.v = (double *)x[18].dev;
+        o.tlon = (const double *)x[2].dev; o.tlat = (const double *)x[3].dev; o.tcos = (const double *)x[4].dev; o.tsin = (const double *)x[5].dev;
+        o.li0 = (const int *)x[6].dev; o.lt = (const double *)x[7].dev; o.sj0 = (const int *)x[8].dev; o.st = (const double *)x[9].dev;
+        o.nl = n_tie_lines; o.ns = n_tie_samples;
+        if (src_kind == XSW_CELLS_C128) { SrcC128 s; s.p = (const double2 *)x[0].dev; launch_cells(c->stream, map, s, x[1].dev, g, o); }
+        else if (src_kind == XSW_CELLS_C64) { SrcC64 s; s.p = (const float2 *)x[0].dev; launch_cells(c->stream, map, s, x[1].dev, g, o); }
+        else {
+            SrcCodes s;
+            s.p = (const unsigned *)x[0].dev; s.sol = c->T.sol; s.plane = (long long)c->T.n_w * c->T.n_phi;
+            launch_cells(c->stream, map, s, x[1].dev, g, o);
+        }
+    }, "wind_cells");
+}
+
+extern "C" int xsw_raster_cells(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, int32_t dtype, const void *x, const uint8_t *keep,
+                                int32_t cell_lines, int32_t cell_samples, int32_t *out_count, double *out_mean, double *out_std)
+{
+    if (!c) return XSW_EINVAL;
+    if (!x) return fail(c, XSW_EINVAL, "raster_cells: no source");
+    if (dtype != XSW_F32 && dtype != XSW_F64) return fail(c, XSW_EINVAL, "raster_cells: dtype must be XSW_F32 or XSW_F64");
+    CellGrid g;
+    int map;
+    if (int rc = plan_cells(c, "raster_cells", lines, samples, mem, cell_lines, cell_samples, g, map)) return rc;
+    const size_t npx = (size_t)lines * samples, nc = (size_t)g.ncells;
+    Buf b[5] = {{x, nullptr, npx * (dtype == XSW_F32 ? 4 : 8)}, in_buf(keep, npx), out_buf(out_count, nc * 4), out_buf(out_mean, nc * 8),
+                out_buf(out_std, nc * 8)};
+    return run(c, mem, b, [&](Buf (&y)[5]) {
+        RealOuts o;
+        o.count = (int *)y[2].dev; o.mean = (double *)y[3].dev; o.std = (double *)y[4].dev;
+        if (dtype == XSW_F32) { SrcReal<float> s; s.p = (const float *)y[0].dev; launch_cells(c->stream, map, s, y[1].dev, g, o); }
+        else { SrcReal<double> s; s.p = (const double *)y[0].dev; launch_cells(c->stream, map, s, y[1].dev, g, o); }
+    }, "raster_cells");
+}

@@ -143,6 +143,13 @@ class CopolCodes:
             return _engine.expand_device(self.lut_co, self.codes)
         return _engine.expand_codes(self.lut_co, None, self.codes, None)[0]
 
+    def cells(self, cell, *, tie_points=None, line=None, sample=None, keep=None):
+        """`xsarsea_amd.wind_cells(self.wind(), cell, ...)` from the stored codes: the co-pol wind on the product grid of
+        `cell = (cell_lines, cell_samples)` pixels per cell (`WindCells`).  The pass reads the 4-byte codes and expands nothing;
+        the result equals that of the complex128 expansion bit for bit.  Arguments and refusals as `wind_cells`."""
+        from .. import cells as _cells
+        return _cells.codes_cells(self.codes, self.lut_co, cell, tie_points=tie_points, line=line, sample=sample, keep=keep)
+
     def dual(self, sigma0_dual, dsig_cr=0.1, model=None, dual_select=True, codes=False, **kwargs):
         """`wind_dual`, the second element of `invert_from_model(inc, sigma0, sigma0_dual, model=(co, model), dsig_cr=...)`, bit
         for bit, from the stored co-pol codes.  model: the cross-pol model; **kwargs go to its `to_lut`.  dual_select=False:
