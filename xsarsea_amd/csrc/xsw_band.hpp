@@ -106,11 +106,23 @@ static_assert(XSW_BAND_WG_WAVES % 4 == 0 || !XSW_BAND_POOL, "pooled class counts
 #endif
 
 struct BandSlot {  // 64 bytes per pixel, read by every lane of its segment (same address: LDS broadcast)
-    double sn, thr_lo, thr_hi, ah, bh, m2;
+    double sn, thr_lo, thr_hi, ah, bh;
+    // pooled queues (k_invert_band, XSW_BAND_POOL): what a block of its own used to hold -- res: the winning flat index of THIS slot's
+    // pixel (-1: undecided); pos: the slot of the pixel of the thread with this slot's number (lane -> slot, parked here through
+    // the passes: one VGPR less where the pressure peaks).  They took the place of |a/2|^2, which a pass needs once, for its settle
+    // threshold, and forms again from ah and bh: the 2 KB pay for most of the direction table in LDS (kBandCsCap).
+    int res, pos;
     int inc_bin /* i_inc | threshold bin of s - d << 16 */, rows /* w_lo | w_hi << 16 */, ipn /* ip_lo | ncols << 16 */;
     int bin_hi /* threshold bin above s + d, or -1 */;
 };
 
+// Directions whose cos / sin pair (DevTables::csphi, 16 bytes each) k_invert_band keeps in LDS for its passes: 192 cover the
+// reference LUT's 181 in 3 KB -- 16 KB of slots + the pool + this is 20 016 B, inside the 20 480 B that eight workgroups per CU
+// leave each.  A LUT with more directions runs the instantiation that reads the table from global memory (ChainPlan::cs_lds).
+#ifndef XSW_BAND_CS_CAP
+#define XSW_BAND_CS_CAP 192
+#endif
+constexpr int kBandCsCap = XSW_BAND_CS_CAP;
 constexpr int kBandClasses = 11;  // window classes S x K = 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128 (band_wave)
 struct BandPool {  // a workgroup's pooled class queues (k_invert_band, XSW_BAND_POOL)
     alignas(4) unsigned char cnt[kBandClasses][XSW_BAND_WG_WAVES];  // pixels of each class in each wave's slots
@@ -209,11 +221,16 @@ __device__ __forceinline__ double ld_co(const char *__restrict__ base, unsigned 
 #ifndef XSW_CHORD_MRG
 #define XSW_CHORD_MRG 2e-3  // index units of slack on a chord's row bounds (k_invert_band2: chord_budget; as box_from_jub)
 #endif
-template <int S, int K, bool COUNT>
+// PACKED: the result goes into the slot itself (BandSlot::res; the pooled queues), not into `res`.  CSLDS: cos / sin of a direction
+// come from `cs_lds`, the workgroup's LDS copy of L.csphi (k_invert_band loads it), not from global memory: K reads of 16 bytes
+// per lane, pass and chunk that the texture addresser -- about three quarters busy in this kernel -- no longer sees, on an LDS
+// pipe that is nearly idle.  Compile-time both: no branch in the pass.
+template <int S, int K, bool COUNT, bool PACKED = false, bool CSLDS = false>
 __device__ __forceinline__ void co_band_pass(const DevTables &L, double inv_dsig, int lane,
-                                             const BandSlot *slots /* this wave's [64], sorted by class; pooled: the workgroup's */, int *res /* by slot */,
+                                             BandSlot *slots /* this wave's [64], sorted by class; pooled: the workgroup's */, int *res /* by slot (PACKED: unused) */,
                                              int first, int count /* slots [first, first + count) -> segments 0 .. count-1 */, unsigned &cand,
-                                             const unsigned short *map = nullptr /* pooled: queue position -> slot (BandPool) */)
+                                             const unsigned short *map = nullptr /* pooled: queue position -> slot (BandPool) */,
+                                             const double2 *cs_lds = nullptr /* CSLDS: [n_phi] in LDS */)
 {
     constexpr int sweep_max = XSW_BAND_MAX;  // rows a direction may hold
     const double inf = __builtin_inf();
@@ -256,7 +273,9 @@ __device__ __forceinline__ void co_band_pass(const DevTables &L, double inv_dsig
             act[j] = valid && vcol < B_ncols;
             ip[j] = B_ip_lo + (act[j] ? vcol : 0);
             const unsigned ipB = (unsigned)ip[j] * 8u;
-            const double2 cs = *(const double2 *)((const char *)L.csphi + 2u * ipB);
+            double2 cs;
+            if constexpr (CSLDS) cs = cs_lds[ip[j]];
+            else cs = *(const double2 *)((const char *)L.csphi + 2u * ipB);
             U[j] = 2.0 * (B.ah * cs.x + B.bh * cs.y);
             off0[j] = slice0 + ipB;
         }
@@ -307,11 +326,22 @@ __device__ __forceinline__ void co_band_pass(const DevTables &L, double inv_dsig
     }
     const int bflat = (int)__umul24((unsigned)brow, (unsigned)L.n_phi) + bip;
     const double gmin = S == 64 ? wave_min_d(best) : seg_min_d<S>(best);
-    const double T = gmin + 1e-9 * (1.0 + fabs(gmin) + slots[owner].m2);  // re-read: not kept live through the sweep
+    // |a/2|^2 of the settle threshold, formed here from a RE-READ of the slot (not kept live through the sweep), in one fixed
+    // order: (ah * ah) + (bh * bh), no contraction.  It only scales a 1e-9-relative margin: should it ever differ in the last bit
+    // from a value formed elsewhere, only a near-tie at the 1e-16 level could move between "decided here" and "listed", and both
+    // give the reference's argmin.
+    // (volatile, and through an LDS pointer -- a generic volatile pointer makes them flat loads: loads of their own, after the sweep)
+    const volatile __attribute__((address_space(3))) BandSlot *again = (const volatile __attribute__((address_space(3))) BandSlot *)(slots + owner);
+    const double ah_t = again->ah, bh_t = again->bh;
+    const double ah2 = ah_t * ah_t, bh2 = bh_t * bh_t;
+    const double T = gmin + 1e-9 * (1.0 + fabs(gmin) + (ah2 + bh2));
     const unsigned long long amb = ballot64(valid && (second <= T || overflow)), surv = ballot64(valid && best <= T);
     const unsigned long long segmask = S == 64 ? ~0ULL : (((1ULL << (S & 63)) - 1ULL) << ((q * S) & 63));
     const bool bad = (amb & segmask) != 0ULL || __popcll(surv & segmask) != 1 || !(gmin < 1e300);
-    if (valid && ((!bad && best <= T) || (bad && sl == 0))) res[owner] = bad ? -1 : bflat;  // -1: undecided here, left to k_invert_list
+    if (valid && ((!bad && best <= T) || (bad && sl == 0))) {  // -1: undecided here, left to k_invert_list
+        if constexpr (PACKED) slots[owner].res = bad ? -1 : bflat;
+        else res[owner] = bad ? -1 : bflat;
+    }
     if (COUNT) {
         unsigned c = ncand;
         for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
@@ -425,11 +455,13 @@ __device__ __forceinline__ void wave_tail(const DevTables &L, const KArgs &A, lo
 //       1 = pixels whose band holds A.long_run or more rows along the a-priori direction are handed to the second band kernel
 //           (list B), the others are swept here (k_invert_band's default);
 //       2 = the rows swept in batches and clipped to the disc's chord (k_invert_band2).
-template <typename T, typename TO, bool CR, bool COUNT, int ROLE = 0>
+template <typename T, typename TO, bool CR, bool COUNT, int ROLE = 0, bool CSLDS = false>
 __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, long long i, bool in, int lane, BandSlot *__restrict__ slots,
-                                          int *__restrict__ res_, bool strip_walk = false /* ROLE 2 walking every strip: the short-run pixels are k_invert_band's */,
+                                          int *__restrict__ res_ /* pooled: unused, the slots hold its words (BandSlot::res, pos) */,
+                                          bool strip_walk = false /* ROLE 2 walking every strip: the short-run pixels are k_invert_band's */,
                                           long long strip = -1 /* the wave's pixels are strip `strip` of the raster (lane = sample); -1: listed pixels */,
-                                          BandPool *__restrict__ pool = nullptr /* k_invert_band: the workgroup's pooled queues (XSW_BAND_POOL) */)
+                                          BandPool *__restrict__ pool = nullptr /* k_invert_band: the workgroup's pooled queues (XSW_BAND_POOL) */,
+                                          double2 *cs_lds = nullptr /* CSLDS: the workgroup's LDS copy of L.csphi, filled here */)
 {
     const double nan = __builtin_nan("");
     int flags, my_flat = -1, my_icr = -1;
@@ -437,10 +469,16 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
     constexpr int NC = kBandClasses;  // window classes: S lanes x K directions = 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128 (and wider: chunks)
     // POOLED (k_invert_band, XSW_BAND_POOL): the classes of the workgroup's waves form ONE queue each, and its passes are dealt to the
     // waves round-robin -- a class present in several waves leaves one part-filled last pass instead of one per wave.  Every wave
-    // still parks its pixels in its own 64 slots, sorted by class; BandPool::map says which slot a queue position is.  The res_
-    // block then holds the workgroup's results by slot (wave * 64 + slot), then the waves' lane -> slot blocks (PK).
+    // still parks its pixels in its own 64 slots, sorted by class; BandPool::map says which slot a queue position is.  Results by
+    // slot and the lanes' lane -> slot words then live in the slots themselves (BandSlot::res, pos), not in res_.
     constexpr bool POOLED = XSW_BAND_POOL && ROLE != 2;
     constexpr int WG = XSW_BAND_WG_WAVES, PK = POOLED ? 64 * WG : 64;
+    // (pooled: the wave's pixels are one strip, so the 64-bit pixel index is lane 0's -- wave-uniform, in SGPRs -- plus a small
+    // per-lane difference: ONE register through the passes instead of two, and the index is put together again for the tail.
+    // With the direction table in LDS the passes need the register: without this the mono kernel put 24 bytes per lane in scratch.)
+    const long long i_first = POOLED ? (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned long long)i >> 32)) << 32) |
+                                                   (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)i)) : 0;
+    int i_delta = POOLED ? (int)(i - i_first) : 0;
     int pos = -1, myc = NC, first[NC] = {}, ncls[NC] = {};  // slot of this lane's pixel, its class; slot range of each class
     // the pixels a class would leave for a part-filled last pass move up into the next wider class when they fit into
     // ITS part-filled last pass (their slots lie right before that class's: only the boundary moves; a narrow window in
@@ -478,7 +516,19 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
         int ncols_p = 0;
         if (todo) {
             bool loose = false;
+#ifdef XSW_BAND_DETOUR_STATS
+            // counter build (profiles/band_detours.py; production chain, xsw_stats_enable(ctx, 2)): per wave of k_invert_band, into
+            // A.stats -- [0] waves with a co-pol search, [1] the library-log10 detour (load_pixel), [2] store_pixel's near-tie path,
+            // [3] the tail-cut branch, [4] trips of the first ray's loop (xsw_invert_tu.hip keeps the other kernels' counters out)
+            unsigned ray_trips = 0;
+            CoWindow W = co_window_lanes<XSW_BAND_RAYS, XSW_BAND_RAY_D, XSW_BAND_SEEDED != 0>(L, P, A.inv_dsig_co, fabs(A.dsig_co), loose, &ray_trips);
+            if (ROLE != 2 && A.stats && A.stats_chain && lane == 0) {
+                atomicAdd(&A.stats[0], 1ULL);
+                atomicAdd(&A.stats[4], (unsigned long long)ray_trips);
+            }
+#else
             CoWindow W = co_window_lanes<XSW_BAND_RAYS, XSW_BAND_RAY_D, XSW_BAND_SEEDED != 0>(L, P, A.inv_dsig_co, fabs(A.dsig_co), loose);
+#endif
             // A window that reaches past the slice's monotone rows is still the band rule's if no row up there can be in the band:
             // every LUT value of the rows >= mono_rows in the window's directions lies above s + d (L.tail_min, a sparse table over
             // the directions: CMOD5.N saturates and then falls back slowly, so this is the common case of an a-priori wind well
@@ -489,6 +539,10 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
             if (L.tail_min) {
                 const bool fin1 = (P.flags & F_NEED_CO) != 0 && (P.flags & F_CO_FINITE) != 0;
                 const int mono1 = L.mono_rows[fin1 ? P.i_inc : 0];
+#ifdef XSW_BAND_DETOUR_STATS
+                if (ROLE != 2 && A.stats && A.stats_chain && __ballot(fin1 && W.w_hi >= mono1 && W.ip_hi >= W.ip_lo) != 0ULL && lane == 0)
+                    atomicAdd(&A.stats[3], 1ULL);
+#endif
                 if (fin1 && W.w_hi >= mono1 && W.ip_hi >= W.ip_lo) {
                     const int len = W.ip_hi - W.ip_lo + 1, k = min(31 - __clz(len), XSW_TAIL_LEVELS);
                     const double *tk = L.tail_min + mul24_sv((unsigned)L.phi_pad, (unsigned)(P.i_inc * (XSW_TAIL_LEVELS + 1) + k));
@@ -646,7 +700,7 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
             if (eligb) {
                 const double ah = 0.5 * P.a_re, bh = 0.5 * P.b_eff;
                 b.sn = -P.s_co * A.inv_dsig_co; b.thr_lo = thr_lo; b.thr_hi = thr_hi;
-                b.ah = ah; b.bh = bh; b.m2 = ah * ah + bh * bh;
+                b.ah = ah; b.bh = bh;
                 b.inc_bin = P.i_inc | (bin << 16); b.rows = W.w_lo | (w_hi_e << 16); b.ipn = W.ip_lo | (ncols_p << 16);
                 b.bin_hi = bhi < XSW_INV_BINS ? bhi : -1;
             }
@@ -673,16 +727,21 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
                 }
             }
             if (eligb) {
-                slots[pos] = b;
 #ifdef XSW_TIMING_STAGE1_ONLY
-                res_[pos] = 0;   // (timing build: pretend the pass decided, so that nothing floods the work list)
+                b.res = 0;   // (timing build: pretend the pass decided, so that nothing floods the work list)
 #else
-                res_[pos] = -1;
+                b.res = -1;
 #endif
+                BandSlot &d = slots[pos];  // (member by member: `pos` is another lane's word, written below)
+                d.sn = b.sn; d.thr_lo = b.thr_lo; d.thr_hi = b.thr_hi; d.ah = b.ah; d.bh = b.bh;
+                d.inc_bin = b.inc_bin; d.rows = b.rows; d.ipn = b.ipn; d.bin_hi = b.bin_hi;
+                if constexpr (POOLED) d.res = b.res;
+                else res_[pos] = b.res;
             }
         }
     }
-    res_[PK + lane] = pos;
+    if constexpr (POOLED) slots[lane].pos = pos;
+    else res_[PK + lane] = pos;
     // (every wave of the workgroup reaches the barriers below: k_invert_band runs a wave past the raster's last line through
     // with no pixel)
     const int wv = POOLED ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
@@ -694,6 +753,16 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
         if (lane == 0) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) pool->cnt[c][wv] = (unsigned char)ncls[c];
+        }
+        // CSLDS: the workgroup copies the cos / sin table into LDS, one entry per thread, coalesced (three wave-loads for 181
+        // directions).  The load is issued HERE, where stage 1's registers are free again (stage 1 holds 63 of the kernel's 64),
+        // and lands in LDS between the two barriers of the pooled queues, its latency behind the first one: the passes run
+        // behind the second, so the table needs no barrier of its own.
+        double2 cs_in;
+        const bool cs_mine = CSLDS && (int)threadIdx.x < L.n_phi;
+        if constexpr (CSLDS) {
+            static_assert(kBandCsCap <= 64 * WG, "one table entry per thread");
+            if (cs_mine) cs_in = ((const double2 *)L.csphi)[threadIdx.x];
         }
         __syncthreads();
         int e = 0, base = 0;
@@ -714,6 +783,9 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
         }
         settle_queues();
         if (pos >= 0) pool->map[pos + e] = (unsigned short)(wv * 64 + pos);
+        if constexpr (CSLDS) {
+            if (cs_mine) cs_lds[threadIdx.x] = cs_in;
+        }
         __syncthreads();
     } else {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -734,8 +806,8 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
             if constexpr (POOLED) {
                 const int npass = (ncls[c] + np - 1) / np;
                 for (int p = (wv - dealt) & (WG - 1); p < npass; p += WG) {
-                    co_band_pass<S, K, COUNT>(L, A.inv_dsig_co, lane, slots - 64 * wv, res_ - 64 * wv, first[c] + p * np, min(np, ncls[c] - p * np), cand,
-                                              pool->map);
+                    co_band_pass<S, K, COUNT, true, CSLDS>(L, A.inv_dsig_co, lane, slots - 64 * wv, nullptr, first[c] + p * np, min(np, ncls[c] - p * np), cand,
+                                                           pool->map, cs_lds);
 #ifdef XSW_BAND_PASS_STATS
                     pst[c < 7 ? c : 7] += (1ULL << 32) + (unsigned long long)min(np, ncls[c] - p * np);
 #endif
@@ -782,8 +854,15 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
             if (pst[k]) atomicAdd(&A.stats[k], pst[k]);
     }
 #endif
-    pos = res_[PK + lane];
-    if (pos >= 0) my_flat = res_[pos];  // -1: undecided by its pass
+    if constexpr (POOLED) {
+        __asm__ volatile("" : "+v"(i_delta));  // (opaque: the index is formed again here, not kept)
+        i = i_first + i_delta;
+        pos = slots[lane].pos;
+        if (pos >= 0) my_flat = slots[pos].res;  // -1: undecided by its pass
+    } else {
+        pos = res_[PK + lane];
+        if (pos >= 0) my_flat = res_[pos];
+    }
     if (ROLE == 1 && (flags & F_REC_DONE) != 0) in = false;  // its record is k_invert_band2's: no cross-pol search, no list, no store here
     if (ROLE == 2 && strip_walk) {  // strip walk: lanes without a co-pol search, and the pixels k_invert_band kept, are not this kernel's
         skip = skip || (flags & F_NEED_CO) == 0;
@@ -792,16 +871,20 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
     wave_tail<T, TO, CR, COUNT>(L, A, i, in, lane, flags, my_flat, strip, cand);
 }
 
-template <typename T, typename TO, bool CR, bool COUNT, int ROLE = 0>
+// CSLDS (pooled builds; the route plan's choice, ChainPlan::cs_lds: the LUT has at most kBandCsCap directions): the passes read
+// cos / sin of their directions from an LDS copy of L.csphi.
+template <typename T, typename TO, bool CR, bool COUNT, int ROLE = 0, bool CSLDS = false>
 __global__ __launch_bounds__(64 * XSW_BAND_WG_WAVES, CR ? XSW_BAND_WAVES_CR : XSW_BAND_WAVES) void k_invert_band(DevTables L, KArgs A)
 {
+    static_assert(!CSLDS || XSW_BAND_POOL, "the LDS copy of the direction table is published by the pooled queues' barriers");
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     __shared__ BandSlot slots[XSW_BAND_WG_WAVES][64];  // search parameters of the wave's eligible pixels, sorted by window class
-    __shared__ int res_[XSW_BAND_WG_WAVES][128];       // [0, 64): slot -> winning flat index (or -1); [64, 128): lane -> its pixel's slot
-                                                       // (parked here through the passes: one VGPR less where the pressure peaks);
-                                                       // pooled: the same words as results by slot of the workgroup, then lane -> slot
 #if XSW_BAND_POOL
     __shared__ BandPool pool;
+    __shared__ double2 cs_lds[CSLDS ? kBandCsCap : 1];
+#else
+    __shared__ int res_[XSW_BAND_WG_WAVES][128];       // [0, 64): slot -> winning flat index (or -1); [64, 128): lane -> its pixel's slot
+                                                       // (parked here through the passes: one VGPR less where the pressure peaks)
 #endif
     // same tile walk as k_invert (XCD x owns a contiguous range of tile columns, line groups fastest), as a 2-D grid so that
     // no division is needed: blockIdx.x = xcd + 8 * line group, blockIdx.y = tile column inside the XCD's range (workgroups
@@ -819,7 +902,7 @@ __global__ __launch_bounds__(64 * XSW_BAND_WG_WAVES, CR ? XSW_BAND_WAVES_CR : XS
     const bool live = line < A.lines;
     const bool in = live && smp < A.samples;
     const long long i = (live ? line : A.lines - 1) * A.samples + (smp < A.samples ? smp : A.samples - 1);
-    band_wave<T, TO, CR, COUNT, ROLE>(L, A, i, in, lane, slots[wv], &res_[0][0] + 64 * wv, false, line * strips_per_line + col, &pool);
+    band_wave<T, TO, CR, COUNT, ROLE, CSLDS>(L, A, i, in, lane, slots[wv], nullptr, false, line * strips_per_line + col, &pool, cs_lds);
 #else
     if (col >= strips_per_line || line >= A.lines) return;  // wave-uniform
     const bool in = smp < A.samples;

@@ -513,7 +513,11 @@ __device__ __forceinline__ double ray_probe(const double *__restrict__ ray, int 
 // 1, 2, 4, ... pairs) for as long as the slope keeps its sign, then bisect what is left.  Every probe is a real candidate, so
 // a column that is not unimodal still only loosens the bound; the trip count is that of the wave's slowest lane.
 template <int NRAYS = 1, int RAY_D = 2, bool SEEDED = false>
-__device__ __forceinline__ CoWindow co_window_lanes(const DevTables &L, const Pixel &P, double inv_dsig, double abs_dsig, bool &loose)
+__device__ __forceinline__ CoWindow co_window_lanes(const DevTables &L, const Pixel &P, double inv_dsig, double abs_dsig, bool &loose
+#ifdef XSW_BAND_DETOUR_STATS
+                                                    , unsigned *first_ray_trips = nullptr  // counter build: trips of the seeded first ray's loop (wave-uniform)
+#endif
+)
 {
     const double inf = __builtin_inf();
     const bool fin = (P.flags & F_CO_FINITE) != 0;
@@ -552,6 +556,9 @@ __device__ __forceinline__ CoWindow co_window_lanes(const DevTables &L, const Pi
             while (__ballot(lo < hi) != 0ULL) {  // wave-uniform; every trip shrinks every open bracket
                 bool right;
                 const double j = ray_probe(ray, mid, L.n_w, whs, wh0, inv_dsig, sn, ur, right);
+#ifdef XSW_BAND_DETOUR_STATS
+                if (first_ray_trips) ++*first_ray_trips;
+#endif
                 rbest = vmin(rbest, j);
                 const bool open = lo < hi;
                 lo = (open && right) ? mid + 1 : lo;
@@ -1260,6 +1267,14 @@ __device__ __forceinline__ void load_pixel(const DevTables &L, const KArgs &A, l
     const double inc = ld<T>(A.inc, il);
     P.s_co = nan; P.s_cr = nan; P.dsig = nan; P.a_re = nan; P.a_im = nan;
     if (A.s_co) P.s_co = to_db(((const T *)A.s_co)[il], A.is_db);
+#ifdef XSW_BAND_DETOUR_STATS
+    // counter build (profiles/band_detours.py): [1] waves in which some lane's float32 sigma0, after the dB offset, is no positive
+    // finite number -- the waves that go through the library's log10 (log10_fast's first line)
+    if (sizeof(T) == 4 && A.stats && A.stats_chain && A.s_co && !A.is_db) {
+        const float y = (float)((const T *)A.s_co)[il] + 1e-15f;
+        if (__ballot(!(y > 0.0f && y <= 3.40282347e38f)) != 0ULL && (threadIdx.x & 63) == 0) atomicAdd(&A.stats[1], 1ULL);
+    }
+#endif
     if (CR && A.s_cr) {
         const T x = ((const T *)A.s_cr)[il];
         P.s_cr = to_db(x, A.is_db);
@@ -1324,6 +1339,12 @@ __device__ __forceinline__ void store_pixel(const DevTables &L, const KArgs &A, 
                                    e2.x == e1.x;
                 bool second = xs < 0.0;
                 if (!clear) {
+#ifdef XSW_BAND_DETOUR_STATS
+                    if (A.stats && A.stats_chain) {  // counter build: [2] waves with a lane on the near-tie path (two emulated divisions, two float64 atan2)
+                        const unsigned long long m = __ballot(true);
+                        if ((int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(&A.stats[2], 1ULL);
+                    }
+#endif
                     const double d1 = angle_of_quotient(P.a_re, P.a_im, s1r, s1i);
                     const double d2 = angle_of_quotient(P.a_re, P.a_im, s2r, s2i);
                     second = !(fabs(d1) <= fabs(d2));

@@ -35,7 +35,7 @@ template <typename T, typename TO>
 static int launch_invert(xsw_ctx *c, const KArgs &A_in, int algo, const LaunchCtl &lc, std::string &err)
 {
     const RouteFacts f = route_facts(c->T, A_in, algo, lc);
-    const ChainPlan p(route_knobs(), f, ChainWaves{XSW_BAND_WG_WAVES, XSW_BAND2_WAVES, XSW_BLOCKS_WAVES});
+    const ChainPlan p(route_knobs(), f, ChainWaves{XSW_BAND_WG_WAVES, XSW_BAND2_WAVES, XSW_BLOCKS_WAVES, XSW_BAND_POOL ? kBandCsCap : 0});
     if (p.route == ChainPlan::TOO_LARGE) return seterr(err, XSW_EINVAL, "raster too large for one launch");
     if (p.route == ChainPlan::EXHAUSTIVE)
         return launch_exhaustive<T, TO>(c->T, A_in, lc.stream, algo == XSW_ALGO_EXHAUSTIVE) == hipSuccess
@@ -62,12 +62,21 @@ static int launch_invert(xsw_ctx *c, const KArgs &A_in, int algo, const LaunchCt
         with_pol(!f.mono, [&](auto cr) {
             constexpr bool CR = decltype(cr)::value;
             if (lc.timing) timing_mark(c);
-            if (p.count_inst) hipLaunchKernelGGL((k_invert_band<T, TO, CR, true>), band_grid, band_block, 0, lc.stream, c->T, B);  // (counts the scored candidates)
-            else if (p.band2) hipLaunchKernelGGL((k_invert_band<T, TO, CR, false, 1>), band_grid, band_block, 0, lc.stream, c->T, B);
-            else hipLaunchKernelGGL((k_invert_band<T, TO, CR, false>), band_grid, band_block, 0, lc.stream, c->T, B);
+            // (p.cs_lds: the LUT's directions fit k_invert_band's LDS copy of the cos / sin table)
+            auto band = [&](auto lds) {
+                constexpr bool CSLDS = decltype(lds)::value;
+                if (p.count_inst) hipLaunchKernelGGL((k_invert_band<T, TO, CR, true, 0, CSLDS>), band_grid, band_block, 0, lc.stream, c->T, B);  // (counts the scored candidates)
+                else if (p.band2) hipLaunchKernelGGL((k_invert_band<T, TO, CR, false, 1, CSLDS>), band_grid, band_block, 0, lc.stream, c->T, B);
+                else hipLaunchKernelGGL((k_invert_band<T, TO, CR, false, 0, CSLDS>), band_grid, band_block, 0, lc.stream, c->T, B);
+            };
+#if XSW_BAND_POOL
+            if (p.cs_lds) band(std::true_type{});
+            else
+#endif
+                band(std::false_type{});
             if (lc.timing) timing_mark(c);
-#ifdef XSW_BAND_PASS_STATS
-            B.stats = nullptr;  // counter build: the statistics buffer holds k_invert_band's passes per class (band_wave), nothing else
+#if defined(XSW_BAND_PASS_STATS) || defined(XSW_BAND_DETOUR_STATS)
+            B.stats = nullptr;  // counter builds: the statistics buffer holds k_invert_band's own counts (band_wave), nothing else
 #endif
             if (p.band2) hipLaunchKernelGGL((k_invert_band2<T, TO, CR>), dim3(p.band2_blocks), band_block, 0, lc.stream, c->T, B);
             if (lc.timing) timing_mark(c);

@@ -239,9 +239,11 @@ struct RouteFacts {
     size_t mask_strips;       // ... and their strip masks hold this many words each
 };
 
-// The kernels' own compile-time figures (xsw_band.hpp, xsw_blocks.hpp): XSW_BAND_WG_WAVES, XSW_BAND2_WAVES, XSW_BLOCKS_WAVES.
+// The kernels' own compile-time figures (xsw_band.hpp, xsw_blocks.hpp): XSW_BAND_WG_WAVES, XSW_BAND2_WAVES, XSW_BLOCKS_WAVES;
+// band_cs_cap: directions k_invert_band's LDS copy of the cos / sin table holds (kBandCsCap; 0: the build has none).
 struct ChainWaves {
     int band_wg, band2, blocks;
+    int band_cs_cap = 0;
 };
 
 struct ChainPlan {
@@ -258,6 +260,7 @@ struct ChainPlan {
     bool band2 = false;       // k_invert_band2 runs (list B)
     bool records = false;     // ... on list B's records (BandRec), not on pixel indices
     bool blocks3 = false;     // k_invert_blocks runs (list C: the finite pixels the band rule is not for)
+    bool cs_lds = false;      // k_invert_band's passes read cos / sin from the workgroup's LDS copy of the table (it holds the LUT's directions)
     bool masks = false;       // strip masks: what the consumers walk when a list overflows (only the marked pixels instead of the whole raster)
     size_t nstrips = 0;       // 64-bit words of each mask for this raster
     // the KArgs thresholds of the same names
@@ -286,6 +289,7 @@ struct ChainPlan {
         count_inst = f.stats && !f.stats_chain;
         band2 = k.long_run > 0 && !count_inst;
         records = band2 && !k.no_records;
+        cs_lds = f.n_phi >= 1 && f.n_phi <= w.band_cs_cap;  // (more directions: the instantiation that reads global memory)
         blocks3 = f.blk && f.blk_span_ok && !k.no_blocks_kernel && f.n_w < 32768 && f.n_phi < 32768;
         long_run = k.long_run;
         area_max = f.blk ? k.b2_area : 0x7fffffff;  // (without the block tables the general kernel has nothing better to offer)
