@@ -151,6 +151,28 @@ __device__ __forceinline__ void band2_core(const DevTables &L, const KArgs &A, c
 
 __device__ __forceinline__ unsigned long long ballot64(bool b) { return __builtin_amdgcn_ballot_w64(b); }
 
+// The kernel's arguments AGAIN, for the code behind the passes.  DevTables + KArgs are about 0x300 bytes of kernel arguments: what
+// the tail needs of them (lists, caps, masks, output pointers, the store's tables) is loaded at entry like everything else, and
+// the scalar allocator then carries it across stage 1 and the passes in lanes of a VGPR -- a v_writelane_b32 / v_readlane_b32 on
+// the vector pipe for every word, and one of the kernel's 64 registers.  The tail reads its arguments from the kernel-argument
+// segment itself instead: scalar loads (constant address space, wave-uniform address) through a copy of the segment pointer that
+// the compiler cannot see through, so that it can neither merge them with the loads at entry nor move them up across the
+// passes.  Layout: the band kernels are `(DevTables L, KArgs A)`, by value -- L at offset 0, A right behind it.
+constexpr int kKernargOffA = (int)((sizeof(DevTables) + alignof(KArgs) - 1) / alignof(KArgs) * alignof(KArgs));
+static_assert(std::is_trivially_copyable<DevTables>::value && std::is_trivially_copyable<KArgs>::value && alignof(DevTables) <= 8 && alignof(KArgs) <= 8,
+              "DevTables and KArgs lie in the kernel-argument segment as they are, side by side");
+struct KernArgs {
+    const DevTables *L;
+    const KArgs *A;
+};
+__device__ __forceinline__ KernArgs kernargs_again()
+{
+    typedef const __attribute__((address_space(4))) char *kptr_t;
+    kptr_t p = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
+    __asm__ volatile("" : "+s"(p));  // opaque: a pointer of its own from here on (still constant address space: s_load)
+    return KernArgs{(const DevTables *)(const char *)p, (const KArgs *)(const char *)(p + kKernargOffA)};
+}
+
 #ifndef XSW_BOUND_SLACK
 #define XSW_BOUND_SLACK 4e-6f  // outward slack of the float32 bound arithmetic (xsw_band2.hpp: Bound32)
 #endif
@@ -529,6 +551,11 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
 #else
             CoWindow W = co_window_lanes<XSW_BAND_RAYS, XSW_BAND_RAY_D, XSW_BAND_SEEDED != 0>(L, P, A.inv_dsig_co, fabs(A.dsig_co), loose);
 #endif
+            // (k_invert_band: the hand-over thresholds and list B's record arguments are stage 1's alone, and nothing before this line
+            // needs them: read here, behind the rays, they are not carried through the rays' loops in lanes of a VGPR either)
+            const KArgs *A1p = &A;
+            if constexpr (POOLED) A1p = kernargs_again().A;
+            const KArgs &A1 = *A1p;
             // A window that reaches past the slice's monotone rows is still the band rule's if no row up there can be in the band:
             // every LUT value of the rows >= mono_rows in the window's directions lies above s + d (L.tail_min, a sparse table over
             // the directions: CMOD5.N saturates and then falls back slowly, so this is the common case of an a-priori wind well
@@ -552,7 +579,7 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
                     // pixels that used to cost k_invert_list the most (whole windows of 1e4 candidates, one pixel at a time).  The
                     // band rule still holds on the monotone part; the rows past it, at most A.tail_max, are swept in full by
                     // k_invert_band2 (clipped to the disc's chord like every row there): the window is cut and the tail noted.
-                    else if (ROLE != 0 && mono1 >= 1 && W.w_hi - mono1 + 1 <= A.tail_max) { has_tail = true; w_hi_e = mono1 - 1; }
+                    else if (ROLE != 0 && mono1 >= 1 && W.w_hi - mono1 + 1 <= A1.tail_max) { has_tail = true; w_hi_e = mono1 - 1; }
                 }
             }
             const int nrows_p = w_hi_e - W.w_lo + 1;
@@ -582,13 +609,13 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
                 if (bhi < XSW_INV_BINS && !(fma((double)bhi, width, t0) > thr_hi)) ++bhi;
                 if (bhi < XSW_INV_BINS && !(fma((double)bhi, width, t0) > thr_hi)) bhi = XSW_INV_BINS;
             }
-            if (ROLE != 0 && A.arc_min < 0x7fffffff) {
+            if (ROLE != 0 && A1.arc_min < 0x7fffffff) {
                 // WIDE windows narrowed to their live arc before they are classed (window_arc) -- when enough of the wave's pixels are wide
                 // to pay for the walk (every lane waits for the widest window: 23 groups of 8 directions for 181)
                 // (a window with a tail keeps its directions: the table says nothing about the rows past the monotone ones -- k_invert_band2's
                 // live arc, which knows the tail's chord, narrows it)
-                const bool widep = eligb && !has_tail && ncols_p >= A.arc_min;
-                if (__popcll(__ballot(widep)) >= A.arc_crowd) {
+                const bool widep = eligb && !has_tail && ncols_p >= A1.arc_min;
+                if (__popcll(__ballot(widep)) >= A1.arc_crowd) {
                     const double rs = W.band_d * fabs(A.inv_dsig_co);
                     const float jub32 = (float)(rs * rs) * (1.0f + 1e-5f) + 1e-5f;
                     // (stage 1 holds 63 live VGPRs here: the walk's own state does not fit beside them, and a compiler spill costs the
@@ -647,9 +674,9 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
                 // (round 5, measured: handing the long runs to k_invert_band2 marked for its refinement moves 12 % of the pixels of the x 2.5 scene
                 // there and nearly all of them come back as too many rows -- 49 + 57 ms where 41 + 63 were; they are the pyramid's)
                 const bool long_one = eligb && run > ((w_hi_e < W.w_hi && !has_tail) ? XSW_LONG_RUN_MAX_CUT : XSW_LONG_RUN_MAX);
-                const bool big_area = eligb && !long_one && run * ncols_p > A.area_max;
-                const bool crowded = __popcll(__ballot(big_area)) >= A.b2_crowd;
-                if (big_area && crowded && run * ncols_p <= A.area_crowd_max) flags |= F_B2_CROWD;
+                const bool big_area = eligb && !long_one && run * ncols_p > A1.area_max;
+                const bool crowded = __popcll(__ballot(big_area)) >= A1.b2_crowd;
+                if (big_area && crowded && run * ncols_p <= A1.area_crowd_max) flags |= F_B2_CROWD;
                 if (long_one || (big_area && (flags & F_B2_CROWD) == 0)) {
                     myc = NC;
                     eligb = false;
@@ -657,7 +684,7 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
                     if (ROLE == 1) flags |= F_TO_C;
                 }
                 hard = has_tail || run * ncols_p >= XSW_B2_HARD_AREA || ncols_p >= 64;
-                const bool handed = eligb && (run >= A.long_run || has_tail || ncols_p >= A.wide_min);  // (a tail is k_invert_band2's whatever the run's length; a WIDE window costs a pass of its own here, while k_invert_band2 first narrows it to its live arc)
+                const bool handed = eligb && (run >= A1.long_run || has_tail || ncols_p >= A1.wide_min);  // (a tail is k_invert_band2's whatever the run's length; a WIDE window costs a pass of its own here, while k_invert_band2 first narrows it to its live arc)
                 if (ROLE == 1 && handed) {  // the second band kernel's
                     myc = NC;
                     eligb = false;
@@ -680,7 +707,7 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
                 base += ncls[c];
             }
             if constexpr (!POOLED) settle_queues();
-            const bool to_rec = ROLE == 1 && A.rec_b != nullptr && (flags & F_TO_B) != 0;
+            const bool to_rec = ROLE == 1 && A1.rec_b != nullptr && (flags & F_TO_B) != 0;
             if constexpr (ROLE == 2) {
                 // k_invert_band2 on a pixel WITHOUT a record (list B as indices, or a pixel marked in the strip mask because its
                 // record did not fit): the record stage 1 of k_invert_band would have written, built here in registers, then
@@ -704,24 +731,24 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
                 b.inc_bin = P.i_inc | (bin << 16); b.rows = W.w_lo | (w_hi_e << 16); b.ipn = W.ip_lo | (ncols_p << 16);
                 b.bin_hi = bhi < XSW_INV_BINS ? bhi : -1;
             }
-            if (ROLE == 1 && A.rec_b != nullptr) {
+            if (ROLE == 1 && A1.rec_b != nullptr) {
                 // the handed pixels' RECORDS (their search parameters: k_invert_band2 then neither gathers the rasters again nor
                 // redoes stage 1), appended compactly, one atomicAdd per wave; a record that does not fit leaves the pixel to the
                 // overflow route (wave_tail: the list's strip mask; k_invert_band2 redoes stage 1 for the marked pixels)
                 const unsigned long long hm = __ballot(to_rec);
                 if (hm) {
                     unsigned at0 = 0;
-                    if (lane == 0) at0 = atomicAdd(A.list_b_count, (unsigned)__popcll(hm));
+                    if (lane == 0) at0 = atomicAdd(A1.list_b_count, (unsigned)__popcll(hm));
                     at0 = (unsigned)__builtin_amdgcn_readfirstlane((int)at0);
                     const unsigned at = at0 + __builtin_amdgcn_mbcnt_hi((unsigned)(hm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hm, 0u));
-                    if (to_rec && at < A.list_b_cap) {
+                    if (to_rec && at < A1.list_b_cap) {
                         BandRec r;
                         r.s = P.s_co; r.ah = 0.5 * P.a_re; r.bh = 0.5 * P.b_eff; r.d = __double2float_ru(W.band_d);
                         r.inc_tail = P.i_inc | ((has_tail ? W.w_hi - w_hi_e : 0) << 16);
                         r.rows = W.w_lo | (w_hi_e << 16); r.ipn = W.ip_lo | (ncols_p << 16);
                         r.idx = (unsigned)i;
                         r.flags = (flags & ~F_TO_B) | (hard ? F_B2_HARD : 0);  // (F_B2_CROWD rides in `flags`)
-                        ((BandRec *)A.rec_b)[at] = r;
+                        ((BandRec *)A1.rec_b)[at] = r;
                         flags |= F_REC_DONE;
                     }
                 }
@@ -868,7 +895,12 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
         skip = skip || (flags & F_NEED_CO) == 0;
         in = in && !skip;
     }
-    wave_tail<T, TO, CR, COUNT>(L, A, i, in, lane, flags, my_flat, strip, cand);
+    if constexpr (POOLED) {  // k_invert_band: nothing of the arguments that only the tail needs is kept across the passes
+        const KernArgs K = kernargs_again();
+        wave_tail<T, TO, CR, COUNT>(*K.L, *K.A, i, in, lane, flags, my_flat, strip, cand);
+    } else {
+        wave_tail<T, TO, CR, COUNT>(L, A, i, in, lane, flags, my_flat, strip, cand);
+    }
 }
 
 // CSLDS (pooled builds; the route plan's choice, ChainPlan::cs_lds: the LUT has at most kBandCsCap directions): the passes read
@@ -877,6 +909,7 @@ template <typename T, typename TO, bool CR, bool COUNT, int ROLE = 0, bool CSLDS
 __global__ __launch_bounds__(64 * XSW_BAND_WG_WAVES, CR ? XSW_BAND_WAVES_CR : XSW_BAND_WAVES) void k_invert_band(DevTables L, KArgs A)
 {
     static_assert(!CSLDS || XSW_BAND_POOL, "the LDS copy of the direction table is published by the pooled queues' barriers");
+    // (L and A stay the kernel's only arguments, in this order: band_wave reads them again from the kernel-argument segment, kernargs_again)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     __shared__ BandSlot slots[XSW_BAND_WG_WAVES][64];  // search parameters of the wave's eligible pixels, sorted by window class
 #if XSW_BAND_POOL
