@@ -890,6 +890,51 @@ int xsw_wind_cells(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, in
 int xsw_raster_cells(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, int32_t dtype, const void *x, const uint8_t *keep,
                      int32_t cell_lines, int32_t cell_samples, int32_t *out_count, double *out_mean, double *out_std);
 
+/* ---- wind on a regular longitude / latitude grid (xsarsea_amd.grid): order-free binning in fixed point, the building block of
+ * maps, mosaics of several scenes and tiled or multi-GPU reductions.  Additive to XSW_VERSION 4; conventions as above.
+ *
+ * Every pixel of the lines x samples source (src_kind, src, keep: the kinds, the validity rule and the keep rule of
+ * xsw_wind_cells) is geolocated from the scene's tie points (REQUIRED here: the four grids, and the PER-PIXEL brackets
+ * line_first / line_t [lines], sample_first / sample_t [samples], prepared exactly as for xsw_ancillary_model) and adds five
+ * 64-bit integers to the bin of the grid it falls into.  The grid: n_lon x n_lat bins, bin (j, i) covering
+ * [lon0 + i * dlon, lon0 + (i + 1) * dlon) x the latitudes between lat0 + j * dlat and lat0 + (j + 1) * dlat; lon0 and lat0 are
+ * the EDGES of bin 0, not nodes; dlon > 0; dlat finite, non-zero and signed (a descending axis: dlat < 0); n_lon, n_lat >= 1 and
+ * n_lon * n_lat fits int32; periodic is 0 or 1.  sums: int64 [5][n_lat][n_lon], the planes n, Su, Sv, Ss, Sq.  The entry ADDS
+ * into sums; the caller zeroes them (XSW_MEM_HOST: sums is copied up, added to and copied down).
+ *
+ * Per pixel, every operation float64 and rounded once, in this order:
+ *   1. (lon, lat, ch, sh): steps 1-2 of xsw_ancillary_model, unchanged (the same device code)
+ *   2. re, im widened to float64;  q = re * re + im * im,  sp = sqrt(q),  u = -(re * ch + im * sh),  v = -(im * ch - re * sh)
+ *      (the cells' expressions, per pixel and with the pixel's own heading)
+ *   3. x = (lon - lon0) / dlon,  y = (lat - lat0) / dlat
+ *      periodic != 0 (n_lon * dlon is 360):  x = x - floor(x / n_lon) * n_lon, and 0 where that is not inside [0, n_lon)  (the
+ *        rule of xsw_ancillary_model);  otherwise, and always for y:  the pixel is dropped unless 0 <= x < n: the upper edge is
+ *        outside;  i = floor(x), j = floor(y)
+ *   4. the pixel is dropped unless the source is valid, keep is non-zero, u and v are not NaN (cancelling headings give NaN) and
+ *      q < 65536 (a speed below 256 m/s)
+ *   5. bin (j, i):  n += 1,  Su += Q24(u),  Sv += Q24(v),  Ss += Q24(sp),  Sq += Q16(q)
+ *      with Q24(a) = llrint(a * 16777216.0), Q16(a) = llrint(a * 65536.0), rounding half to even
+ * Integer addition has no order: any launch geometry, any pre-aggregation, any split of a scene into tiles, any order of scenes
+ * and any number of devices whose planes are added afterwards give the same bits.  tests/grid_ref.py restates the entry in numpy.
+ *
+ * Overflow.  Every addend is below 2**32 * (1 + 2**-50) in magnitude (step 4's last condition makes this unconditional), so a
+ * bin is exact up to 2**30 pixels over all accumulated calls (a 20000 x 20000 scene has 2**28.6 pixels in all).  This is not
+ * checked at run time.
+ *
+ * Finish (not part of the entry: elementwise on the grid, in the caller's float64), with nd = (double)n:
+ *   u = ((double)Su / nd) * 2**-24, v and wspd (from Ss) likewise;  s1 = (double)Ss * 2**-24,  s2 = (double)Sq * 2**-16,
+ *   var = (s2 - (s1 * s1) / nd) / (nd - 1),  wspd_std = NaN for n < 2, else sqrt(var < 0 ? 0 : var),
+ *   steadiness = sqrt(u * u + v * v) / wspd;  n == 0 gives NaN everywhere.
+ * A mean differs from the exact mean of the per-pixel values by at most 2**-25 (the quantisation) + the division's rounding.
+ *
+ * Environment XSW_GRID_PATH = direct | lds, read at every call (any other value is refused): `direct` sends every pixel's five
+ * adds straight to global memory, `lds` (the default) pre-aggregates per thread and per workgroup first.  Both give the same bits. */
+int xsw_wind_grid(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, int32_t src_kind, const void *src, const uint8_t *keep,
+                  int32_t n_tie_lines, int32_t n_tie_samples, const double *tie_lon, const double *tie_lat, const double *tie_cos,
+                  const double *tie_sin, const int32_t *line_first, const double *line_t, const int32_t *sample_first,
+                  const double *sample_t, double lon0, double dlon, int32_t n_lon, int32_t periodic, double lat0, double dlat,
+                  int32_t n_lat, int64_t *sums);
+
 #ifdef __cplusplus
 }
 #endif

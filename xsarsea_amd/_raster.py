@@ -51,7 +51,7 @@ class _Raster:
         self.pol = (np.arange(values.shape[0]) if pol is None else _coord_values(pol)) if self.has_pol else None
 
 
-_TORCH_DTYPE = {np.float32: "float32", np.float64: "float64", np.complex128: "complex128", np.int32: "int32", np.uint8: "uint8"}
+_TORCH_DTYPE = {np.float32: "float32", np.float64: "float64", np.complex128: "complex128", np.int32: "int32", np.int64: "int64", np.uint8: "uint8"}
 
 
 class _Call:

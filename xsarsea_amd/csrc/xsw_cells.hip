@@ -8,6 +8,9 @@
 //                       pixel, nothing expanded), float32 / float64 rasters.  MAP: one wave per cell, or one 256-thread
 //                       workgroup per cell.  A cell has exactly one owner and there is no atomic: the result does not depend
 //                       on the launch.
+//   k_wind_grid<Src, DIRECT>  the same wind sources binned on a regular longitude / latitude grid (xsw_wind_grid,
+//                       xsarsea_amd.grid): every pixel geolocated from the tie points, its terms added to its bin as 64-bit
+//                       integers in fixed point, which have no order; stated and described further down.
 //
 // The order of every sum: pixel p = r * w + c of a cell (w its clipped width) goes to accumulator p mod 256; each accumulator
 // starts at +0.0 and adds its pixels in ascending p, an invalid pixel adding +0.0 (which changes no accumulator: none is ever
@@ -268,7 +271,232 @@ static int plan_cells(xsw_ctx *c, const char *who, int64_t lines, int64_t sample
     return XSW_OK;
 }
 
+// ---- wind on a regular longitude / latitude grid: order-free binning in fixed point (xsw_wind_grid; include/xsw.h has the
+// statement).  Every valid pixel adds five 64-bit integers to its bin, so the sums depend on no order: the launch geometry, the
+// pre-aggregation below and the path switch change no bit.
+#ifndef XSW_GRID_LINES
+#define XSW_GRID_LINES 4  // lines in flight per lane: their loads are issued before the first is used, as k_ancillary_model does
+#endif
+#ifndef XSW_GRID_MIN_LINES
+#define XSW_GRID_MIN_LINES 32  // a workgroup's strip is at least this many lines long (strip_grid alone gives small rasters one line per workgroup: no run)
+#endif
+#ifndef XSW_GRID_SLOTS
+#define XSW_GRID_SLOTS 256  // slots of the workgroup's LDS table, a power of two: 4 B of tag and 40 B of sums each, 11 KiB
+#endif
+static_assert((XSW_GRID_SLOTS & (XSW_GRID_SLOTS - 1)) == 0 && XSW_GRID_SLOTS >= 2, "the slot of a bin is a masked hash");
+
+// The path of a call.  Environment XSW_GRID_PATH = direct | lds forces one (tests, measurements); read on the host at every call.
+enum { GRID_LDS = 0, GRID_DIRECT = 1 };
+static int grid_path(bool &bad_env)
+{
+    bad_env = false;
+    if (const char *v = getenv("XSW_GRID_PATH")) {
+        if (!strcmp(v, "direct")) return GRID_DIRECT;
+        if (!strcmp(v, "lds")) return GRID_LDS;
+        bad_env = true;
+    }
+    return GRID_LDS;
+}
+
+struct LonLat {
+    double lon0, dlon, lat0, dlat;
+    int n_lon, n_lat, periodic;
+};
+
+struct GridTies {
+    const double *tlon, *tlat, *tcos, *tsin;
+    const int *li0, *sj0;  // per line / per sample: the pixel's bracket between tie points
+    const double *lt, *st;
+    int nl, ns;
+};
+
+// llrint(a * scale), halves to even; |a * scale| < 2**33 for every pixel that is added.
+__device__ inline unsigned long long fixed_point(double a, double scale) { return (unsigned long long)(long long)__builtin_rint(a * scale); }
+
+// The geometry of k_ancillary_model: grid.x tiles the sample axis, one column per thread; grid.y tiles the lines into strips.  A
+// thread keeps its sample bracket and the eight tie values blended along the sample axis; the line bracket is wave-uniform.
+// DIRECT: every valid pixel's five adds go to global memory.  Otherwise three stages:
+//   (a) while a thread walking down its column stays in one bin it keeps (bin, n, Su, Sv, Ss, Sq) in registers;
+//   (b) on a bin change the run goes to the workgroup's direct-mapped LDS table: the slot's tag is claimed with a compare-and-swap,
+//       the sums are added with LDS 64-bit adds; a slot held by another bin sends the run straight to global memory;
+//   (c) at the end every occupied slot is added to global memory.
+// Global adds are device-scope and return nothing; two's-complement addition makes the signed sums right.
+// Measured on 20000 x 20000 complex128 (profiles/grid_bench.json; ms staged / DIRECT): bins of 0.1 degree 3.35 / 429, of 0.01 degree
+// 3.73 / 131 (k_ancillary_model in the same run: 3.30); bins smaller than a pixel, 4000 x 4000: 2.40 / 2.30, where every pixel's five
+// adds reach global memory either way: 3.4e10 64-bit adds per second.
+template <typename Src, bool DIRECT>
+__global__ __launch_bounds__(256) void k_wind_grid(const Src src, const unsigned char *__restrict__ keep, long long lines, long long samples,
+                                                   const LonLat g, const GridTies tp, long long lines_per_block,
+                                                   unsigned long long *__restrict__ sums)
+{
+    constexpr int SLOTS = DIRECT ? 1 : XSW_GRID_SLOTS;
+    __shared__ int tag[SLOTS];
+    __shared__ unsigned long long tab[5][SLOTS];
+    const long long plane = (long long)g.n_lat * g.n_lon;
+    if constexpr (!DIRECT) {
+        for (int t = threadIdx.x; t < SLOTS; t += 256) {
+            tag[t] = -1;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) tab[k][t] = 0;
+        }
+        __syncthreads();
+    }
+    const auto to_global = [&](int bin, const unsigned long long (&s)[5]) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) atomicAdd(sums + k * plane + bin, s[k]);
+    };
+    const auto to_table = [&](int bin, const unsigned long long (&s)[5]) {
+        const unsigned slot = (((unsigned)bin * 2654435761u) >> 16) & (SLOTS - 1);
+        const int old = atomicCAS(&tag[slot], -1, bin);
+        if (old == -1 || old == bin) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) atomicAdd(&tab[k][slot], s[k]);
+        } else {
+            to_global(bin, s);
+        }
+    };
+
+    const long long col = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (col < samples) {  // (no return: the barriers around the table are the whole workgroup's)
+        const long long l0 = (long long)blockIdx.y * lines_per_block;
+        const long long l1 = l0 + lines_per_block < lines ? l0 + lines_per_block : lines;
+        const int j0 = min(max(tp.sj0[col], 0), tp.ns - 1), j1 = min(j0 + 1, tp.ns - 1);
+        const double ts = tp.st[col], ws0 = 1.0 - ts, ws1 = ts;
+        const double dn_lon = (double)g.n_lon, dn_lat = (double)g.n_lat;
+        int tie_cur = -1;
+        TieRows q;
+        int cur = -1;  // (a): the run's bin, none yet
+        unsigned long long acc[5] = {0, 0, 0, 0, 0};
+        for (long long l = l0; l < l1; l += XSW_GRID_LINES) {
+            Px x[XSW_GRID_LINES];
+#pragma unroll
+            for (int k = 0; k < XSW_GRID_LINES; ++k) {
+                x[k] = Px{0.0, 0.0, false};
+                if (l + k < l1) {
+                    const long long i = (l + k) * samples + col;
+                    x[k] = src.fetch(i);
+                    if (keep) x[k].ok = x[k].ok && keep[i] != 0;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < XSW_GRID_LINES; ++k) {
+                if (l + k >= l1) break;
+                const int i0 = min(max(tp.li0[l + k], 0), tp.nl - 1);
+                const double tl = tp.lt[l + k];
+                if (i0 != tie_cur) {
+                    q = tie_rows(tp.tlon, tp.tlat, tp.tcos, tp.tsin, i0, min(i0 + 1, tp.nl - 1), j0, j1, tp.ns, ws0, ws1);
+                    tie_cur = i0;
+                }
+                const TiePoint p = tie_point(q, 1.0 - tl, tl);
+                const double re = x[k].a, im = x[k].b;
+                const double qq = re * re + im * im, sp = sqrt(qq);
+                const double u = -(re * p.ch + im * p.sh), v = -(im * p.ch - re * p.sh);
+                double gx = (p.lon - g.lon0) / g.dlon;
+                const double gy = (p.lat - g.lat0) / g.dlat;
+                bool inside = gy >= 0.0 && gy < dn_lat;
+                if (g.periodic) {
+                    gx = gx - floor(gx / dn_lon) * dn_lon;
+                    if (!(gx >= 0.0) || gx >= dn_lon) gx = 0.0;  // a rounding's width from a whole number of turns: bin 0
+                } else {
+                    inside = inside && gx >= 0.0 && gx < dn_lon;
+                }
+                if (!(x[k].ok && inside && !(u != u) && !(v != v) && qq < 65536.0)) continue;
+                const int bi = min((int)floor(gx), g.n_lon - 1), bj = min((int)floor(gy), g.n_lat - 1);  // inside [0, n) already: never trusted
+                const int bin = bj * g.n_lon + bi;
+                const unsigned long long a[5] = {1ull, fixed_point(u, 16777216.0), fixed_point(v, 16777216.0), fixed_point(sp, 16777216.0),
+                                                 fixed_point(qq, 65536.0)};
+                if constexpr (DIRECT) {
+                    to_global(bin, a);
+                } else {
+                    if (bin != cur) {
+                        if (cur >= 0) to_table(cur, acc);
+                        cur = bin;
+#pragma unroll
+                        for (int m = 0; m < 5; ++m) acc[m] = 0;
+                    }
+#pragma unroll
+                    for (int m = 0; m < 5; ++m) acc[m] += a[m];
+                }
+            }
+        }
+        if constexpr (!DIRECT)
+            if (cur >= 0) to_table(cur, acc);
+    }
+    if constexpr (!DIRECT) {
+        __syncthreads();
+        for (int t = threadIdx.x; t < SLOTS; t += 256) {  // (c)
+            const int bin = tag[t];
+            if (bin < 0) continue;
+            const unsigned long long s[5] = {tab[0][t], tab[1][t], tab[2][t], tab[3][t], tab[4][t]};
+            to_global(bin, s);
+        }
+    }
+}
+
+template <typename Src>
+static void launch_grid(hipStream_t stream, int path, const Src &src, const void *keep, long long lines, long long samples, const LonLat &g,
+                        const GridTies &tp, int64_t *sums)
+{
+    const Strips s = strip_grid(lines, samples);
+    const long long lpb = std::max<long long>(s.rows_per_block, XSW_GRID_MIN_LINES);
+    const dim3 grid((unsigned)s.gx, (unsigned)((lines + lpb - 1) / lpb));  // no more strips than strip_grid's: at most 65535
+    if (path == GRID_DIRECT)
+        hipLaunchKernelGGL((k_wind_grid<Src, true>), grid, dim3(256), 0, stream, src, (const unsigned char *)keep, lines, samples, g, tp, lpb,
+                           (unsigned long long *)sums);
+    else
+        hipLaunchKernelGGL((k_wind_grid<Src, false>), grid, dim3(256), 0, stream, src, (const unsigned char *)keep, lines, samples, g, tp, lpb,
+                           (unsigned long long *)sums);
+}
+
 }  // namespace
+
+extern "C" int xsw_wind_grid(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, int32_t src_kind, const void *src, const uint8_t *keep,
+                             int32_t n_tie_lines, int32_t n_tie_samples, const double *tie_lon, const double *tie_lat, const double *tie_cos,
+                             const double *tie_sin, const int32_t *line_first, const double *line_t, const int32_t *sample_first,
+                             const double *sample_t, double lon0, double dlon, int32_t n_lon, int32_t periodic, double lat0, double dlat,
+                             int32_t n_lat, int64_t *sums)
+{
+    if (!c) return XSW_EINVAL;
+    if (!src) return fail(c, XSW_EINVAL, "wind_grid: no source");
+    if (!sums) return fail(c, XSW_EINVAL, "wind_grid: no sums");
+    if (src_kind != XSW_CELLS_C128 && src_kind != XSW_CELLS_C64 && src_kind != XSW_CELLS_CODES)
+        return fail(c, XSW_EINVAL, "wind_grid: src_kind must be XSW_CELLS_C128, XSW_CELLS_C64 or XSW_CELLS_CODES");
+    if (src_kind == XSW_CELLS_CODES && !c->have_co) return fail(c, XSW_ENOLUT, "wind_grid: co-pol codes given but no co-pol LUT on this context");
+    if (!tie_lon || !tie_lat || !tie_cos || !tie_sin || !line_first || !line_t || !sample_first || !sample_t || n_tie_lines < 1 || n_tie_samples < 1)
+        return fail(c, XSW_EINVAL, "wind_grid: tie points are required: their four grids, both brackets and one point or more per axis");
+    if (lines < 1 || samples < 1) return fail(c, XSW_EINVAL, "wind_grid: the raster must have one line and one sample or more");
+    if (int rc = check_dims(c, "wind_grid", lines, samples)) return rc;
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
+    if (!std::isfinite(lon0) || !std::isfinite(lat0) || !std::isfinite(dlon) || !std::isfinite(dlat) || !(dlon > 0.0) || dlat == 0.0)
+        return fail(c, XSW_EINVAL, "wind_grid: the grid needs finite edges, dlon > 0 and a finite non-zero dlat");
+    if (n_lon < 1 || n_lat < 1 || (int64_t)n_lon * n_lat > 0x7fffffffLL)
+        return fail(c, XSW_EINVAL, "wind_grid: n_lon and n_lat must be 1 or more and n_lon * n_lat must fit int32, not %d x %d", (int)n_lon, (int)n_lat);
+    if (periodic != 0 && periodic != 1) return fail(c, XSW_EINVAL, "wind_grid: periodic must be 0 or 1");
+    bool bad_env;
+    const int path = grid_path(bad_env);
+    if (bad_env) return fail(c, XSW_EINVAL, "wind_grid: XSW_GRID_PATH must be direct or lds");
+    const size_t npx = (size_t)lines * samples, ties = (size_t)n_tie_lines * n_tie_samples * 8;
+    const size_t elem = src_kind == XSW_CELLS_C128 ? 16 : src_kind == XSW_CELLS_C64 ? 8 : 4;
+    Buf b[11] = {{src, nullptr, npx * elem}, in_buf(keep, npx), {tie_lon, nullptr, ties}, {tie_lat, nullptr, ties}, {tie_cos, nullptr, ties},
+                 {tie_sin, nullptr, ties}, {line_first, nullptr, (size_t)lines * 4}, {line_t, nullptr, (size_t)lines * 8},
+                 {sample_first, nullptr, (size_t)samples * 4}, {sample_t, nullptr, (size_t)samples * 8},
+                 {sums, sums, (size_t)n_lon * n_lat * 40}};  // copied up, added to, copied down
+    const LonLat g{lon0, dlon, lat0, dlat, (int)n_lon, (int)n_lat, (int)periodic};
+    return run(c, mem, b, [&](Buf (&x)[11]) {
+        GridTies tp;
+        tp.tlon = (const double *)x[2].dev; tp.tlat = (const double *)x[3].dev; tp.tcos = (const double *)x[4].dev; tp.tsin = (const double *)x[5].dev;
+        tp.li0 = (const int *)x[6].dev; tp.lt = (const double *)x[7].dev; tp.sj0 = (const int *)x[8].dev; tp.st = (const double *)x[9].dev;
+        tp.nl = n_tie_lines; tp.ns = n_tie_samples;
+        int64_t *out = (int64_t *)x[10].dev;
+        if (src_kind == XSW_CELLS_C128) { SrcC128 s; s.p = (const double2 *)x[0].dev; launch_grid(c->stream, path, s, x[1].dev, lines, samples, g, tp, out); }
+        else if (src_kind == XSW_CELLS_C64) { SrcC64 s; s.p = (const float2 *)x[0].dev; launch_grid(c->stream, path, s, x[1].dev, lines, samples, g, tp, out); }
+        else {
+            SrcCodes s;
+            s.p = (const unsigned *)x[0].dev; s.sol = c->T.sol; s.plane = (long long)c->T.n_w * c->T.n_phi;
+            launch_grid(c->stream, path, s, x[1].dev, lines, samples, g, tp, out);
+        }
+    }, "wind_grid");
+}
 
 extern "C" int xsw_wind_cells(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, int32_t src_kind, const void *src, const uint8_t *keep,
                               int32_t cell_lines, int32_t cell_samples, int32_t n_tie_lines, int32_t n_tie_samples, const double *tie_lon,

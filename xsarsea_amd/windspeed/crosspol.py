@@ -150,6 +150,13 @@ class CopolCodes:
         from .. import cells as _cells
         return _cells.codes_cells(self.codes, self.lut_co, cell, tie_points=tie_points, line=line, sample=sample, keep=keep)
 
+    def grid(self, tie_points, *, lon, lat, line=None, sample=None, keep=None, into=None):
+        """`xsarsea_amd.wind_grid(self.wind(), tie_points, lon=..., lat=..., ...)` from the stored codes: the co-pol wind binned
+        on a regular longitude / latitude grid (`WindGrid`).  The pass reads the 4-byte codes and expands nothing; the result
+        equals that of the complex128 expansion bit for bit.  Arguments and refusals as `wind_grid`."""
+        from .. import grid as _grid
+        return _grid.codes_grid(self.codes, self.lut_co, tie_points, lon=lon, lat=lat, line=line, sample=sample, keep=keep, into=into)
+
     def dual(self, sigma0_dual, dsig_cr=0.1, model=None, dual_select=True, codes=False, **kwargs):
         """`wind_dual`, the second element of `invert_from_model(inc, sigma0, sigma0_dual, model=(co, model), dsig_cr=...)`, bit
         for bit, from the stored co-pol codes.  model: the cross-pol model; **kwargs go to its `to_lut`.  dual_select=False:
