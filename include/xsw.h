@@ -935,6 +935,47 @@ int xsw_wind_grid(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, int
                   const double *sample_t, double lon0, double dlon, int32_t n_lon, int32_t periodic, double lat0, double dlat,
                   int32_t n_lat, int64_t *sums);
 
+/* ---- calibration: sigma0, NESZ, incidence and a validity mask from a product's digital numbers (xsarsea_amd.calibrate), the way
+ * IN to device memory: 2 bytes per pixel and a few kilobytes of annotation instead of 4 bytes per pixel and raster.  Additive to
+ * XSW_VERSION 4; conventions as above.
+ *
+ * A table is an annotation grid values[n_lines][n_samples] (float64) with the bracket of every raster line and sample between its
+ * nodes, prepared by the caller exactly as for xsw_ancillary_model: i0 = line_first[l], i1 = min(i0 + 1, n_lines - 1), weights
+ * wl = (1 - line_t[l], line_t[l]); j0, j1, ws likewise from sample_first / sample_t (indices are clamped into range, never
+ * trusted).  Every table has its OWN brackets.  A NULL table pointer, or one whose `values` is NULL, means the table is absent.
+ * Its value at pixel (l, s), every operation float64 and rounded once:
+ *   f(l, s) = wl0 * (ws0 * f[i0][j0] + ws1 * f[i0][j1]) + wl1 * (ws0 * f[i1][j0] + ws1 * f[i1][j1])
+ * (two nodes at neighbouring integer coordinates s, s + 1 therefore state a jump exactly: pixel s reads node s alone, pixel
+ * s + 1 the next one).
+ *
+ * dn: the lines x samples digital numbers, uint16 (XSW_DN_U16) or float32 (XSW_DN_F32).  Per pixel, every operation float64 and
+ * rounded once, in this order:
+ *   1. A from sigma0_lut and, where given, Nr from noise_range, Na from noise_azimuth, inc from incidence, each by f above
+ *   2. N = Nr * Na;  Nr or Na alone when only one is given;  0.0 when neither is
+ *   3. d = (double)dn,  q = d * d,  g = 1.0 / (A * A)
+ *   4. nesz = N * g,  sigma0 = (q - N) * g          (one division per pixel; DN**2 / A**2 - N / A**2 in xsar's words)
+ *   5. use_fill != 0 and dn == fill (uint16: as integers, fill a whole number in 0 .. 65535; float32: compared as float32
+ *      against (float)fill):  sigma0 = NaN;  nesz and incidence are still written
+ *   6. valid = 1 iff the pixel is not fill and sigma0 > 0, else 0   (uint8)
+ *   7. sigma0, nesz, incidence rounded once to out_dtype (XSW_F32 or XSW_F64)
+ * Every output pointer may be NULL: it is not computed and never written; out_incidence needs the incidence table.
+ * dn == NULL with the incidence table alone and out_incidence alone is the table at every pixel (any annotation grid: incidence,
+ * elevation, ground heading).  Any other combination with dn == NULL, and dn without sigma0_lut, is XSW_EINVAL, as are a bad
+ * dtype, mem or fill and a present table with a NULL bracket or an empty axis; a refused call writes no output.
+ * One streaming pass (k_calibrate): 2 B (4 B) read per pixel, 4 B (8 B) written per float raster, the tables stay in cache. */
+enum { XSW_DN_U16 = 0, XSW_DN_F32 = 1 };
+typedef struct xsw_table {
+    int32_t n_lines, n_samples;
+    const double *values;        /* [n_lines][n_samples]; NULL: the table is absent */
+    const int32_t *line_first;   /* [lines] */
+    const double *line_t;        /* [lines] */
+    const int32_t *sample_first; /* [samples] */
+    const double *sample_t;      /* [samples] */
+} xsw_table;
+int xsw_calibrate(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, int32_t dn_dtype, int32_t out_dtype, const void *dn,
+                  const xsw_table *sigma0_lut, const xsw_table *noise_range, const xsw_table *noise_azimuth, const xsw_table *incidence,
+                  int32_t use_fill, double fill, void *out_sigma0, void *out_nesz, void *out_incidence, uint8_t *out_valid);
+
 #ifdef __cplusplus
 }
 #endif

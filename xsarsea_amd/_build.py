@@ -12,6 +12,7 @@ SRC_GRAD = os.path.join(CSRC, "xsw_gradients.hip")  # wind-streak direction hist
 SRC_STREAKS = os.path.join(CSRC, "xsw_streaks.hip")  # histograms -> streak directions -> a-priori wind raster (xsarsea_amd.streaks)
 SRC_ANCILLARY = os.path.join(CSRC, "xsw_ancillary.hip")  # model grid + tie points -> a-priori wind raster (xsarsea_amd.ancillary)
 SRC_CELLS = os.path.join(CSRC, "xsw_cells.hip")  # wind / real raster -> statistics on a product grid (xsarsea_amd.cells)
+SRC_CALIBRATE = os.path.join(CSRC, "xsw_calibrate.hip")  # digital numbers + annotation tables -> sigma0, nesz, incidence, valid (xsarsea_amd.calibrate)
 DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".hpp"))] + [os.path.join(REPO, "include", "xsw.h")]
 LIB = os.environ.get("XSW_LIB") or os.path.join(HERE, "libxsw.so")  # XSW_LIB: experiment builds only
 OBJDIR = os.path.join(REPO, "build", "obj")
@@ -33,8 +34,8 @@ def needs_build():
 
 
 def build(force=False, verbose=False):
-    """Compile csrc/*.hip -> libxsw.so for gfx950: nine translation units side by side (xsw.hip, xsw_invert_tu.hip once per
-    dtype pair, xsw_gradients.hip, xsw_streaks.hip, xsw_ancillary.hip, xsw_cells.hip), then one link; skipped, unless `force`, when libxsw.so is the newest file.
+    """Compile csrc/*.hip -> libxsw.so for gfx950: ten translation units side by side (xsw.hip, xsw_invert_tu.hip once per
+    dtype pair, xsw_gradients.hip, xsw_streaks.hip, xsw_ancillary.hip, xsw_cells.hip, xsw_calibrate.hip), then one link; skipped, unless `force`, when libxsw.so is the newest file.
     -ffp-contract=off: the kernels decide exact float64 orderings; FMAs appear only where written explicitly."""
     if not force and not needs_build():
         return LIB
@@ -50,6 +51,7 @@ def build(force=False, verbose=False):
     jobs += [(SRC_STREAKS, os.path.join(OBJDIR, f"{tag}_streaks.o"), [])]
     jobs += [(SRC_ANCILLARY, os.path.join(OBJDIR, f"{tag}_ancillary.o"), [])]
     jobs += [(SRC_CELLS, os.path.join(OBJDIR, f"{tag}_cells.o"), [])]
+    jobs += [(SRC_CALIBRATE, os.path.join(OBJDIR, f"{tag}_calibrate.o"), [])]
     procs = []
     for src, obj, defs in jobs:
         cmd = common + defs + ["-c", src, "-o", obj]

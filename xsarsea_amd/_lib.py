@@ -50,7 +50,7 @@ EXPORTS = (
     "xsw_grad_r2_sqrt", "xsw_grad_local_sqrt", "xsw_grad_smooth", "xsw_grad_mean", "xsw_grad_filter",
     "xsw_grad_hist_masked", "xsw_grad_keep_f64", "xsw_grad_keep_u8",
     "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary", "xsw_ancillary_model",
-    "xsw_wind_cells", "xsw_raster_cells", "xsw_wind_grid",
+    "xsw_wind_cells", "xsw_raster_cells", "xsw_wind_grid", "xsw_calibrate",
     "xsw_cross_from_codes", "xsw_cost_from_codes", "xsw_cost_cr_from_codes",
     "xsw_uncertainty_from_codes", "xsw_uncertainty_cr_from_codes", "xsw_joint_from_codes",
     "xsw_uncertainty_joint_from_codes",
@@ -118,6 +118,7 @@ RASTER_ENTRIES = {
 }
 assert list(RASTER_ENTRIES) == [n for n in EXPORTS if n.startswith(("xsw_grad_", "xsw_streaks_", "xsw_ancillary_")) or n.endswith(("_cells", "_grid"))]
 CELLS_C128, CELLS_C64, CELLS_CODES = 0, 1, 2  # XSW_CELLS_* (include/xsw.h): the source kinds of xsw_wind_cells
+DN_U16, DN_F32 = 0, 1  # XSW_DN_* (include/xsw.h): the digital numbers of xsw_calibrate
 # letter -> (ctypes type, conversion the wrapper applies: ctypes alone refuses numpy scalars)
 _SIG = {"l": (ctypes.c_int64, int), "i": (ctypes.c_int32, int), "d": (ctypes.c_double, float), "p": (ctypes.c_void_p, lambda a: a)}
 
@@ -166,6 +167,12 @@ class InvertArgs(ctypes.Structure):
                 ("out_co", ctypes.c_void_p), ("out_cr", ctypes.c_void_p), ("out_idx", ctypes.c_void_p),
                 ("out_code_co", ctypes.c_void_p), ("out_code_cr", ctypes.c_void_p),
                 ("stage", ctypes.c_void_p), ("stage_user", ctypes.c_void_p)]
+
+
+class Table(ctypes.Structure):
+    """xsw_table (include/xsw.h): an annotation grid of xsw_calibrate with the brackets of the raster's lines and samples."""
+    _fields_ = [("n_lines", ctypes.c_int32), ("n_samples", ctypes.c_int32), ("values", ctypes.c_void_p), ("line_first", ctypes.c_void_p),
+                ("line_t", ctypes.c_void_p), ("sample_first", ctypes.c_void_p), ("sample_t", ctypes.c_void_p)]
 
 
 #: int stage(void *user, int32 which, int64 px0, int64 npx, void *dst)  (xsw_invert_args.stage)
@@ -278,6 +285,8 @@ def load():
         lib.xsw_dsig.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_dsig_flat.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] * 4
         lib.xsw_dsig_wspd.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 3
+        lib.xsw_calibrate.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int32] * 3 + [ctypes.c_void_p] + \
+            [ctypes.POINTER(Table)] * 4 + [ctypes.c_int32, ctypes.c_double] + [ctypes.c_void_p] * 4
         lib.xsw_host_alloc.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
         lib.xsw_host_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         lib.xsw_set_host_threads.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -743,6 +752,16 @@ class Context:
         if want_codes:
             return out_co, out_cr, idx, codes
         return out_co, out_cr, idx
+
+    @_locked
+    def calibrate_raw(self, lines, samples, mem, dn_dtype, out_dtype, dn, sigma0_lut, noise_range, noise_azimuth, incidence, fill, out_sigma0,
+                      out_nesz, out_incidence, out_valid):
+        """Thin call of xsw_calibrate (pointers are ints or None).  A table is None or (n_lines, n_samples, values, line_first, line_t,
+        sample_first, sample_t) with the five arrays as addresses; fill is a number, or None for no fill value."""
+        tabs = [None if t is None else Table(int(t[0]), int(t[1]), *t[2:]) for t in (sigma0_lut, noise_range, noise_azimuth, incidence)]
+        self._check(self._lib.xsw_calibrate(self._h, int(lines), int(samples), mem, dn_dtype, out_dtype, dn,
+                                            *[None if t is None else ctypes.byref(t) for t in tabs], int(fill is not None),
+                                            0.0 if fill is None else float(fill), out_sigma0, out_nesz, out_incidence, out_valid), "xsw_calibrate")
 
     @_locked
     def nesz_flatten_raw(self, lines, samples, dtype, mem, noise_ptr, inc_ptr, out_ptr):
