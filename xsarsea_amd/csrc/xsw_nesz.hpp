@@ -131,6 +131,8 @@ __global__ __launch_bounds__(1024) void k_nesz_center(const double *__restrict__
 // log10 / exp10 for the arguments of this kernel (positive normal finite doubles; |t| < 300), ~1e-15 relative: frexp + atanh
 // series, and 2^k * exp(g) with a degree-13 Taylor polynomial.  About 55 float64 instructions for the pair instead of the
 // ~120 of the library calls, which bound the float64 passes (one of each per pixel); anything else goes to the library.
+// tests/test_gpu_nesz_pair.py holds the pair (and the float32 rasters' v_log_f32 / v_exp_f32) to exact arithmetic at mantissas on
+// both sides of the fold and exponents over the whole range, within bounds built from these statements (tests/nesz_ref.py).
 __device__ __forceinline__ double nesz_log10(double v)
 {
     if (!(v >= 2.2250738585072014e-308 && v <= 1.7976931348623157e308)) return log10(v);  // 0, negative, denormal, inf, NaN
@@ -205,7 +207,12 @@ __global__ __launch_bounds__(XSW_NESZ_THREADS) void k_nesz_fit(const T *__restri
     auto take = [&](int j, double v, double m, double x) {
         if (v != v) v = m;
         // NaN for v < 0 or NaN, -inf for 0: dropped like the reference's isfinite mask
-        const double y = F32 ? (double)(3.0102999566398120f * __builtin_amdgcn_logf((float)v)) : 10.0 * nesz_log10(v);
+        // v_log_f32 takes a denormal argument for zero (-inf: the line would lose the sample), numpy's float32 log10 does not:
+        // such an argument is scaled into the normal range first, exactly; every other one keeps its bits (l - 0.0f == l)
+        const float vf = (float)v;
+        const bool tiny = vf < 1.17549435e-38f;  // (0 and the negative values too: -inf and NaN either way)
+        const double y = F32 ? (double)(3.0102999566398120f * (__builtin_amdgcn_logf(tiny ? vf * 16777216.0f : vf) - (tiny ? 24.0f : 0.0f)))
+                             : 10.0 * nesz_log10(v);
         // polyfit sees x[ok]: a NaN abscissa (column without valid incidence) poisons the fit there; here too
         if (isfinite(y)) { n[j] += 1.0; sx[j] += x; sy[j] += y; sxx[j] += x * x; sxy[j] += x * y; }
     };
