@@ -935,6 +935,61 @@ int xsw_wind_grid(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, int
                   const double *sample_t, double lon0, double dlon, int32_t n_lon, int32_t periodic, double lat0, double dlat,
                   int32_t n_lat, int64_t *sums);
 
+/* ---- wind around a given centre (xsarsea_amd.polar): the storm-centred description of a cyclone scene -- azimuthal means, the
+ * largest speed, the radial and tangential components -- binned in rings and sectors, order-free in fixed point as
+ * xsw_wind_grid.  Additive to XSW_VERSION 4; conventions as above.
+ *
+ * Source, keep, tie points and per-pixel brackets: exactly as xsw_wind_grid.  The bins: n_r rings of width dr_km (> 0) around
+ * the centre (lon_c, lat_c: finite, |lat_c| <= 89), ring k covering [k * dr_km, (k + 1) * dr_km); each ring has n_theta sectors
+ * counted clockwise from north, sector 0 starting at north; n_theta is a multiple of 4 from 4 to 360, so that the quadrant
+ * borders are sector borders; n_r >= 1 and n_r * n_theta fits int32.  cos_lat_c, sin_lat_c: cos and sin of lat_c, by the caller.
+ * sector_sin, sector_cos [n_theta / 4 + 1]: sin and cos of j * 90 / (n_theta / 4) degrees, j = 0 .. n_theta / 4, by the caller:
+ * the device calls no trigonometric function.  sums: int64 [6][n_r][n_theta], the planes n, Ss, Sq, Sr, St, Mx.  The entry
+ * ACCUMULATES into sums: the first five planes are added to, Mx is raised to the maximum (unsigned 64-bit; the value is never
+ * negative); the caller zeroes them (XSW_MEM_HOST: sums is copied up, accumulated into and copied down).
+ *
+ * Per pixel, every operation float64 and rounded once, in this order, with R = 6371.0088 (km), D = 0.017453292519943295
+ * (pi / 180) and K = R * D (one rounding):
+ *   0. once per call:  lon_c = lon_c - 360 * rint(lon_c / 360)   (a centre given as -179.6 or as 180.4 is the same centre)
+ *   1. (lon, lat, ch, sh): steps 1-2 of xsw_ancillary_model, unchanged (the same device code)
+ *   2. q, sp, u, v: step 2 of xsw_wind_grid, unchanged
+ *   3. dl = lon - lon_c;  dl = dl - 360 * rint(dl / 360)  (halves to even);  dy = (lat - lat_c) * D;  h = 0.5 * dy
+ *      m = (cos_lat_c - sin_lat_c * h) - (0.5 * cos_lat_c) * (h * h)      (cos of the mid-latitude to second order)
+ *      x = (K * dl) * m  (east, km);   y = R * dy  (north, km)
+ *   4. rr = x * x + y * y,  r = sqrt(rr),  kr = floor(r / dr_km);  the pixel is dropped unless kr < n_r
+ *   5. the quadrant Q and the pair (a, b), from signs alone:
+ *        Q = 0 if x >= 0 and y > 0:  (a, b) = (x, y)         Q = 1 if x > 0 and y <= 0:  (a, b) = (-y, x)
+ *        Q = 2 if x <= 0 and y < 0:  (a, b) = (-x, -y)       Q = 3 if x < 0 and y >= 0:  (a, b) = (y, -x)
+ *        x = y = 0:  Q = 0 and sector 0
+ *      with mq = n_theta / 4:  lo = 0, hi = mq;  while hi - lo > 1:  mid = (lo + hi) >> 1;
+ *        if a * sector_cos[mid] >= b * sector_sin[mid]:  lo = mid  else  hi = mid
+ *      sector = Q * mq + lo
+ *   6. vr = (u * x + v * y) / r  (outward),  vt = (v * x - u * y) / r  (positive counter-clockwise);  both 0 where r == 0
+ *   7. the pixel is dropped unless the source is valid, keep is non-zero, u and v are not NaN and q < 65536
+ *   8. bin (kr, sector):  n += 1,  Ss += Q24(sp),  Sq += Q16(q),  Sr += Q24(vr),  St += Q24(vt),  Mx = max(Mx, Q24(sp))
+ *      with Q24 and Q16 as in xsw_wind_grid
+ * Integer addition and the maximum have no order: what xsw_wind_grid says of launches, tiles, scenes and devices holds here,
+ * with "planes 0-4 added, plane 5 the maximum" as the merge.  tests/polar_ref.py restates the entry in numpy.
+ *
+ * The chart.  (x, y) is the equirectangular chart at the mid-latitude, its cosine expanded to second order around lat_c; against
+ * the great-circle distance and initial bearing it is off by less than 2e-4 of the distance and 1.5 degrees of bearing out to
+ * 300 km for |lat_c| <= 35 (tests/test_polar_cpu.py measures it; DESIGN has the figures).
+ *
+ * Overflow.  |vr|, |vt| <= sp up to rounding, so every addend is below 2**33 in magnitude (step 7's last condition makes this
+ * unconditional) and a bin is exact up to 2**30 pixels over all accumulated calls, as in xsw_wind_grid.  Not checked at run time.
+ *
+ * Finish (not part of the entry: elementwise on the bins, in the caller's float64), with nd = (double)n:
+ *   wspd = ((double)Ss / nd) * 2**-24, vr and vt (from Sr, St) likewise;  wspd_std from Ss and Sq as in xsw_wind_grid;
+ *   vmax = (double)Mx * 2**-24;  n == 0 gives NaN everywhere.
+ *
+ * Environment XSW_GRID_PATH = direct | lds, read at every call (any other value is refused), with the meaning it has for
+ * xsw_wind_grid.  Both give the same bits. */
+int xsw_wind_polar(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, int32_t src_kind, const void *src, const uint8_t *keep,
+                   int32_t n_tie_lines, int32_t n_tie_samples, const double *tie_lon, const double *tie_lat, const double *tie_cos,
+                   const double *tie_sin, const int32_t *line_first, const double *line_t, const int32_t *sample_first,
+                   const double *sample_t, double lon_c, double lat_c, double cos_lat_c, double sin_lat_c, double dr_km, int32_t n_r,
+                   int32_t n_theta, const double *sector_sin, const double *sector_cos, int64_t *sums);
+
 /* ---- calibration: sigma0, NESZ, incidence and a validity mask from a product's digital numbers (xsarsea_amd.calibrate), the way
  * IN to device memory: 2 bytes per pixel and a few kilobytes of annotation instead of 4 bytes per pixel and raster.  Additive to
  * XSW_VERSION 4; conventions as above.

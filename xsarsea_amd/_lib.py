@@ -50,7 +50,7 @@ EXPORTS = (
     "xsw_grad_r2_sqrt", "xsw_grad_local_sqrt", "xsw_grad_smooth", "xsw_grad_mean", "xsw_grad_filter",
     "xsw_grad_hist_masked", "xsw_grad_keep_f64", "xsw_grad_keep_u8",
     "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary", "xsw_ancillary_model",
-    "xsw_wind_cells", "xsw_raster_cells", "xsw_wind_grid", "xsw_calibrate",
+    "xsw_wind_cells", "xsw_raster_cells", "xsw_wind_grid", "xsw_wind_polar", "xsw_calibrate",
     "xsw_cross_from_codes", "xsw_cost_from_codes", "xsw_cost_cr_from_codes",
     "xsw_uncertainty_from_codes", "xsw_uncertainty_cr_from_codes", "xsw_joint_from_codes",
     "xsw_uncertainty_joint_from_codes",
@@ -60,7 +60,7 @@ EXPORTS = (
 )
 
 
-# The raster entries behind xsarsea_amd.gradients, xsarsea_amd.streaks, xsarsea_amd.ancillary, xsarsea_amd.cells and xsarsea_amd.grid: their C signature after the context, one letter per
+# The raster entries behind xsarsea_amd.gradients, xsarsea_amd.streaks, xsarsea_amd.ancillary, xsarsea_amd.cells, xsarsea_amd.grid and xsarsea_amd.polar: their C signature after the context, one letter per
 # argument (l int64, i int32, d double, p pointer: an int address, device or host per `mem`, or None).  `load` sets the argtypes
 # from it and every row becomes a Context method, e.g. `grad_area_raw(lines, samples, factor, dtype, mem, in_ptr, out_ptr)`.
 RASTER_ENTRIES = {
@@ -115,8 +115,13 @@ RASTER_ENTRIES = {
     # co-pol codes (CELLS_*) adds its fixed-point terms to its bin of the longitude / latitude grid: int64 sums [5, n_lat, n_lon],
     # added to, never zeroed; keep may be None, the tie points and the per-pixel brackets are required
     "xsw_wind_grid": "lliippiipppppppp" + "ddiiddi" + "p",
+    # (lines, samples, mem, src_kind, src, keep, n_tie_lines, n_tie_samples, tie_lon, tie_lat, tie_cos, tie_sin, line_first, line_t,
+    # sample_first, sample_t, lon_c, lat_c, cos_lat_c, sin_lat_c, dr_km, n_r, n_theta, sector_sin, sector_cos, sums): the same pixels
+    # binned in n_r rings of dr_km and n_theta sectors around the centre: int64 sums [6, n_r, n_theta], the first five planes added
+    # to, the sixth raised to the maximum, never zeroed; sector_sin / sector_cos: the borders of one quadrant's sectors
+    "xsw_wind_polar": "lliippiipppppppp" + "dddddii" + "pp" + "p",
 }
-assert list(RASTER_ENTRIES) == [n for n in EXPORTS if n.startswith(("xsw_grad_", "xsw_streaks_", "xsw_ancillary_")) or n.endswith(("_cells", "_grid"))]
+assert list(RASTER_ENTRIES) == [n for n in EXPORTS if n.startswith(("xsw_grad_", "xsw_streaks_", "xsw_ancillary_")) or n.endswith(("_cells", "_grid", "_polar"))]
 CELLS_C128, CELLS_C64, CELLS_CODES = 0, 1, 2  # XSW_CELLS_* (include/xsw.h): the source kinds of xsw_wind_cells
 DN_U16, DN_F32 = 0, 1  # XSW_DN_* (include/xsw.h): the digital numbers of xsw_calibrate
 # letter -> (ctypes type, conversion the wrapper applies: ctypes alone refuses numpy scalars)

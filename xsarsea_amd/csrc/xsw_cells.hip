@@ -11,6 +11,8 @@
 //   k_wind_grid<Src, DIRECT>  the same wind sources binned on a regular longitude / latitude grid (xsw_wind_grid,
 //                       xsarsea_amd.grid): every pixel geolocated from the tie points, its terms added to its bin as 64-bit
 //                       integers in fixed point, which have no order; stated and described further down.
+//   k_wind_polar<Src, DIRECT> the same binned in rings and sectors around a given centre (xsw_wind_polar, xsarsea_amd.polar),
+//                       with the radial and tangential components and the bin's largest speed; after k_wind_grid.
 //
 // The order of every sum: pixel p = r * w + c of a cell (w its clipped width) goes to accumulator p mod 256; each accumulator
 // starts at +0.0 and adds its pixels in ascending p, an invalid pixel adding +0.0 (which changes no accumulator: none is ever
@@ -448,6 +450,166 @@ static void launch_grid(hipStream_t stream, int path, const Src &src, const void
                            (unsigned long long *)sums);
 }
 
+// ---- wind around a given centre: rings and sectors on a local chart (xsw_wind_polar; include/xsw.h has the statement).  The
+// sources, the geolocation, the walk down a column and the three stages are k_wind_grid's; a pixel adds five integers to its bin
+// and raises a sixth, the bin's largest speed, by an unsigned 64-bit maximum (the value is never negative), which has no order
+// either.  No trigonometric call: the sector is found by comparing against a host table of sin / cos of the sector borders of
+// one quadrant, kept in LDS.
+#ifndef XSW_POLAR_MAX_SECTORS
+#define XSW_POLAR_MAX_SECTORS 360  // the LDS table holds sin and cos of XSW_POLAR_MAX_SECTORS / 4 + 1 borders
+#endif
+static_assert(XSW_POLAR_MAX_SECTORS % 4 == 0 && XSW_POLAR_MAX_SECTORS >= 4, "quadrant borders are sector borders");
+
+struct Polar {
+    double lon_c, lat_c, cos_c, sin_c, dr_km;
+    int n_r, n_theta;
+};
+
+template <typename Src, bool DIRECT>
+__global__ __launch_bounds__(256) void k_wind_polar(const Src src, const unsigned char *__restrict__ keep, long long lines, long long samples,
+                                                    const Polar g, const double *__restrict__ sector_sin, const double *__restrict__ sector_cos,
+                                                    const GridTies tp, long long lines_per_block, unsigned long long *__restrict__ sums)
+{
+    constexpr int SLOTS = DIRECT ? 1 : XSW_GRID_SLOTS, BORDERS = XSW_POLAR_MAX_SECTORS / 4 + 1;
+    constexpr double D2R = 0.017453292519943295, R_KM = 6371.0088, KX = R_KM * D2R;
+    __shared__ int tag[SLOTS];
+    __shared__ unsigned long long tab[6][SLOTS];
+    __shared__ double bsin[BORDERS], bcos[BORDERS];
+    const long long plane = (long long)g.n_r * g.n_theta;
+    const int mq = min(g.n_theta / 4, BORDERS - 1);  // (the entry refuses more sectors: never trusted)
+    for (int t = threadIdx.x; t <= mq; t += 256) {
+        bsin[t] = sector_sin[t];
+        bcos[t] = sector_cos[t];
+    }
+    if constexpr (!DIRECT) {
+        for (int t = threadIdx.x; t < SLOTS; t += 256) {
+            tag[t] = -1;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) tab[k][t] = 0;
+        }
+    }
+    __syncthreads();
+    const auto to_global = [&](int bin, const unsigned long long (&s)[6]) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) atomicAdd(sums + k * plane + bin, s[k]);
+        atomicMax(sums + 5 * plane + bin, s[5]);
+    };
+    const auto to_table = [&](int bin, const unsigned long long (&s)[6]) {
+        const unsigned slot = (((unsigned)bin * 2654435761u) >> 16) & (SLOTS - 1);
+        const int old = atomicCAS(&tag[slot], -1, bin);
+        if (old == -1 || old == bin) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) atomicAdd(&tab[k][slot], s[k]);
+            atomicMax(&tab[5][slot], s[5]);
+        } else {
+            to_global(bin, s);
+        }
+    };
+
+    const long long col = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (col < samples) {  // (no return: the barriers around the table are the whole workgroup's)
+        const long long l0 = (long long)blockIdx.y * lines_per_block;
+        const long long l1 = l0 + lines_per_block < lines ? l0 + lines_per_block : lines;
+        const int j0 = min(max(tp.sj0[col], 0), tp.ns - 1), j1 = min(j0 + 1, tp.ns - 1);
+        const double ts = tp.st[col], ws0 = 1.0 - ts, ws1 = ts;
+        const double dn_r = (double)g.n_r, half_c = 0.5 * g.cos_c;
+        int tie_cur = -1;
+        TieRows q;
+        int cur = -1;  // (a): the run's bin, none yet
+        unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
+        for (long long l = l0; l < l1; l += XSW_GRID_LINES) {
+            Px px[XSW_GRID_LINES];
+#pragma unroll
+            for (int k = 0; k < XSW_GRID_LINES; ++k) {
+                px[k] = Px{0.0, 0.0, false};
+                if (l + k < l1) {
+                    const long long i = (l + k) * samples + col;
+                    px[k] = src.fetch(i);
+                    if (keep) px[k].ok = px[k].ok && keep[i] != 0;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < XSW_GRID_LINES; ++k) {
+                if (l + k >= l1) break;
+                const int i0 = min(max(tp.li0[l + k], 0), tp.nl - 1);
+                const double tl = tp.lt[l + k];
+                if (i0 != tie_cur) {
+                    q = tie_rows(tp.tlon, tp.tlat, tp.tcos, tp.tsin, i0, min(i0 + 1, tp.nl - 1), j0, j1, tp.ns, ws0, ws1);
+                    tie_cur = i0;
+                }
+                const TiePoint p = tie_point(q, 1.0 - tl, tl);
+                const double re = px[k].a, im = px[k].b;
+                const double qq = re * re + im * im, sp = sqrt(qq);
+                const double u = -(re * p.ch + im * p.sh), v = -(im * p.ch - re * p.sh);
+                double dl = p.lon - g.lon_c;
+                dl = dl - 360.0 * __builtin_rint(dl / 360.0);
+                const double dy = (p.lat - g.lat_c) * D2R, h = 0.5 * dy;
+                const double m = (g.cos_c - g.sin_c * h) - half_c * (h * h);
+                const double x = (KX * dl) * m, y = R_KM * dy;
+                const double rr = x * x + y * y, r = sqrt(rr);
+                const double fr = floor(r / g.dr_km);
+                if (!(px[k].ok && fr < dn_r && !(u != u) && !(v != v) && qq < 65536.0)) continue;  // (a NaN radius fails fr < n_r)
+                int quadrant = 0;
+                double a = 0.0, b = 1.0;  // x = y = 0: sector 0
+                if (x >= 0.0 && y > 0.0) { a = x; b = y; }
+                else if (x > 0.0 && y <= 0.0) { quadrant = 1; a = -y; b = x; }
+                else if (x <= 0.0 && y < 0.0) { quadrant = 2; a = -x; b = -y; }
+                else if (x < 0.0 && y >= 0.0) { quadrant = 3; a = y; b = -x; }
+                int lo = 0, hi = mq;
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (a * bcos[mid] >= b * bsin[mid]) lo = mid;
+                    else hi = mid;
+                }
+                const bool centre = r == 0.0;
+                const double vr = centre ? 0.0 : (u * x + v * y) / r, vt = centre ? 0.0 : (v * x - u * y) / r;
+                const int bin = min((int)fr, g.n_r - 1) * g.n_theta + quadrant * mq + lo;  // fr inside [0, n_r) already: never trusted
+                const unsigned long long s24 = fixed_point(sp, 16777216.0);
+                const unsigned long long t[6] = {1ull, s24, fixed_point(qq, 65536.0), fixed_point(vr, 16777216.0), fixed_point(vt, 16777216.0), s24};
+                if constexpr (DIRECT) {
+                    to_global(bin, t);
+                } else {
+                    if (bin != cur) {
+                        if (cur >= 0) to_table(cur, acc);
+                        cur = bin;
+#pragma unroll
+                        for (int n = 0; n < 6; ++n) acc[n] = 0;
+                    }
+#pragma unroll
+                    for (int n = 0; n < 5; ++n) acc[n] += t[n];
+                    acc[5] = acc[5] > t[5] ? acc[5] : t[5];
+                }
+            }
+        }
+        if constexpr (!DIRECT)
+            if (cur >= 0) to_table(cur, acc);
+    }
+    if constexpr (!DIRECT) {
+        __syncthreads();
+        for (int t = threadIdx.x; t < SLOTS; t += 256) {  // (c)
+            const int bin = tag[t];
+            if (bin < 0) continue;
+            const unsigned long long s[6] = {tab[0][t], tab[1][t], tab[2][t], tab[3][t], tab[4][t], tab[5][t]};
+            to_global(bin, s);
+        }
+    }
+}
+
+template <typename Src>
+static void launch_polar(hipStream_t stream, int path, const Src &src, const void *keep, long long lines, long long samples, const Polar &g,
+                         const double *sector_sin, const double *sector_cos, const GridTies &tp, int64_t *sums)
+{
+    const Strips s = strip_grid(lines, samples);
+    const long long lpb = std::max<long long>(s.rows_per_block, XSW_GRID_MIN_LINES);
+    const dim3 grid((unsigned)s.gx, (unsigned)((lines + lpb - 1) / lpb));  // as launch_grid
+    if (path == GRID_DIRECT)
+        hipLaunchKernelGGL((k_wind_polar<Src, true>), grid, dim3(256), 0, stream, src, (const unsigned char *)keep, lines, samples, g, sector_sin,
+                           sector_cos, tp, lpb, (unsigned long long *)sums);
+    else
+        hipLaunchKernelGGL((k_wind_polar<Src, false>), grid, dim3(256), 0, stream, src, (const unsigned char *)keep, lines, samples, g, sector_sin,
+                           sector_cos, tp, lpb, (unsigned long long *)sums);
+}
+
 }  // namespace
 
 extern "C" int xsw_wind_grid(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, int32_t src_kind, const void *src, const uint8_t *keep,
@@ -496,6 +658,58 @@ extern "C" int xsw_wind_grid(xsw_ctx *c, int64_t lines, int64_t samples, int32_t
             launch_grid(c->stream, path, s, x[1].dev, lines, samples, g, tp, out);
         }
     }, "wind_grid");
+}
+
+extern "C" int xsw_wind_polar(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, int32_t src_kind, const void *src, const uint8_t *keep,
+                              int32_t n_tie_lines, int32_t n_tie_samples, const double *tie_lon, const double *tie_lat, const double *tie_cos,
+                              const double *tie_sin, const int32_t *line_first, const double *line_t, const int32_t *sample_first,
+                              const double *sample_t, double lon_c, double lat_c, double cos_lat_c, double sin_lat_c, double dr_km, int32_t n_r,
+                              int32_t n_theta, const double *sector_sin, const double *sector_cos, int64_t *sums)
+{
+    if (!c) return XSW_EINVAL;
+    if (!src) return fail(c, XSW_EINVAL, "wind_polar: no source");
+    if (!sums) return fail(c, XSW_EINVAL, "wind_polar: no sums");
+    if (src_kind != XSW_CELLS_C128 && src_kind != XSW_CELLS_C64 && src_kind != XSW_CELLS_CODES)
+        return fail(c, XSW_EINVAL, "wind_polar: src_kind must be XSW_CELLS_C128, XSW_CELLS_C64 or XSW_CELLS_CODES");
+    if (src_kind == XSW_CELLS_CODES && !c->have_co) return fail(c, XSW_ENOLUT, "wind_polar: co-pol codes given but no co-pol LUT on this context");
+    if (!tie_lon || !tie_lat || !tie_cos || !tie_sin || !line_first || !line_t || !sample_first || !sample_t || n_tie_lines < 1 || n_tie_samples < 1)
+        return fail(c, XSW_EINVAL, "wind_polar: tie points are required: their four grids, both brackets and one point or more per axis");
+    if (lines < 1 || samples < 1) return fail(c, XSW_EINVAL, "wind_polar: the raster must have one line and one sample or more");
+    if (int rc = check_dims(c, "wind_polar", lines, samples)) return rc;
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
+    if (!std::isfinite(lon_c) || !std::isfinite(lat_c) || !(std::fabs(lat_c) <= 89.0))
+        return fail(c, XSW_EINVAL, "wind_polar: the centre needs a finite longitude and a latitude within 89 degrees of the equator");
+    if (!std::isfinite(cos_lat_c) || !std::isfinite(sin_lat_c)) return fail(c, XSW_EINVAL, "wind_polar: cos and sin of the centre's latitude must be finite");
+    if (!std::isfinite(dr_km) || !(dr_km > 0.0)) return fail(c, XSW_EINVAL, "wind_polar: dr_km must be finite and positive");
+    if (n_r < 1 || n_theta < 4 || n_theta % 4 != 0 || n_theta > XSW_POLAR_MAX_SECTORS || (int64_t)n_r * n_theta > 0x7fffffffLL)
+        return fail(c, XSW_EINVAL, "wind_polar: n_r must be 1 or more, n_theta a multiple of 4 from 4 to %d and n_r * n_theta must fit int32, not %d x %d",
+                    XSW_POLAR_MAX_SECTORS, (int)n_r, (int)n_theta);
+    if (!sector_sin || !sector_cos) return fail(c, XSW_EINVAL, "wind_polar: the table of sector borders is required");
+    bool bad_env;
+    const int path = grid_path(bad_env);
+    if (bad_env) return fail(c, XSW_EINVAL, "wind_polar: XSW_GRID_PATH must be direct or lds");
+    const size_t npx = (size_t)lines * samples, ties = (size_t)n_tie_lines * n_tie_samples * 8, borders = (size_t)(n_theta / 4 + 1) * 8;
+    const size_t elem = src_kind == XSW_CELLS_C128 ? 16 : src_kind == XSW_CELLS_C64 ? 8 : 4;
+    Buf b[13] = {{src, nullptr, npx * elem}, in_buf(keep, npx), {tie_lon, nullptr, ties}, {tie_lat, nullptr, ties}, {tie_cos, nullptr, ties},
+                 {tie_sin, nullptr, ties}, {line_first, nullptr, (size_t)lines * 4}, {line_t, nullptr, (size_t)lines * 8},
+                 {sample_first, nullptr, (size_t)samples * 4}, {sample_t, nullptr, (size_t)samples * 8}, {sector_sin, nullptr, borders},
+                 {sector_cos, nullptr, borders}, {sums, sums, (size_t)n_r * n_theta * 48}};  // copied up, accumulated into, copied down
+    const Polar g{lon_c - 360.0 * std::rint(lon_c / 360.0), lat_c, cos_lat_c, sin_lat_c, dr_km, (int)n_r, (int)n_theta};  // step 0
+    return run(c, mem, b, [&](Buf (&x)[13]) {
+        GridTies tp;
+        tp.tlon = (const double *)x[2].dev; tp.tlat = (const double *)x[3].dev; tp.tcos = (const double *)x[4].dev; tp.tsin = (const double *)x[5].dev;
+        tp.li0 = (const int *)x[6].dev; tp.lt = (const double *)x[7].dev; tp.sj0 = (const int *)x[8].dev; tp.st = (const double *)x[9].dev;
+        tp.nl = n_tie_lines; tp.ns = n_tie_samples;
+        const double *ss = (const double *)x[10].dev, *sc = (const double *)x[11].dev;
+        int64_t *out = (int64_t *)x[12].dev;
+        if (src_kind == XSW_CELLS_C128) { SrcC128 s; s.p = (const double2 *)x[0].dev; launch_polar(c->stream, path, s, x[1].dev, lines, samples, g, ss, sc, tp, out); }
+        else if (src_kind == XSW_CELLS_C64) { SrcC64 s; s.p = (const float2 *)x[0].dev; launch_polar(c->stream, path, s, x[1].dev, lines, samples, g, ss, sc, tp, out); }
+        else {
+            SrcCodes s;
+            s.p = (const unsigned *)x[0].dev; s.sol = c->T.sol; s.plane = (long long)c->T.n_w * c->T.n_phi;
+            launch_polar(c->stream, path, s, x[1].dev, lines, samples, g, ss, sc, tp, out);
+        }
+    }, "wind_polar");
 }
 
 extern "C" int xsw_wind_cells(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, int32_t src_kind, const void *src, const uint8_t *keep,

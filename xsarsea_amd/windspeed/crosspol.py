@@ -157,6 +157,14 @@ class CopolCodes:
         from .. import grid as _grid
         return _grid.codes_grid(self.codes, self.lut_co, tie_points, lon=lon, lat=lat, line=line, sample=sample, keep=keep, into=into)
 
+    def polar(self, tie_points, *, centre, radius, sectors, line=None, sample=None, keep=None, into=None):
+        """`xsarsea_amd.wind_polar(self.wind(), tie_points, centre=..., radius=..., sectors=..., ...)` from the stored codes: the
+        co-pol wind in rings and sectors around a centre (`WindPolar`).  The pass reads the 4-byte codes and expands nothing; the
+        result equals that of the complex128 expansion bit for bit.  Arguments and refusals as `wind_polar`."""
+        from .. import polar as _polar
+        return _polar.codes_polar(self.codes, self.lut_co, tie_points, centre=centre, radius=radius, sectors=sectors, line=line, sample=sample,
+                                  keep=keep, into=into)
+
     def dual(self, sigma0_dual, dsig_cr=0.1, model=None, dual_select=True, codes=False, **kwargs):
         """`wind_dual`, the second element of `invert_from_model(inc, sigma0, sigma0_dual, model=(co, model), dsig_cr=...)`, bit
         for bit, from the stored co-pol codes.  model: the cross-pol model; **kwargs go to its `to_lut`.  dual_select=False:
