@@ -1,10 +1,12 @@
 """CPU: the restatement tests/filtering_ref.py against scipy itself, the host-side pieces of
 xsarsea_amd.gradients.filtering_parameters, and the conditions that keep the GPU comparison honest, asserted on the restatement
-alone for every scene tests/test_gpu_filtering.py uses."""
+alone for every scene tests/test_gpu_filtering.py uses and every case of tests/filter_cases.py (the seam shapes and in-ramp inputs
+of tests/test_gpu_filter_seams.py), with four wrong halos that the comparison there has to be able to see."""
 import numpy as np
 import pytest
 from scipy import ndimage, signal
 
+import filter_cases as fc
 import filtering_ref as fr
 from xsarsea_amd import gradients
 from xsarsea_amd.gradients import FilteringParameters, Mean, filtering_parameters, smoothing  # noqa: F401  (the feature's names)
@@ -118,3 +120,89 @@ def test_scene_conditions(spec):
     assert ill <= 1e-3
     assert min_ramp >= 0.05
     assert finite >= 0.8
+
+
+# ------------------------------------------------------------------------------------- the seam cases of tests/filter_cases.py
+def test_filter_cases_conditions():
+    """Builds every case of tests/filter_cases.py: each asserts on the restatement the property it is there for (designed inputs
+    inside the ramps on >= 99 % of the pixels and no ill-conditioned pixel, >= 16 seam pixels inside every ramp of a chain scene,
+    every valid-count of the 2 x 2 mean, NaN where the NaN variants want it and at least half of every field finite)."""
+    fc.check_all()
+    seam = fc.seam_mask((70, 40))
+    assert seam[31].all() and seam[32].all() and seam[:, 5].all() and seam[:, 34].all() and seam[64].all() and seam[69].all()
+    assert not seam[6:31, 6:31].any() and not seam[33:63, 6:31].any() and not seam[33, 33] and seam.sum() == 70 * 40 - (25 + 30) * (25 + 1)
+
+
+def mean_by_tiles(x):
+    """Wrong halo (a): every 32 x 32 tile reflects at its own edge."""
+    out = np.empty_like(x)
+    for y in range(0, x.shape[0], fc.TILE):
+        for xx in range(0, x.shape[1], fc.TILE):
+            out[y:y + fc.TILE, xx:xx + fc.TILE] = fr.Mean(x[y:y + fc.TILE, xx:xx + fc.TILE])
+    return out
+
+
+def mean_shifted_column(x):
+    """Wrong halo (b): the output column 31 mod 32 comes from the input rolled by one column."""
+    out = fr.Mean(x)
+    out[:, fc.TILE - 1::fc.TILE] = fr.Mean(np.roll(x, 1, axis=1))[:, fc.TILE - 1::fc.TILE]
+    return out
+
+
+def mean_reflect_101(x):
+    """Wrong halo (c): both convolutions with the reflect-101 border (numpy's "reflect") instead of "symm"."""
+    a = signal.convolve2d(np.pad(x, 2, mode="reflect"), fr.B4, mode="valid")
+    return signal.convolve2d(np.pad(a, 4, mode="reflect"), fr.B42, mode="valid")
+
+
+def zoom_wrong_factor(q4, out_shape):
+    """Wrong zoom (d): the output o reads the coordinate o * n_in / n_out instead of o * (n_in - 1) / (n_out - 1)."""
+    taps = []
+    for n_in, n_out in zip(q4.shape, out_shape):
+        cc = np.arange(n_out) * (n_in / n_out)
+        i0 = np.floor(cc).astype(np.int64)
+        taps.append((np.minimum(i0, n_in - 1), np.minimum(i0 + 1, n_in - 1), cc - i0))
+    (y0, y1, ty), (x0, x1, tx) = taps
+    ty = ty[:, None]
+    return (q4[np.ix_(y0, x0)] * (1 - ty) + q4[np.ix_(y1, x0)] * ty) * (1 - tx) + (q4[np.ix_(y0, x1)] * (1 - ty) + q4[np.ix_(y1, x1)] * ty) * tx
+
+
+WRONG = {"tiles": mean_by_tiles, "column": mean_shifted_column, "reflect101": mean_reflect_101, "zoom": zoom_wrong_factor}
+
+
+def test_wrong_halo_variants_are_wrong_only_where_they_should_be():
+    """The variants themselves: equal to Mean away from the seam they break, the right zoom at the first output."""
+    x = fc.mean_input((63, 65))
+    right = fr.Mean(x)
+    np.testing.assert_allclose(mean_by_tiles(x)[6:26, 6:26], right[6:26, 6:26], rtol=1e-13)
+    assert not np.isclose(mean_by_tiles(x)[28:36], right[28:36], rtol=1e-6).all()
+    np.testing.assert_array_equal(mean_shifted_column(x)[:, :31], right[:, :31])
+    np.testing.assert_allclose(mean_reflect_101(x)[6:-6, 6:-6], right[6:-6, 6:-6], rtol=1e-13)
+    assert np.abs(mean_reflect_101(x)[0] / right[0] - 1).max() > 1e-6
+    q4 = fc.designed((63, 65), "B", 1)["q4"]
+    assert zoom_wrong_factor(q4, (63, 65))[0, 0] == q4[0, 0]
+    np.testing.assert_allclose(mean_reflect_101(np.ones((2, 9))), 1.0, rtol=1e-15)  # an axis shorter than the reach still pads
+
+
+def applicable(grid, variant):
+    """(a) needs an interior seam, (b) a column 31; (c) and (d) only the raster's edge."""
+    return {"tiles": max(grid) > fc.TILE, "column": grid[1] >= fc.TILE}.get(variant, True)
+
+
+@pytest.mark.parametrize("grid,variant", [(g, v) for g in fc.RAW_GRIDS if max(g) > 6 for v in sorted(WRONG) if applicable(g, v)],
+                         ids=lambda v: v if isinstance(v, str) else f"{v[0]}x{v[1]}")
+def test_the_comparison_can_fail(grid, variant):
+    """A wrong halo in Mean (set A, f1) or a wrong zoom factor (set B, f2) moves the restatement's own filter by more than
+    1e3 ATOL = 1e-6 on at least one seam pixel strictly inside the ramp: the comparison of tests/test_gpu_filter_seams.py at
+    ATOL = 1e-9 would fail on a kernel with that fault."""
+    for phase in fc.PHASES:
+        which, k = ("B", 1) if variant == "zoom" else ("A", 0)
+        t = fc.designed(grid, which, phase)
+        right = fc.designed_want(grid, which, phase)[k]
+        if variant == "zoom":
+            wrong = fc.combine_with(t, Z=zoom_wrong_factor(t["q4"], grid))[k]
+        else:
+            wrong = fc.combine_with(t, mean=WRONG[variant])[k]
+        hit = fc.seam_mask(grid) & fc.inside(right) & (np.abs(wrong - right) > 1e-6)
+        print(f"{grid} {variant} phase {phase:+d}: {int(hit.sum())} seam pixels moved, by up to {np.abs(wrong - right)[fc.inside(right)].max():.3g}")
+        assert hit.any()
