@@ -97,13 +97,13 @@ def bracket(centres, coords):
     return np.array(first), np.array(second), np.array(t)
 
 
-def ancillary(dirs, windows_line, windows_sample, anc, line, sample):
-    """|a| v / |v| per pixel, v the bilinear blend of the resolved directions: corners in line-major order, each weighing
-    (line weight) * (sample weight), NaN corners skipped; a where |v| == 0; NaN + NaN j where a has a NaN part."""
-    anc, dirs = np.asarray(anc, dtype=np.complex128), np.asarray(dirs, dtype=np.complex128)
+def blend_sums(dirs, windows_line, windows_sample, line, sample):
+    """(vx, vy) per pixel: the float64 sums of the bilinear blend, corners in line-major order from 0, each weighing
+    (line weight) * (sample weight), NaN corners skipped."""
+    dirs = np.asarray(dirs, dtype=np.complex128)
     i0, i1, tl = bracket(windows_line, line)
     j0, j1, ts = bracket(windows_sample, sample)
-    vx, vy = np.zeros(anc.shape), np.zeros(anc.shape)
+    vx, vy = np.zeros((len(i0), len(j0))), np.zeros((len(i0), len(j0)))
     for ii, wl in ((i0, 1.0 - tl), (i1, tl)):
         for jj, ws in ((j0, 1.0 - ts), (j1, ts)):
             w = wl[:, None] * ws[None, :]
@@ -111,6 +111,61 @@ def ancillary(dirs, windows_line, windows_sample, anc, line, sample):
             ok = ~(np.isnan(d.real) | np.isnan(d.imag))
             vx = np.where(ok, vx + w * np.where(ok, d.real, 0.0), vx)
             vy = np.where(ok, vy + w * np.where(ok, d.imag, 0.0), vy)
+    return vx, vy
+
+
+LONGDOUBLE_EPS = float(np.finfo(np.longdouble).eps)   # 2**-63 where long double is the x87 format
+
+
+def ancillary_exact(dirs, windows_line, windows_sample, anc, line, sample):
+    """The finish of `ancillary` in np.longdouble on the float64 sums of `blend_sums` (which are the rule, not an approximation:
+    four corners in a stated order): hypot(vx, vy), hypot(a.re, a.im), the product and the quotient.  dict(real, imag
+    (longdouble; meaningful on `blend` only), nan, fallback, blend: the three classes of pixels, which cover the raster; vx, vy)."""
+    anc = np.asarray(anc, dtype=np.complex128)
+    vx, vy = blend_sums(dirs, windows_line, windows_sample, line, sample)
+    nan = np.isnan(anc.real) | np.isnan(anc.imag)
+    fallback = ~nan & (vx == 0) & (vy == 0)     # hypot(vx, vy) == 0 exactly there and nowhere else
+    blend = ~nan & ~fallback
+    lx, ly = vx.astype(np.longdouble), vy.astype(np.longdouble)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        nv, m = np.hypot(lx, ly), np.hypot(anc.real.astype(np.longdouble), anc.imag.astype(np.longdouble))
+        re, im = m * lx / nv, m * ly / nv
+    assert (nan ^ fallback ^ blend).all() and not (nan & fallback).any()
+    return dict(real=re, imag=im, nan=nan, fallback=fallback, blend=blend, vx=vx, vy=vy)
+
+
+TINY_NORMAL = float(np.finfo(np.float64).tiny)
+
+
+def ancillary_ulps(got, exact):
+    """(worst error of the blend pixels' components in units of spacing(|exact|), worst absolute error of the components whose
+    exact value is non-zero and below the smallest normal float64 in units of 2**-1074, their count, the count of all blend
+    components).  A component whose exact value is 0 (its float64 sum is 0: every corner lies on the other axis; or |a| is 0) is
+    not in those counts: it must be a zero of the sum's sign, which is asserted here.  m * (+-0.0) / |v| and 0 * v / |v| have no
+    rounding, and a sum that starts from +0.0 never gives -0.0."""
+    got = np.asarray(got)
+    b = exact["blend"]
+    worst, worst_tiny, n_tiny = 0.0, 0.0, 0
+    for g, e, v in ((got.real[b], exact["real"][b], exact["vx"][b]), (got.imag[b], exact["imag"][b], exact["vy"][b])):
+        zero = e == 0
+        assert not np.signbit(v[v == 0]).any()
+        assert (g[zero].view(np.int64) == np.copysign(0.0, v[zero]).view(np.int64)).all(), "an exact zero keeps the sum's sign"
+        tiny = ~zero & (np.abs(e) < TINY_NORMAL)
+        n_tiny += int(tiny.sum())
+        if tiny.any():
+            worst_tiny = float(np.maximum(worst_tiny, np.max(np.abs(g[tiny] - e[tiny])) / np.longdouble(2.0) ** -1074))   # (NaN propagates)
+        rest = ~zero & ~tiny
+        if rest.any():
+            err = np.abs(g[rest].astype(np.longdouble) - e[rest])
+            worst = float(np.maximum(worst, np.max(err / np.spacing(np.abs(e[rest]).astype(np.float64)))))
+    return worst, worst_tiny, n_tiny, 2 * int(b.sum())
+
+
+def ancillary(dirs, windows_line, windows_sample, anc, line, sample):
+    """|a| v / |v| per pixel, v the bilinear blend of the resolved directions: corners in line-major order, each weighing
+    (line weight) * (sample weight), NaN corners skipped; a where |v| == 0; NaN + NaN j where a has a NaN part."""
+    anc = np.asarray(anc, dtype=np.complex128)
+    vx, vy = blend_sums(dirs, windows_line, windows_sample, line, sample)
     nv, m = np.hypot(vx, vy), np.hypot(anc.real, anc.imag)
     out = anc.copy()
     go = nv != 0

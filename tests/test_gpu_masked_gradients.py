@@ -296,7 +296,7 @@ def test_masked_windows_drop_out_of_the_a_priori_wind(torch):
     want = compare_streaks(s, h.weight[None], h.used_ratio[None], BINS, True, True, "masked chain")
     dw = sref.resolve(s.angle, s.weight, s.used_ratio, sref.at_windows(anc, line, sample, at["line"], at["sample"]), min_used_ratio=r)
     assert bits_equal(d, dw)
-    check_ancillary(prior, sref.ancillary(dw, at["line"], at["sample"], anc, line, sample), anc, "masked chain")
+    check_ancillary(prior, anc, (dw, at["line"], at["sample"], line, sample), "masked chain")
     assert want["used_ratio"].shape == (3, 3)
     # device tensors: synchronised step by step, then on a user stream with nothing synchronised before the read-back
     t_s0, t_anc = torch.from_numpy(s0).cuda(), torch.from_numpy(anc).cuda()

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import gradients_ref as ref
+import streak_cases as sc
 import streaks_ref as sref
 import strip_shapes
 from test_gpu_gradients import LINE, SAMPLE, scene
@@ -26,35 +27,20 @@ def host(t):
     return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
 
 
-def assert_rel(got, want, rtol, what):
-    """NaN positions equal, the rest to rtol relative."""
-    got, want = host(got), host(want)
-    assert got.shape == want.shape, what
-    np.testing.assert_array_equal(np.isnan(got), np.isnan(want), err_msg=what)
-    ok = ~np.isnan(want)
-    err = np.abs(got[ok] - want[ok])
-    print(f"{what}: max relative error {np.max(err / np.maximum(np.abs(want[ok]), 1e-300), initial=0.0):.3g} (bound {rtol:g})")
-    assert (err <= rtol * np.abs(want[ok])).all(), what
-
-
 def compare_streaks(s, W, R, angles, smooth, orthogonal, what):
-    """Device result against the restatement on the same histograms.  index is equal except where the two largest smoothed
-    values differ by less than 1e-9 relative, and at most 1 window in 100 may be such a window (asserted on the restatement
-    alone); angle is bit-equal where index is; weight and used_ratio agree to 1e-12 relative (float64 sums in another order)."""
+    """Device result against the restatement on the same histograms: index equal at every window; weight, used_ratio and angle
+    bit-equal (NaN included).  The restatement adds in the kernel's order (the mean in axis order with one division, every
+    smoothing pass from 0 over all its taps in ascending order), the kernel is built without contractions and calls no library
+    function, so nothing allows a difference in bits and no window is excused."""
+    W, R = host(W), host(R)
     want = sref.streaks_direction(W, R, angles, smooth=smooth, orthogonal=orthogonal)
-    tie = sref.near_tie(want["m"])
-    print(f"{what}: {tie.size} windows, {int(tie.sum())} excluded as near ties")
-    assert tie.sum() * 100 <= tie.size, f"{what}: too many near ties for this scene to test the peak"
     index = host(s.index)
     assert index.dtype == np.int32
-    np.testing.assert_array_equal(index[~tie], want["index"][~tie], err_msg=what)
-    same = index == want["index"]
-    assert bits_equal(host(s.angle)[same], want["angle"][same]), what
-    np.testing.assert_array_equal(host(s.angle), (angles + (np.pi / 2 if orthogonal else 0))[index])
-    assert_rel(host(s.used_ratio), want["used_ratio"], 1e-12, what + " used_ratio")
-    got_w = host(s.weight)
-    np.testing.assert_array_equal(np.isnan(got_w), np.isnan(want["weight"]))
-    assert_rel(got_w[same], want["weight"][same], 1e-12, what + " weight")
+    np.testing.assert_array_equal(index, want["index"], err_msg=what)
+    assert bits_equal(host(s.weight), want["weight"]), what + " weight"
+    assert bits_equal(host(s.used_ratio), want["used_ratio"]), what + " used_ratio"
+    assert bits_equal(host(s.angle), want["angle"]), what + " angle"
+    assert bits_equal(host(s.angle), (angles + (np.pi / 2 if orthogonal else 0))[want["index"]]), what + " angle from the table"
     return want
 
 
@@ -92,10 +78,11 @@ def test_hand_built_histograms_and_angle_counts():
         want = sref.streaks_direction(W, np.full(R.shape, np.nan), BINS, smooth=smooth)
         np.testing.assert_array_equal(s.index, want["index"])
         assert list(s.index[0]) == [0, 71, 10, 0] and np.isnan(s.weight[0, 3]) and np.isnan(s.used_ratio).all()
-        assert_rel(s.weight, want["weight"], 1e-12, "hand-built weight")
+        assert bits_equal(s.weight, want["weight"]), "hand-built weight"
+        assert bits_equal(s.angle, want["angle"]), "hand-built angle"
     h = gradients.GradientsHistogram(W, R, BINS, np.arange(2) * 100.0, np.arange(4) * 50.0, ("c", "line", "sample", "angles"))
     s = streaks.streaks_direction(h)
-    assert_rel(s.used_ratio, sref.nanmean_leading(R, 2), 1e-12, "hand-built used_ratio")
+    compare_streaks(s, W, R, BINS, True, True, "hand-built, with used_ratio")
     assert s.line[1] == 100.0 and s.sample[3] == 150.0
     for n in (8, 12, 90, 360, 512):
         Wn = rng.uniform(0, 1, (2, 3, 5, n))
@@ -103,15 +90,10 @@ def test_hand_built_histograms_and_angle_counts():
         bins = ref.angles_bins(n)
         for smooth in (True, False):
             s = streaks.streaks_direction(Wn, smooth=smooth, angles=bins)
-            want = sref.streaks_direction(Wn, np.ones((2, 3, 5)), bins, smooth=smooth)
-            # 8 bins: the passes at reach 1, 2 and 4 average all of them, the smoothed histogram is flat and every window a tie
-            tie = sref.near_tie(want["m"])
-            assert tie.all() if (n == 8 and smooth) else not tie.any()
-            np.testing.assert_array_equal(s.index[~tie], want["index"][~tie])
-            same = s.index == want["index"]
-            assert bits_equal(s.angle[same], want["angle"][same])
-            assert_rel(s.weight[same], want["weight"][same], 1e-12, f"n_angles {n}")
-            assert_rel(s.weight, np.take_along_axis(want["m"], s.index[..., None].astype(np.int64), -1)[..., 0], 1e-12, f"n_angles {n}, own peak")
+            # 8 bins: the passes at reach 1, 2 and 4 average all of them, the smoothed histogram is flat and rounding decides the
+            # peak: in the restatement's order, which is the kernel's, so these windows are asserted like the others
+            want = compare_streaks(s, Wn, np.full((2, 3, 5), np.nan), bins, smooth, True, f"n_angles {n} smooth {smooth}")
+            assert bits_equal(s.weight, np.take_along_axis(want["m"], s.index[..., None].astype(np.int64), -1)[..., 0]), f"n_angles {n}, own peak"
     for n in (7, 513):
         with pytest.raises(_lib.XswError):
             streaks.streaks_direction(np.zeros((1, 1, n)), angles=ref.angles_bins(n))
@@ -196,23 +178,49 @@ def raster(rng, shape):
     return a
 
 
-def check_ancillary(got, want, anc, what):
-    """1e-12 relative to |a| on both parts, NaN positions equal, fallback pixels (the restatement returns a itself) bit-equal."""
+# The raster pass cannot be held to the bit: its two moduli are the device library's double hypot, whose rounding is its own.
+# Everything else is: the blend sums (four corners in a stated order, tests/streaks_ref.py::blend_sums), one product, one quotient.
+# So each component is compared with the same finish done in np.longdouble on those sums (sref.ancillary_exact), in ulps of
+# that component: K = 2 h + 1 + 1, for two hypot calls of at most h ulp each, the product and the quotient of half an ulp
+# each, and one ulp of slack.  h is measured, the library's accuracy table not being shipped with it: the device's hypot against
+# the longdouble value on every (vx, vy) and (a.re, a.im) of the blend pixels of the nine cases below (HYPOT_PAIRS pairs) is off
+# by at most HYPOT_ULP_MEASURED ulp, which h rounds up to the next half ulp.  (glibc's hypot stays within 0.56 ulp on the same
+# pairs, and numpy's own finish of the restatement within 2.8 ulp of the longdouble one.)
+#
+# Measured on the MI355X, worst error of a component in ulps of that component, per case: odd 3.17, one_row 2.38, one_window 1.31,
+# irregular 2.88, dense 2.82, wide 3.44, dense_blocks 3.81 (16.4 million components), small_components 2.85, closed_form 1.32;
+# tests/test_gpu_masked_gradients.py's masked chain 3.39.  No component below the smallest normal float64 in any of them.
+HYPOT_PAIRS = 19265848
+HYPOT_ULP_MEASURED = 1.1938
+HYPOT_ULP = 1.5
+K_ULP = 2 * HYPOT_ULP + 1 + 1   # 5
+
+
+def check_ancillary(got, anc, geometry, what):
+    """Every pixel in one of three classes: NaN positions equal; fallback pixels (the restated |v| is 0) bit-equal to a; every
+    other pixel per component within K_ULP * spacing(|exact|) of the longdouble finish.  A component whose exact value is below
+    the smallest normal float64 is held to K_ULP * 2**-1074 instead, and fewer than 1 in 1000 may be such (an exact zero is held
+    to the bit and not counted, sref.ancillary_ulps).  Returns (fallback pixels, blend pixels)."""
     got = host(got)
-    np.testing.assert_array_equal(np.isnan(got.real), np.isnan(want.real), err_msg=what)
-    np.testing.assert_array_equal(np.isnan(got.imag), np.isnan(want.imag), err_msg=what)
-    ok = ~np.isnan(want.real)
-    mag = np.abs(anc[ok])
-    err = np.maximum(np.abs(got.real[ok] - want.real[ok]), np.abs(got.imag[ok] - want.imag[ok]))
-    print(f"{what}: max error / |a| = {np.max(err / np.maximum(mag, 1e-300), initial=0.0):.3g} (bound 1e-12), {int(ok.sum())} pixels")
-    assert (err <= 1e-12 * mag).all(), what
-    fallback = ok & (want.real.view(np.int64) == anc.real.view(np.int64)) & (want.imag.view(np.int64) == anc.imag.view(np.int64))
-    assert bits_equal(got[fallback], anc[fallback]), what + ": fallback pixels"
-    return int(fallback.sum())
+    ex = sref.ancillary_exact(*geometry[:3], anc, *geometry[3:])
+    assert sref.LONGDOUBLE_EPS < 2.0 ** -60, "np.longdouble is no wider than float64 here"
+    assert (ex["nan"] ^ ex["fallback"] ^ ex["blend"]).all()
+    np.testing.assert_array_equal(np.isnan(got.real), ex["nan"], err_msg=what)
+    np.testing.assert_array_equal(np.isnan(got.imag), ex["nan"], err_msg=what)
+    assert bits_equal(got[ex["fallback"]], anc[ex["fallback"]]), what + ": fallback pixels"
+    worst, worst_tiny, n_tiny, n = sref.ancillary_ulps(got, ex)
+    print(f"{what}: worst / K = {worst:.3f} / {K_ULP} = {worst / K_ULP:.3f} ulp of the component over {n} components; "
+          f"{n_tiny} below the smallest normal (worst {worst_tiny:.3g} of 2**-1074); {int(ex['fallback'].sum())} fallback, {int(ex['nan'].sum())} NaN pixels")
+    assert worst <= K_ULP, what
+    assert worst_tiny <= K_ULP and n_tiny * 1000 < max(n, 1), what
+    return int(ex["fallback"].sum()), int(ex["blend"].sum())
 
 
-@pytest.mark.parametrize("case", ["odd", "one_row", "one_window", "irregular", "dense", "wide", "dense_blocks"])
-def test_ancillary_from_streaks_matches_the_restatement(case):
+ANCILLARY_CASES = ["odd", "one_row", "one_window", "irregular", "dense", "wide", "dense_blocks"]
+
+
+def ancillary_case(case):
+    """(dirs, windows_line, windows_sample, anc, line, sample) of one case of the raster pass."""
     rng = np.random.default_rng(40)
     if case == "odd":  # odd sizes, regular centres that start inside the raster and end outside
         shape, wl, ws = (203, 317), np.arange(5) * 47.0 + 20, np.arange(8) * 45.0 + 11
@@ -251,12 +259,38 @@ def test_ancillary_from_streaks_matches_the_restatement(case):
         shape, wl, ws = (1031, 1237), np.arange(6) * 200.0, np.arange(7) * 200.0
         line, sample = np.arange(1031.0), np.arange(1237.0)
     dirs, anc = field(rng, len(wl), len(ws), holes=case != "one_window"), raster(rng, shape)
+    return dirs, wl, ws, anc, line, sample
+
+
+@pytest.mark.parametrize("case", ANCILLARY_CASES)
+def test_ancillary_from_streaks_matches_the_restatement(case):
+    """Every pixel through check_ancillary: K = 5 ulp of each component.  Measured worst on the MI355X: odd 3.17, one_row 2.38,
+    one_window 1.31, irregular 2.88, dense 2.82, wide 3.44, dense_blocks 3.81 ulp."""
+    dirs, wl, ws, anc, line, sample = ancillary_case(case)
+    shape = anc.shape
     got = streaks.ancillary_from_streaks(dirs, anc, line, sample, windows_line=wl, windows_sample=ws)
-    want = sref.ancillary(dirs, wl, ws, anc, line, sample)
-    n = check_ancillary(got, want, anc, case)
+    n, n_blend = check_ancillary(got, anc, (dirs, wl, ws, line, sample), case)
     assert got.dtype == np.complex128 and got.shape == shape
     if case in ("odd", "irregular", "wide"):
-        assert 0 < n < (~np.isnan(want.real)).sum() // 2  # both the fallback and the blend occur
+        assert 0 < n < (n + n_blend) // 2  # both the fallback and the blend occur, the blend on more than half of the non-NaN pixels
+
+
+@pytest.mark.parametrize("name", sorted(sc.FIELDS))
+def test_ancillary_on_the_designed_fields(name, torch):
+    """small_components: directions within 1e-8 rad of the axes, so one component of v is 1e-8 of the other, with mixed signs: the
+    pixels a bound relative to |a| said nothing about.  closed_form: windows of 1, -1 (as complex(-1.0, -0.0)), 1j and -1j, a on
+    an axis with |a| = 7 * 2**k, dyadic weights: inside a bracket of four equal corners the output is |a| times that axis and the
+    other part is +0.0, to the bit.  Both through numpy arrays and device tensors (bit-identical routes).  K = 5 ulp; measured
+    worst on the MI355X: small_components 2.85, closed_form 1.32 ulp (its brackets of unequal corners)."""
+    f = sc.FIELDS[name]()
+    got = streaks.ancillary_from_streaks(f.dirs, f.anc, f.line, f.sample, windows_line=f.windows_line, windows_sample=f.windows_sample)
+    check_ancillary(got, f.anc, (f.dirs, f.windows_line, f.windows_sample, f.line, f.sample), name)
+    if name == "closed_form":
+        eq = f.claim["equal"]
+        assert bits_equal(got[eq], f.claim["expected"][eq]), "closed form, the sign of zero included"
+    got_d = streaks.ancillary_from_streaks(torch.from_numpy(f.dirs.copy()).cuda(), torch.from_numpy(f.anc.copy()).cuda(), f.line, f.sample,
+                                           windows_line=f.windows_line, windows_sample=f.windows_sample)
+    assert bits_equal(host(got_d), got), name + ": device tensors"
 
 
 def test_ancillary_full_size(torch):

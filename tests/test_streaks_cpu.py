@@ -3,7 +3,9 @@ import numpy as np
 import pytest
 
 import gradients_ref as ref
+import streak_cases as sc
 import streaks_ref as sref
+from util import bits_equal
 from xsarsea_amd import _lib, gradients, streaks
 
 BINS = ref.angles_bins(72)
@@ -182,6 +184,78 @@ def test_streak_scene_quadrants_are_recovered():
     out = sref.ancillary(dirs, at["line"], at["sample"], np.full((32, 32), 7 + 0j), line[::10], sample[::10])
     np.testing.assert_allclose(np.abs(out), 7.0, rtol=1e-14)
     np.testing.assert_array_equal(out[:9, :9], np.broadcast_to(7 * dirs[0, 0], (9, 9)))
+
+
+@pytest.mark.parametrize("family", sorted(sc.BUILDERS))
+def test_streak_case_builders_hold_what_they_claim(family):
+    """Every builder of tests/streak_cases.py runs here, with the assertions it makes on the restatement."""
+    built = sc.BUILDERS[family]()
+    assert len(built) == {"periodic": 20, "lanes": 22, "counts": 12, "values": 12}[family]
+    assert len({c.name for c in built}) == len(built) and set(sc.names()) >= {c.name for c in built}
+    for c in built:
+        assert not c.weight.flags.writeable and not c.want["index"].flags.writeable and c.want["index"].dtype == np.int32
+        assert c.weight.shape[-1] == c.n and 8 <= c.n <= 512
+    if family == "periodic":
+        assert {(c.n, c.claim["period"]) for c in built} == {(n, p) for n, p, _ in sc.PERIODIC}
+        assert {len(c.claim["tied"]) for c in built} == {6, 2, 8, 12}
+    if family == "lanes":
+        assert {c.n for c in built} == set(sc.LANE_ANGLES)
+        assert sc.lane_positions(512) == (0, 63, 64, 511) and sc.lane_positions(360) == (0, 63, 64, 319, 359)
+        assert sc.lane_positions(65) == (0, 63, 64) and sc.lane_positions(63) == (0, 62) and sc.lane_positions(129) == (0, 63, 64, 127, 128)
+    if family == "counts":
+        assert sorted({c.weight.shape[1] * c.weight.shape[2] for c in built}) == [1, 3, 4, 5, 9]
+        assert max(c.weight.size for c in sc.cases().values()) == built[-1].weight.size == 3 * 9 * 512
+
+
+def smooth_in_python(h):
+    """circ_smooth of one histogram, element by element in Python floats: the same taps in the same order."""
+    x = [float(v) for v in h]
+    n = len(x)
+    for reach in (1, 2, 4, 8):
+        taps = [0.0] * (2 * reach + 1)
+        taps[0], taps[reach], taps[-1] = 0.25, 0.5, 0.25
+        out = []
+        for i in range(n):
+            s = 0.0
+            for j, b in enumerate(taps):
+                s = s + b * x[(i + j - reach) % n]
+            out.append(s)
+        x = out
+    return np.array(x)
+
+
+def test_circ_smooth_agrees_with_a_loop_in_python_floats_on_the_periodic_cases():
+    for c in sc.periodic_cases():
+        m0 = sref.nanmean_leading(c.weight, 3)
+        for w in range(m0.shape[1]):
+            if c.smooth:
+                assert bits_equal(smooth_in_python(m0[0, w]), c.want["m"][0, w]), c.name
+            else:
+                assert bits_equal(m0[0, w], c.want["m"][0, w]), c.name
+    h8 = sc.cases()["lanes_n8_smooth"]   # the taps wrap more than once
+    assert bits_equal(smooth_in_python(sref.nanmean_leading(h8.weight, 3)[0, 5]), h8.want["m"][0, 5])
+
+
+@pytest.mark.parametrize("name", sorted(sc.FIELDS))
+def test_raster_fields_and_the_longdouble_finish(name):
+    """The two designed fields of the raster pass hold what they claim, and numpy's own finish of the restatement stays within
+    K = 2h + 2 = 4 ulp of the longdouble finish per component (h = 1: glibc's hypot is within 1 ulp)."""
+    f = sc.FIELDS[name]()
+    want = sref.ancillary(f.dirs, f.windows_line, f.windows_sample, f.anc, f.line, f.sample)
+    ex = sref.ancillary_exact(f.dirs, f.windows_line, f.windows_sample, f.anc, f.line, f.sample)
+    assert (ex["nan"] ^ ex["fallback"] ^ ex["blend"]).all()
+    np.testing.assert_array_equal(np.isnan(want.real), ex["nan"])
+    assert bits_equal(want[ex["fallback"]], f.anc[ex["fallback"]])
+    if name == "closed_form":   # |a| times the corners' axis, the other part +0.0, to the bit
+        eq = f.claim["equal"]
+        assert not (eq & ~ex["blend"]).any()
+        assert bits_equal(want[eq], f.claim["expected"][eq])
+        assert set(np.abs(f.claim["expected"][eq]) / 7) <= {2.0 ** k for k in range(-20, 21)}
+    if sref.LONGDOUBLE_EPS >= 2.0 ** -60:
+        pytest.skip("np.longdouble is no wider than float64 here: nothing to compare the ulps against")
+    worst, worst_tiny, n_tiny, n = sref.ancillary_ulps(want, ex)
+    print(f"{name}: numpy finish worst {worst:.3g} ulp over {n} components, {n_tiny} below the smallest normal")
+    assert worst <= 4 and n_tiny == 0 and worst_tiny == 0
 
 
 def test_public_call_raises_without_gpu():
