@@ -14,7 +14,11 @@
 //   k_nesz_eval     the raster from the column abscissae and the lines' coefficients (write only).
 // Sums are float64 whatever the raster dtype (numpy accumulates float32 rasters in float32); the fit is the closed
 // form of the normal equations about x0 instead of numpy's SVD: results agree with the host route to ~1e-13 relative
-// for float64 rasters (tests state 1e-10), ~1e-6 for float32 rasters (numpy's float32 log10 and float32 column sums).
+// for float64 rasters, ~1e-6 for float32 rasters (numpy's float32 log10 and float32 column sums).  tests/test_gpu_nesz_chain.py
+// holds the whole chain to a longdouble evaluation of the operation (tests/nesz_chain_ref.py) within a bound per pixel built
+// from the pair's stated accuracy, the fit's hat vector and the error of a float64 restatement in this order of operations;
+// the moments are taken about x0, not about a line's own mean abscissa, so a line whose few fitted samples lie close
+// together far from x0 loses (distance / spread)^2 of the float64 precision (1e-9 at two adjacent samples of 300).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
