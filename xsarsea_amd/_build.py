@@ -13,6 +13,7 @@ SRC_STREAKS = os.path.join(CSRC, "xsw_streaks.hip")  # histograms -> streak dire
 SRC_ANCILLARY = os.path.join(CSRC, "xsw_ancillary.hip")  # model grid + tie points -> a-priori wind raster (xsarsea_amd.ancillary)
 SRC_CELLS = os.path.join(CSRC, "xsw_cells.hip")  # wind / real raster -> statistics on a product grid (xsarsea_amd.cells)
 SRC_CALIBRATE = os.path.join(CSRC, "xsw_calibrate.hip")  # digital numbers + annotation tables -> sigma0, nesz, incidence, valid (xsarsea_amd.calibrate)
+SRC_LANDMASK = os.path.join(CSRC, "xsw_landmask.hip")  # coastline edges + tie points -> sea / land keep mask (xsarsea_amd.landmask)
 DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".hpp"))] + [os.path.join(REPO, "include", "xsw.h")]
 LIB = os.environ.get("XSW_LIB") or os.path.join(HERE, "libxsw.so")  # XSW_LIB: experiment builds only
 OBJDIR = os.path.join(REPO, "build", "obj")
@@ -34,8 +35,8 @@ def needs_build():
 
 
 def build(force=False, verbose=False):
-    """Compile csrc/*.hip -> libxsw.so for gfx950: ten translation units side by side (xsw.hip, xsw_invert_tu.hip once per
-    dtype pair, xsw_gradients.hip, xsw_streaks.hip, xsw_ancillary.hip, xsw_cells.hip, xsw_calibrate.hip), then one link; skipped, unless `force`, when libxsw.so is the newest file.
+    """Compile csrc/*.hip -> libxsw.so for gfx950: eleven translation units side by side (xsw.hip, xsw_invert_tu.hip once per
+    dtype pair, xsw_gradients.hip, xsw_streaks.hip, xsw_ancillary.hip, xsw_cells.hip, xsw_calibrate.hip, xsw_landmask.hip), then one link; skipped, unless `force`, when libxsw.so is the newest file.
     -ffp-contract=off: the kernels decide exact float64 orderings; FMAs appear only where written explicitly."""
     if not force and not needs_build():
         return LIB
@@ -52,6 +53,7 @@ def build(force=False, verbose=False):
     jobs += [(SRC_ANCILLARY, os.path.join(OBJDIR, f"{tag}_ancillary.o"), [])]
     jobs += [(SRC_CELLS, os.path.join(OBJDIR, f"{tag}_cells.o"), [])]
     jobs += [(SRC_CALIBRATE, os.path.join(OBJDIR, f"{tag}_calibrate.o"), [])]
+    jobs += [(SRC_LANDMASK, os.path.join(OBJDIR, f"{tag}_landmask.o"), [])]
     procs = []
     for src, obj, defs in jobs:
         cmd = common + defs + ["-c", src, "-o", obj]
@@ -136,8 +138,9 @@ def kernel_mnemonics(name_part, lib=None):
     return out
 
 
-def write_kernel_resources(path):
-    rows = kernel_resources()
+def write_kernel_resources(path, only=None):
+    """The table of kernel_resources() as a TSV; `only`: the kernels whose name holds this text."""
+    rows = [r for r in kernel_resources() if only is None or only in r["kernel"]]
     with open(path, "w") as f:
         f.write("# per-kernel resources of libxsw.so's gfx950 code object (xsarsea_amd/_build.py: kernel_resources)\n")
         f.write("vgpr\tagpr\tsgpr\tlds_B\tscratch_B\twaves/SIMD(vgpr)\tkernel\n")
@@ -163,7 +166,7 @@ if __name__ == "__main__":
     import sys
     if len(sys.argv) > 2 and sys.argv[1] == "--resources":
         build()
-        write_kernel_resources(sys.argv[2])
+        write_kernel_resources(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else None)
     elif len(sys.argv) > 1 and sys.argv[1] == "--code-sha":
         print(code_object_sha256())
     else:

@@ -49,4 +49,19 @@ __device__ inline TiePoint tie_point(const TieRows &q, double wl0, double wl1)
     return p;
 }
 
+// Longitude and latitude alone (step 1 of xsw_ancillary_model restricted to its first two fields; xsw_land_mask): the same
+// products and sums in the same order as tie_rows + tie_point, no hypot and no division.
+struct TieLonLat {
+    double lon, lat;
+};
+
+__device__ inline TieLonLat tie_lonlat(const double *__restrict__ tlon, const double *__restrict__ tlat, int i0, int i1, int j0, int j1, int ns,
+                                       double ws0, double ws1, double wl0, double wl1)
+{
+    TieLonLat p;
+    p.lon = wl0 * along(tlon, i0, j0, j1, ns, ws0, ws1) + wl1 * along(tlon, i1, j0, j1, ns, ws0, ws1);
+    p.lat = wl0 * along(tlat, i0, j0, j1, ns, ws0, ws1) + wl1 * along(tlat, i1, j0, j1, ns, ws0, ws1);
+    return p;
+}
+
 }  // namespace
