@@ -46,6 +46,7 @@
 // interval rule of search_cr_interval when the cross-pol table is absent.
 #pragma once
 #include "xsw_device.hpp"
+#include "xsw_tilewalk.hpp"
 
 namespace xsw {
 
@@ -919,17 +920,26 @@ __global__ __launch_bounds__(64 * XSW_BAND_WG_WAVES, CR ? XSW_BAND_WAVES_CR : XS
     __shared__ int res_[XSW_BAND_WG_WAVES][128];       // [0, 64): slot -> winning flat index (or -1); [64, 128): lane -> its pixel's slot
                                                        // (parked here through the passes: one VGPR less where the pressure peaks)
 #endif
-    // same tile walk as k_invert (XCD x owns a contiguous range of tile columns, line groups fastest), as a 2-D grid so that
-    // no division is needed: blockIdx.x = xcd + 8 * line group, blockIdx.y = tile column inside the XCD's range (workgroups
-    // are dealt to the XCDs round-robin in linear order, x fastest: the XCD of a workgroup is still blockIdx.x & 7)
+    // same tile walk as k_invert (xsw_tilewalk.hpp: XCD x owns a contiguous range of tile columns, line groups fastest; the
+    // leftover columns shared among all XCDs), as a 2-D grid so that no division is needed: blockIdx.x = xcd + 8 * line group,
+    // blockIdx.y = tile column slot of the XCD (workgroups are dealt to the XCDs round-robin in linear order, x fastest: the
+    // XCD of a workgroup is still blockIdx.x & 7)
     const long long strips_per_line = (A.samples + 63) >> 6;
-    const long long cols_per_xcd = (strips_per_line + 7) >> 3;
-    const long long xcd = blockIdx.x & 7;
-    const long long col = xcd * cols_per_xcd + blockIdx.y;
-    const long long line = (long long)(blockIdx.x >> 3) * XSW_BAND_WG_WAVES + wv;
+    const long long band_groups = (A.lines + (XSW_BAND_WG_WAVES - 1)) / XSW_BAND_WG_WAVES;  // gridDim.x / 8
+    long long col_, group_;
+    const bool tile_ = tile_walk(strips_per_line, band_groups, blockIdx.x & 7, blockIdx.y, blockIdx.x >> 3, col_, group_);
+    // (the tile is formed on the scalar unit and stays there: both numbers fit 32 bits, the launch limits see to that.  The
+    // line takes the wave number through readfirstlane as well: with the line -- and so the strip number -- in SGPRs the four
+    // production instantiations stay at 64 VGPRs or fewer without scratch; with the per-lane wave number the remap cost the
+    // mono kernel 8 bytes of scratch and the dual-pol one its eighth wave.  profiles/tile_walk_isa.txt)
+    const bool tile = __builtin_amdgcn_readfirstlane((int)tile_) != 0;
+    unsigned col32 = (unsigned)__builtin_amdgcn_readfirstlane((int)col_), group32 = (unsigned)__builtin_amdgcn_readfirstlane((int)group_);
+    __asm__ volatile("" : "+s"(col32), "+s"(group32));
+    const long long col = col32, group = group32;
+    const long long line = group * XSW_BAND_WG_WAVES + __builtin_amdgcn_readfirstlane(wv);
     const long long smp = col * 64 + lane;
 #if XSW_BAND_POOL
-    if (col >= strips_per_line) return;  // workgroup-uniform
+    if (!tile) return;  // workgroup-uniform
     // a wave past the raster's last line (raster heights that are not a multiple of XSW_BAND_WG_WAVES) runs through without a
     // pixel, on the last line's addresses: it publishes empty classes and takes its share of the workgroup's passes
     const bool live = line < A.lines;
@@ -937,7 +947,7 @@ __global__ __launch_bounds__(64 * XSW_BAND_WG_WAVES, CR ? XSW_BAND_WAVES_CR : XS
     const long long i = (live ? line : A.lines - 1) * A.samples + (smp < A.samples ? smp : A.samples - 1);
     band_wave<T, TO, CR, COUNT, ROLE, CSLDS>(L, A, i, in, lane, slots[wv], nullptr, false, line * strips_per_line + col, &pool, cs_lds);
 #else
-    if (col >= strips_per_line || line >= A.lines) return;  // wave-uniform
+    if (!tile || line >= A.lines) return;  // wave-uniform
     const bool in = smp < A.samples;
     const long long i = line * A.samples + (in ? smp : A.samples - 1);
     band_wave<T, TO, CR, COUNT, ROLE>(L, A, i, in, lane, slots[wv], res_[wv], false, line * strips_per_line + col);

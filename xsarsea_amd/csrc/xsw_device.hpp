@@ -25,6 +25,7 @@
 
 #include "xsw_codes.hpp"    // the grid codes: co_decode / co_encode, cr_decode / cr_encode
 #include "xsw_lutplan.hpp"  // the table shapes (XSW_INV_BINS, XSW_TAIL_LEVELS, XSW_BLK_*, XSW_CELL_*)
+#include "xsw_tilewalk.hpp"  // tile_walk: workgroup slot -> raster tile
 
 namespace xsw {
 
@@ -1535,13 +1536,13 @@ __global__ __launch_bounds__(256, XSW_INVERT_WAVES_PER_SIMD) void k_invert(DevTa
     // `sample` only, so a column of tiles shares one or two LUT slices.  Workgroups are dealt round-robin
     // over the 8 XCDs (b % 8 shares an XCD; placement is a speed heuristic, never a correctness
     // assumption): XCD x walks its own contiguous range of tile columns, line groups fastest, so that the
-    // waves resident on one XCD at any time work in the same few slices and its L2 keeps them.
+    // waves resident on one XCD at any time work in the same few slices and its L2 keeps them; the columns left
+    // over by the division by 8 are shared among all XCDs (xsw_tilewalk.hpp).
     const long long strips_per_line = (A.samples + 63) >> 6, line_groups = (A.lines + 3) >> 2;
-    const long long cols_per_xcd = (strips_per_line + 7) >> 3;
-    const long long xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const long long col = xcd * cols_per_xcd + j / line_groups;
-    const long long line = (j % line_groups) * 4 + (threadIdx.x >> 6);
-    if (j / line_groups >= cols_per_xcd || col >= strips_per_line || line >= A.lines) return;  // wave-uniform
+    long long col, group;
+    if (!tile_walk_linear(strips_per_line, line_groups, blockIdx.x, col, group)) return;  // workgroup-uniform
+    const long long line = group * 4 + (threadIdx.x >> 6);
+    if (line >= A.lines) return;  // wave-uniform
     const long long smp = col * 64 + lane;
     const bool in = smp < A.samples;
     const long long i = line * A.samples + (in ? smp : A.samples - 1);
@@ -1571,10 +1572,10 @@ __global__ __launch_bounds__(256, XSW_LIST_WAVES) void k_invert_list(DevTables L
         // unknown, so every tile of the raster is inverted by the general algorithm -- k_invert's tile walk as a grid-stride loop.
         // Results do not depend on which kernel wrote a pixel.
         for (long long b = blockIdx.x; b < nb; b += gridDim.x) {
-            const long long xcd = b & 7, j = b >> 3;
-            const long long col = xcd * cols_per_xcd + j / line_groups;
-            const long long line = (j % line_groups) * 4 + (threadIdx.x >> 6);
-            if (col >= strips_per_line || line >= A.lines) continue;  // wave-uniform
+            long long col, group;
+            if (!tile_walk_linear(strips_per_line, line_groups, b, col, group)) continue;  // workgroup-uniform
+            const long long line = group * 4 + (threadIdx.x >> 6);
+            if (line >= A.lines) continue;  // wave-uniform
             const long long smp = col * 64 + lane;
             const bool in = smp < A.samples;
             invert_strip<T, TO, 1, CR>(L, A, line * A.samples + (in ? smp : A.samples - 1), in, lane);
@@ -1606,10 +1607,10 @@ __global__ __launch_bounds__(256, XSW_LIST_WAVES) void k_invert_list(DevTables L
         // the pixels that did not fit into the list are marked in mask_g (one bit per pixel, a word per strip): the marked pixels
         // of the marked strips, k_invert's tile walk as a grid-stride loop, rasters read in place
         for (long long b = blockIdx.x; b < nb; b += gridDim.x) {
-            const long long xcd = b & 7, j = b >> 3;
-            const long long col = xcd * cols_per_xcd + j / line_groups;
-            const long long line = (j % line_groups) * 4 + (threadIdx.x >> 6);
-            if (col >= strips_per_line || line >= A.lines) continue;  // wave-uniform
+            long long col, group;
+            if (!tile_walk_linear(strips_per_line, line_groups, b, col, group)) continue;  // workgroup-uniform
+            const long long line = group * 4 + (threadIdx.x >> 6);
+            if (line >= A.lines) continue;  // wave-uniform
             const unsigned long long m = A.mask_g[line * strips_per_line + col];  // wave-uniform address
             if (m == 0ULL) continue;
             const long long smp = col * 64 + lane;

@@ -32,12 +32,9 @@ __global__ __launch_bounds__(256) void k_invert_exhaustive(DevTables L, KArgs A,
 
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const long long strips_per_line = (A.samples + 63) >> 6, line_groups = (A.lines + 3) >> 2;
-    const long long cols_per_xcd = (strips_per_line + 7) >> 3;
-    const long long xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const long long col = xcd * cols_per_xcd + j / line_groups;
-    const long long line = (j % line_groups) * 4 + wv;
-    const bool tile_ok = (j / line_groups < cols_per_xcd) && col < strips_per_line;  // block-uniform
-    if (!tile_ok) return;
+    long long col, group;
+    if (!tile_walk_linear(strips_per_line, line_groups, blockIdx.x, col, group)) return;  // block-uniform (xsw_tilewalk.hpp)
+    const long long line = group * 4 + wv;
     const long long smp = col * 64 + lane;
     const bool in = line < A.lines && smp < A.samples;
     const long long i = in ? line * A.samples + smp : 0;
@@ -204,11 +201,9 @@ __global__ __launch_bounds__(256) void k_invert_exhaustive32(DevTables L, KArgs 
 
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const long long strips_per_line = (A.samples + 63) >> 6, line_groups = (A.lines + 3) >> 2;
-    const long long cols_per_xcd = (strips_per_line + 7) >> 3;
-    const long long xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const long long col = xcd * cols_per_xcd + j / line_groups;
-    const long long line = (j % line_groups) * 4 + wv;
-    if (!((j / line_groups < cols_per_xcd) && col < strips_per_line)) return;  // block-uniform
+    long long col, group;
+    if (!tile_walk_linear(strips_per_line, line_groups, blockIdx.x, col, group)) return;  // block-uniform (xsw_tilewalk.hpp)
+    const long long line = group * 4 + wv;
     const long long smp = col * 64 + lane;
     const bool in = line < A.lines && smp < A.samples;
     const long long i = in ? line * A.samples + smp : 0;
