@@ -27,6 +27,11 @@
 // gives a row at or below the band's first, the smallest threshold > s + d one past a row at or above its last: two 2-byte
 // reads per direction instead of a bisection, and the number of rows to score is known before the sweep starts.
 //
+// What is the same for every lane of a pixel's segment is formed ONCE, by stage 1, and travels in the pixel's slot (BandSlot): the
+// byte offsets of the incidence slice and of those two table rows (packing: xsw_bandslot.hpp; "no threshold above s + d" is a
+// reserved offset), the a-priori halves already doubled, and |a/2|^2 of the settle threshold.  A pass adds its direction to the
+// offsets and loads: no incidence bin, no bin numbers and no multiplies of its own.
+//
 // Work decomposition: a workgroup = 4 waves = a tile of 4 lines x 64 samples (as k_invert); lane i loads pixel i, finds its
 // incidence bin, the upper bound along the a-priori direction and two neighbours (co_window_lanes), the window and the two
 // threshold bins, and parks the pixel's search parameters in an LDS slot -- slots SORTED by window class, so that a pass takes
@@ -45,8 +50,10 @@
 // The cross-pol search (dual-pol) runs one pixel per lane: search_cr_scan (table + scan of the admissible interval), or the
 // interval rule of search_cr_interval when the cross-pol table is absent.
 #pragma once
+#include <cstddef>
 #include "xsw_device.hpp"
 #include "xsw_tilewalk.hpp"
+#include "xsw_bandslot.hpp"
 
 namespace xsw {
 
@@ -107,15 +114,21 @@ static_assert(XSW_BAND_WG_WAVES % 4 == 0 || !XSW_BAND_POOL, "pooled class counts
 #endif
 
 struct BandSlot {  // 64 bytes per pixel, read by every lane of its segment (same address: LDS broadcast)
-    double sn, thr_lo, thr_hi, ah, bh;
+    // What stage 1 knows once per pixel and every lane of the segment would otherwise form again in every pass: the a-priori wind
+    // already doubled (ah2 = 2 ah, bh2 = 2 bh with ah, bh = the ancillary wind / 2: U = ah2 cos + bh2 sin, bit for bit 2 (ah cos +
+    // bh sin)), q = (ah * ah) + (bh * bh) of the settle threshold (read once, behind the sweep), and the table offsets below.
+    double sn, ah2, bh2, q;
     // pooled queues (k_invert_band, XSW_BAND_POOL): what a block of its own used to hold -- res: the winning flat index of THIS slot's
     // pixel (-1: undecided); pos: the slot of the pixel of the thread with this slot's number (lane -> slot, parked here through
-    // the passes: one VGPR less where the pressure peaks).  They took the place of |a/2|^2, which a pass needs once, for its settle
-    // threshold, and forms again from ah and bh: the 2 KB pay for most of the direction table in LDS (kBandCsCap).
+    // the passes: one VGPR less where the pressure peaks).
     int res, pos;
-    int inc_bin /* i_inc | threshold bin of s - d << 16 */, rows /* w_lo | w_hi << 16 */, ipn /* ip_lo | ncols << 16 */;
-    int bin_hi /* threshold bin above s + d, or -1 */;
+    int rows /* w_lo | w_hi << 16 */, ipn /* ip_lo | ncols << 16 */;
+    // byte offsets, formed once per pixel (xsw_bandslot.hpp): the incidence slice in L.co; the inverse-table rows of the largest
+    // threshold <= s - d and of the smallest threshold > s + d (kBandInvNone: no threshold above s + d on the grid)
+    unsigned slice0, inv0, inv1;
+    int spare_;
 };
+static_assert(sizeof(BandSlot) == 64 && offsetof(BandSlot, res) == 32, "four doubles (stage 1 parks two in a still unused slot: window_arc), then eight words");
 
 // Directions whose cos / sin pair (DevTables::csphi, 16 bytes each) k_invert_band keeps in LDS for its passes: 192 cover the
 // reference LUT's 181 in 3 KB -- 16 KB of slots + the pool + this is 20 016 B, inside the 20 480 B that eight workgroups per CU
@@ -262,23 +275,21 @@ __device__ __forceinline__ void co_band_pass(const DevTables &L, double inv_dsig
     // slot index (idle segment: any slot, its contents are overridden below)
     const int owner = valid ? (map ? (int)map[first + q] : first + q) : lane;
     BandSlot B = slots[owner];
-    if (!valid) { B.inc_bin = 0; B.rows = 0; B.ipn = 0; B.bin_hi = -1; }  // idle segment: harmless addresses, nothing scored
+    if (!valid) { B.rows = 0; B.ipn = 0; B.slice0 = 0u; B.inv0 = 0u; B.inv1 = kBandInvNone; }  // idle segment: harmless addresses, nothing scored
     const int B_ip_lo = B.ipn & 0xffff, B_ncols = (int)((unsigned)B.ipn >> 16);
     const int w_lo = B.rows & 0xffff, w_hi = B.rows >> 16;
-    const double thr_lo = B.thr_lo, thr_hi = B.thr_hi, sn = B.sn;
+    const double sn = B.sn;
     const double wh0 = 0.5 * L.w0, whs = L.wstep_half;
     const char *__restrict__ base = (const char *)L.co;
     const unsigned rowB = (unsigned)L.phi_pad * 8u;
-    const int i_inc = B.inc_bin & 0xffff;
-    // (24-bit multiplies: full rate, where v_mul_lo_u32 takes four issue slots -- four of them per lane and pass; the operands fit:
-    // the band kernels run only when n_inc * n_w and n_inc * XSW_INV_BINS stay below 2^24, xsw_lutplan.hpp: band_mul24)
-    const unsigned slice0 = mul24_sv(rowB, mul24_sv((unsigned)L.n_w, (unsigned)i_inc));
-    // rows of the inverse table (2-byte entries, one per direction, < 4 GB: xsw_lutplan.hpp): the largest threshold <= s - d gives a
-    // row at or below the band's first, the smallest threshold > s + d one past a row at or above its last
+    // The byte offsets of the incidence slice and of the two rows of the inverse table (2-byte entries, one per direction: the
+    // largest threshold <= s - d gives a row at or below the band's first, the smallest threshold > s + d one past a row at or
+    // above its last) come with the slot: stage 1 forms them once per pixel (xsw_bandslot.hpp), not every lane in every pass.
+    const unsigned slice0 = B.slice0;
     const unsigned short *__restrict__ inv_tab = L.inv_rows;
-    const unsigned inv_rowB = (unsigned)L.phi_pad * 2u;
-    const unsigned inv0 = mul24_sv(inv_rowB, (unsigned)(i_inc * XSW_INV_BINS) + ((unsigned)B.inc_bin >> 16));
-    const unsigned inv1 = mul24_sv(inv_rowB, (unsigned)(i_inc * XSW_INV_BINS) + (unsigned)max(B.bin_hi, 0));
+    const unsigned inv0 = B.inv0;
+    const bool capped = band_inv1_capped(B.inv1);
+    const unsigned inv1 = band_inv1_row(inv0, B.inv1);
     double best = inf, second = inf;
     int brow = 0, bip = 0;
     unsigned ncand = 0;
@@ -299,7 +310,7 @@ __device__ __forceinline__ void co_band_pass(const DevTables &L, double inv_dsig
             double2 cs;
             if constexpr (CSLDS) cs = cs_lds[ip[j]];
             else cs = *(const double2 *)((const char *)L.csphi + 2u * ipB);
-            U[j] = 2.0 * (B.ah * cs.x + B.bh * cs.y);
+            U[j] = B.ah2 * cs.x + B.bh2 * cs.y;  // = 2 (ah cos + bh sin) exactly: the slot holds the doubled halves
             off0[j] = slice0 + ipB;
         }
         // rows to look at: from the tabulated row at or below the band's first to the one at or above its last, inside the window
@@ -310,7 +321,7 @@ __device__ __forceinline__ void co_band_pass(const DevTables &L, double inv_dsig
             const int ra = (int)*(const unsigned short *)((const char *)inv_tab + o_first);
             const int rb = (int)*(const unsigned short *)((const char *)inv_tab + o_last);
             r[j] = max(ra, w_lo);
-            const int last = B.bin_hi >= 0 ? min(rb - 1, w_hi) : w_hi;
+            const int last = capped ? min(rb - 1, w_hi) : w_hi;
             nrow[j] = act[j] ? last - r[j] + 1 : 0;
             nmax = max(nmax, nrow[j]);
         }
@@ -349,15 +360,12 @@ __device__ __forceinline__ void co_band_pass(const DevTables &L, double inv_dsig
     }
     const int bflat = (int)__umul24((unsigned)brow, (unsigned)L.n_phi) + bip;
     const double gmin = S == 64 ? wave_min_d(best) : seg_min_d<S>(best);
-    // |a/2|^2 of the settle threshold, formed here from a RE-READ of the slot (not kept live through the sweep), in one fixed
-    // order: (ah * ah) + (bh * bh), no contraction.  It only scales a 1e-9-relative margin: should it ever differ in the last bit
-    // from a value formed elsewhere, only a near-tie at the 1e-16 level could move between "decided here" and "listed", and both
-    // give the reference's argmin.
-    // (volatile, and through an LDS pointer -- a generic volatile pointer makes them flat loads: loads of their own, after the sweep)
+    // |a/2|^2 of the settle threshold: stage 1 formed it once, (ah * ah) + (bh * bh), no contraction; read HERE from the slot, not
+    // kept live through the sweep.
+    // (volatile, and through an LDS pointer -- a generic volatile pointer makes it a flat load: a load of its own, after the sweep)
     const volatile __attribute__((address_space(3))) BandSlot *again = (const volatile __attribute__((address_space(3))) BandSlot *)(slots + owner);
-    const double ah_t = again->ah, bh_t = again->bh;
-    const double ah2 = ah_t * ah_t, bh2 = bh_t * bh_t;
-    const double T = gmin + 1e-9 * (1.0 + fabs(gmin) + (ah2 + bh2));
+    const double q_t = again->q;
+    const double T = gmin + 1e-9 * (1.0 + fabs(gmin) + q_t);
     const unsigned long long amb = ballot64(valid && (second <= T || overflow)), surv = ballot64(valid && best <= T);
     const unsigned long long segmask = S == 64 ? ~0ULL : (((1ULL << (S & 63)) - 1ULL) << ((q * S) & 63));
     const bool bad = (amb & segmask) != 0ULL || __popcll(surv & segmask) != 1 || !(gmin < 1e300);
@@ -598,7 +606,7 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
             // threshold bins of the slice's inverse table: the largest grid threshold <= s - d (bin 0 also stands for anything
             // below the grid; the check repeats the builder's own expression, k_inv_rows), and the smallest grid threshold
             // > s + d (none: the band may reach the window's last row)
-            double thr_lo = P.s_co - W.band_d, thr_hi = P.s_co + W.band_d;
+            const double thr_lo = P.s_co - W.band_d, thr_hi = P.s_co + W.band_d;
             int bin = 0, bhi = XSW_INV_BINS;
             if (eligb) {
                 const double *g = L.inv_grid + 3 * P.i_inc;
@@ -620,17 +628,17 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
                     const double rs = W.band_d * fabs(A.inv_dsig_co);
                     const float jub32 = (float)(rs * rs) * (1.0f + 1e-5f) + 1e-5f;
                     // (stage 1 holds 63 live VGPRs here: the walk's own state does not fit beside them, and a compiler spill costs the
-                    // kernel scratch -- four doubles wait in the lane's own, still unused LDS slot instead)
+                    // kernel scratch -- two doubles wait in the lane's own, still unused LDS slot instead)
                     // (ROLE 2 runs on k_invert_band2's LDS block: 64 slots of kBand2SlotBytes, not of sizeof(BandSlot))
                     double *park;
                     if constexpr (ROLE == 2) park = (double *)((char *)slots + lane * kBand2SlotBytes);
                     else park = (double *)&slots[lane];
-                    park[0] = thr_lo; park[1] = thr_hi; park[2] = W.band_d; park[3] = P.s_co;
+                    park[0] = W.band_d; park[1] = P.s_co;
                     __asm__ volatile("" ::: "memory");
                     const unsigned arc = window_arc(L.inv_rows, (const float *)L.csphi32, L.phi_pad, (float)(0.5 * L.w0), (float)L.wstep_half, widep, P.i_inc, bin, bhi,
                                                     (float)(0.5 * P.a_re), (float)(0.5 * P.b_eff), jub32, W.ip_lo, ncols_p, W.w_lo, w_hi_e);
                     __asm__ volatile("" ::: "memory");
-                    thr_lo = park[0]; thr_hi = park[1]; W.band_d = park[2]; P.s_co = park[3];
+                    W.band_d = park[0]; P.s_co = park[1];
                     const int a_first = (int)(arc & 0xffffu), a_last = (int)(arc >> 16);
                     if (widep && a_last >= a_first) {  // (the bound's own candidate is live: there always is an arc; stay safe)
                         W.ip_lo = a_first;
@@ -640,6 +648,13 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
             }
             bool hard = false;  // ROLE 1: the handed pixel is worth k_invert_band2's refinement (long run x wide window, or a tail)
             myc = NC;
+            // the two rows of the slice's inverse table, as element offsets (32-bit by 24-bit multiplies: band_mul24, the table is
+            // < 4 GB): the run length below reads through them, and the slot carries them, in bytes, to the passes
+            unsigned inv_lo = 0u, inv_hi = 0u;
+            if (eligb) {
+                inv_lo = band_inv_elems((unsigned)L.phi_pad, (unsigned)P.i_inc, (unsigned)bin);
+                inv_hi = band_inv_elems((unsigned)L.phi_pad, (unsigned)P.i_inc, (unsigned)bhi);
+            }
             if (eligb) {
                 const int nv = ncols_p;
                 const int p2 = 31 - __clz(max(nv, 2) - 1);  // 2^p2 < n <= 2^(p2 + 1)
@@ -652,11 +667,9 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
                 // per SIMD); its strip walk repeats this per-pixel decision.
                 int run = 0;
                 if (eligb) {
-                    // (32-bit element offsets by 24-bit multiplies: band_mul24, the table is < 4 GB)
-                    const unsigned tab0 = (unsigned)(P.i_inc * XSW_INV_BINS);
                     auto run_at = [&](int ip) {
-                        const int ra = (int)L.inv_rows[mul24_sv((unsigned)L.phi_pad, tab0 + (unsigned)bin) + (unsigned)ip];
-                        const int rb = bhi < XSW_INV_BINS ? (int)L.inv_rows[mul24_sv((unsigned)L.phi_pad, tab0 + (unsigned)bhi) + (unsigned)ip] : w_hi_e + 1;
+                        const int ra = (int)L.inv_rows[inv_lo + (unsigned)ip];
+                        const int rb = bhi < XSW_INV_BINS ? (int)L.inv_rows[inv_hi + (unsigned)ip] : w_hi_e + 1;
                         return min(rb - 1, w_hi_e) - max(ra, W.w_lo) + 1;
                     };
                     run = run_at(P.ipr);  // (the window's first and last directions as well: hands over 3.5x the pixels for 2 ms less here, 4 ms more there)
@@ -727,10 +740,12 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
             BandSlot b;
             if (eligb) {
                 const double ah = 0.5 * P.a_re, bh = 0.5 * P.b_eff;
-                b.sn = -P.s_co * A.inv_dsig_co; b.thr_lo = thr_lo; b.thr_hi = thr_hi;
-                b.ah = ah; b.bh = bh;
-                b.inc_bin = P.i_inc | (bin << 16); b.rows = W.w_lo | (w_hi_e << 16); b.ipn = W.ip_lo | (ncols_p << 16);
-                b.bin_hi = bhi < XSW_INV_BINS ? bhi : -1;
+                b.sn = -P.s_co * A.inv_dsig_co;
+                b.ah2 = 2.0 * ah; b.bh2 = 2.0 * bh;
+                b.q = (ah * ah) + (bh * bh);
+                b.rows = W.w_lo | (w_hi_e << 16); b.ipn = W.ip_lo | (ncols_p << 16);
+                b.slice0 = band_slice0((unsigned)L.phi_pad, (unsigned)L.n_w, (unsigned)P.i_inc);
+                b.inv0 = band_inv0(inv_lo); b.inv1 = band_inv1(inv_hi, bhi);
             }
             if (ROLE == 1 && A1.rec_b != nullptr) {
                 // the handed pixels' RECORDS (their search parameters: k_invert_band2 then neither gathers the rasters again nor
@@ -761,8 +776,8 @@ __device__ __forceinline__ void band_wave(const DevTables &L, const KArgs &A, lo
                 b.res = -1;
 #endif
                 BandSlot &d = slots[pos];  // (member by member: `pos` is another lane's word, written below)
-                d.sn = b.sn; d.thr_lo = b.thr_lo; d.thr_hi = b.thr_hi; d.ah = b.ah; d.bh = b.bh;
-                d.inc_bin = b.inc_bin; d.rows = b.rows; d.ipn = b.ipn; d.bin_hi = b.bin_hi;
+                d.sn = b.sn; d.ah2 = b.ah2; d.bh2 = b.bh2; d.q = b.q;
+                d.rows = b.rows; d.ipn = b.ipn; d.slice0 = b.slice0; d.inv0 = b.inv0; d.inv1 = b.inv1;
                 if constexpr (POOLED) d.res = b.res;
                 else res_[pos] = b.res;
             }
@@ -916,6 +931,7 @@ __global__ __launch_bounds__(64 * XSW_BAND_WG_WAVES, CR ? XSW_BAND_WAVES_CR : XS
 #if XSW_BAND_POOL
     __shared__ BandPool pool;
     __shared__ double2 cs_lds[CSLDS ? kBandCsCap : 1];
+    static_assert(sizeof(slots) + sizeof(BandPool) + sizeof(cs_lds) <= 20480, "eight workgroups per CU leave each 20 480 B of LDS");
 #else
     __shared__ int res_[XSW_BAND_WG_WAVES][128];       // [0, 64): slot -> winning flat index (or -1); [64, 128): lane -> its pixel's slot
                                                        // (parked here through the passes: one VGPR less where the pressure peaks)
