@@ -990,6 +990,46 @@ int xsw_wind_polar(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, in
                    const double *sample_t, double lon_c, double lat_c, double cos_lat_c, double sin_lat_c, double dr_km, int32_t n_r,
                    int32_t n_theta, const double *sector_sin, const double *sector_cos, int64_t *sums);
 
+/* ---- the cyclone centre from the wind field (xsarsea_amd.centre): the annulus sums of xsw_wind_polar around every node of a
+ * lattice of candidate centres, in one pass over the raster: what a search for the circulation centre (the largest mean
+ * tangential wind in an annulus near the radius of maximum wind), the calmest disc, the highest or the most uniform annulus
+ * speed scores its candidates with.  Additive to XSW_VERSION 4; conventions as above.
+ *
+ * Source, keep, tie points and per-pixel brackets: exactly as xsw_wind_grid.  (lon_g, lat_g): the first guess, finite,
+ * |lat_g| <= 89, the centre of the chart; cos_lat_g, sin_lat_g: cos and sin of lat_g, by the caller.  The candidates: an
+ * n_c x n_c lattice on that chart, n_c odd, 1 <= n_c <= 31, spaced step_km (finite, > 0; with n_c == 1 step_km is not read and
+ * the one candidate is the first guess).  The annulus: r_in_km <= r < r_out_km around each candidate, both finite,
+ * 0 <= r_in_km < r_out_km.  sums: int64 [5][n_c][n_c], the planes n, Ss, Sq, Sr, St: planes 0-4 of xsw_wind_polar, in its
+ * units.  The entry ADDS into sums; the caller zeroes them (XSW_MEM_HOST: sums is copied up, added to and copied down).
+ *
+ * Per pixel, every operation float64 and rounded once:
+ *   0. once per call:  lon_g = lon_g - 360 * rint(lon_g / 360)
+ *   1.-3. (lon, lat, ch, sh), then q, sp, u, v, then (x, y) in km: steps 1-3 of xsw_wind_polar with (lon_g, lat_g, cos_lat_g,
+ *      sin_lat_g) as its centre, unchanged
+ *   4. the pixel is dropped unless the source is valid, keep is non-zero, u and v are not NaN and q < 65536
+ * Per pixel and candidate (i, j), with h = (n_c - 1) / 2:
+ *   5. cy = (double)(i - h) * step_km  (row i runs south to north),  cx = (double)(j - h) * step_km  (both 0 for n_c == 1)
+ *   6. dx = x - cx,  dy = y - cy,  r = sqrt(dx * dx + dy * dy);  the pixel counts iff r_in_km <= r && r < r_out_km (a NaN fails)
+ *   7. vr = (u * dx + v * dy) / r,  vt = (v * dx - u * dy) / r;  both 0 where r == 0
+ *   8. sums[:, i, j]:  n += 1,  Ss += Q24(sp),  Sq += Q16(q),  Sr += Q24(vr),  St += Q24(vt), Q24 and Q16 as in xsw_wind_grid
+ * With n_c == 1 and r_in_km == 0 the sums are those of xsw_wind_polar with one ring of r_out_km, added over its sectors.
+ * Integer addition has no order: what xsw_wind_grid says of launches, tiles, scenes and devices holds here, and so does its
+ * overflow statement: a candidate is exact up to 2**30 pixels over all accumulated calls.  tests/centre_ref.py restates the
+ * entry in numpy.  Finish: wspd, wspd_std, vr, vt as in xsw_wind_polar.
+ *
+ * XSW_EINVAL, before any launch: a NULL source, sums or tie table, a bad src_kind or mem, n_c even or outside 1 .. 31, step_km
+ * not finite or not positive with n_c > 1, radii that are not finite or not ordered, a first guess that is not finite or lies
+ * beyond 89 degrees of latitude.
+ *
+ * Environment XSW_CENTRE_PATH = direct, read at every call (any other value is refused): every pixel meets every candidate in a
+ * plain loop and sends each hit's five adds straight to global memory.  Unset (the default): the pixels near the lattice are
+ * staged in LDS and every thread keeps its candidates' sums in registers.  Both give the same bits. */
+int xsw_wind_centre(xsw_ctx *ctx, int64_t lines, int64_t samples, int32_t mem, int32_t src_kind, const void *src, const uint8_t *keep,
+                    int32_t n_tie_lines, int32_t n_tie_samples, const double *tie_lon, const double *tie_lat, const double *tie_cos,
+                    const double *tie_sin, const int32_t *line_first, const double *line_t, const int32_t *sample_first,
+                    const double *sample_t, double lon_g, double lat_g, double cos_lat_g, double sin_lat_g, double step_km, int32_t n_c,
+                    double r_in_km, double r_out_km, int64_t *sums);
+
 /* ---- calibration: sigma0, NESZ, incidence and a validity mask from a product's digital numbers (xsarsea_amd.calibrate), the way
  * IN to device memory: 2 bytes per pixel and a few kilobytes of annotation instead of 4 bytes per pixel and raster.  Additive to
  * XSW_VERSION 4; conventions as above.

@@ -50,7 +50,7 @@ EXPORTS = (
     "xsw_grad_r2_sqrt", "xsw_grad_local_sqrt", "xsw_grad_smooth", "xsw_grad_mean", "xsw_grad_filter",
     "xsw_grad_hist_masked", "xsw_grad_keep_f64", "xsw_grad_keep_u8",
     "xsw_streaks_peak", "xsw_streaks_resolve", "xsw_streaks_ancillary", "xsw_ancillary_model",
-    "xsw_wind_cells", "xsw_raster_cells", "xsw_wind_grid", "xsw_wind_polar", "xsw_land_mask", "xsw_land_chunk_edges", "xsw_calibrate",
+    "xsw_wind_cells", "xsw_raster_cells", "xsw_wind_grid", "xsw_wind_polar", "xsw_wind_centre", "xsw_land_mask", "xsw_land_chunk_edges", "xsw_calibrate",
     "xsw_cross_from_codes", "xsw_cost_from_codes", "xsw_cost_cr_from_codes",
     "xsw_uncertainty_from_codes", "xsw_uncertainty_cr_from_codes", "xsw_joint_from_codes",
     "xsw_uncertainty_joint_from_codes",
@@ -60,7 +60,7 @@ EXPORTS = (
 )
 
 
-# The raster entries behind xsarsea_amd.gradients, xsarsea_amd.streaks, xsarsea_amd.ancillary, xsarsea_amd.cells, xsarsea_amd.grid, xsarsea_amd.polar and xsarsea_amd.landmask: their C signature after the context, one letter per
+# The raster entries behind xsarsea_amd.gradients, xsarsea_amd.streaks, xsarsea_amd.ancillary, xsarsea_amd.cells, xsarsea_amd.grid, xsarsea_amd.polar, xsarsea_amd.centre and xsarsea_amd.landmask: their C signature after the context, one letter per
 # argument (l int64, i int32, d double, p pointer: an int address, device or host per `mem`, or None).  `load` sets the argtypes
 # from it and every row becomes a Context method, e.g. `grad_area_raw(lines, samples, factor, dtype, mem, in_ptr, out_ptr)`.
 RASTER_ENTRIES = {
@@ -120,13 +120,18 @@ RASTER_ENTRIES = {
     # binned in n_r rings of dr_km and n_theta sectors around the centre: int64 sums [6, n_r, n_theta], the first five planes added
     # to, the sixth raised to the maximum, never zeroed; sector_sin / sector_cos: the borders of one quadrant's sectors
     "xsw_wind_polar": "lliippiipppppppp" + "dddddii" + "pp" + "p",
+    # (lines, samples, mem, src_kind, src, keep, n_tie_lines, n_tie_samples, tie_lon, tie_lat, tie_cos, tie_sin, line_first, line_t,
+    # sample_first, sample_t, lon_g, lat_g, cos_lat_g, sin_lat_g, step_km, n_c, r_in_km, r_out_km, sums): the same pixels added to
+    # every node of the n_c x n_c lattice of candidate centres around the first guess whose annulus [r_in_km, r_out_km) they lie
+    # in: int64 sums [5, n_c, n_c], added to, never zeroed
+    "xsw_wind_centre": "lliippiipppppppp" + "dddddidd" + "p",
     # (lines, samples, mem, n_tie_lines, n_tie_samples, tie_lon, tie_lat, line_first, line_t, sample_first, sample_t, n_edges, edges,
     # n_bands, band_start, n_list, band_edges, lat0, h, and_with, invert, out): the uint8 sea / land keep mask (1 = water) from the
     # float64 edges [n_edges, 4] = x1, y1, x2, y2 by the even-odd rule; n_bands = 0 with band_start / band_edges None: every pixel
     # against every edge; edges (with n_edges = 0) and and_with may be None
     "xsw_land_mask": "lliiippppppipipipddpip",
 }
-assert list(RASTER_ENTRIES) == [n for n in EXPORTS if n.startswith(("xsw_grad_", "xsw_streaks_", "xsw_ancillary_")) or n.endswith(("_cells", "_grid", "_polar", "_mask"))]
+assert list(RASTER_ENTRIES) == [n for n in EXPORTS if n.startswith(("xsw_grad_", "xsw_streaks_", "xsw_ancillary_")) or n.endswith(("_cells", "_grid", "_polar", "_centre", "_mask"))]
 CELLS_C128, CELLS_C64, CELLS_CODES = 0, 1, 2  # XSW_CELLS_* (include/xsw.h): the source kinds of xsw_wind_cells
 DN_U16, DN_F32 = 0, 1  # XSW_DN_* (include/xsw.h): the digital numbers of xsw_calibrate
 # letter -> (ctypes type, conversion the wrapper applies: ctypes alone refuses numpy scalars)

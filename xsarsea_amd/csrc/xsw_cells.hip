@@ -13,6 +13,8 @@
 //                       integers in fixed point, which have no order; stated and described further down.
 //   k_wind_polar<Src, DIRECT> the same binned in rings and sectors around a given centre (xsw_wind_polar, xsarsea_amd.polar),
 //                       with the radial and tangential components and the bin's largest speed; after k_wind_grid.
+//   k_wind_centre<Src, DIRECT> the annulus sums of k_wind_polar around every node of a lattice of candidate centres
+//                       (xsw_wind_centre, xsarsea_amd.centre): every pixel meets every candidate; after k_wind_polar.
 //
 // The order of every sum: pixel p = r * w + c of a cell (w its clipped width) goes to accumulator p mod 256; each accumulator
 // starts at +0.0 and adds its pixels in ascending p, an invalid pixel adding +0.0 (which changes no accumulator: none is ever
@@ -610,6 +612,247 @@ static void launch_polar(hipStream_t stream, int path, const Src &src, const voi
                            sector_cos, tp, lpb, (unsigned long long *)sums);
 }
 
+// ---- the cyclone centre from the wind field: annulus sums on a lattice of candidate centres (xsw_wind_centre; include/xsw.h has
+// the statement).  The sources, the geolocation, the chart and the walk down a column are k_wind_polar's; here a pixel meets EVERY
+// candidate and adds its five integers to each one whose annulus it lies in: many bins per pixel, so the stages are the other way
+// round -- the pixels are staged, the bins live in registers.
+//   DIRECT  a thread owns a pixel, loops over all candidates and sends each hit's five adds to global memory.
+//   staged  (a) the walk: a thread computes its pixel's candidate-independent terms (x, y, u, v, Q24(sp), Q16(q)) once; pixels
+//               that the drop rule drops, or that lie outside the square |x|, |y| < bound around the lattice, go no further; the
+//               survivors of a line are compacted into the workgroup's LDS tile of 48 B entries (a ballot, the lane's rank among
+//               the wave's survivors, one LDS add per wave for the wave's base);
+//           (b) the sweep, when the tile cannot take another line of 256 entries and at the end of the strip: thread t owns the
+//               candidates t, t + 256, ... (at most four: 31 * 31 <= 1024), keeps their five sums in registers across the whole
+//               strip and reads the entries one after the other, every lane the same address: broadcast reads, as k_land_mask
+//               walks its edges.  A lattice below 256 candidates is owned by 256 / candidates thread groups, group s taking
+//               the entries s, s + groups, ...; their partial sums meet by 64-bit LDS adds in the idle tile before (c);
+//           (c) the flush: every candidate with n > 0 adds its five words to global memory.
+// The cull.  A hit has fl(sqrt(fl(dx * dx + dy * dy))) < r_out, so |dx| < r_out * (1 + 4 ulp); dx = fl(x - cx) and |cx| <=
+// fl(h * step_km) for every candidate, so |x| < (fl(h * step_km) + r_out) * (1 + 8 ulp).  bound is that sum, rounded, times
+// (1 + 2**-40): a margin of 2**13 ulp where 10 are needed, the same for y.  A NaN coordinate fails the comparison, as it fails the
+// annulus test.  The pre-test on rr = dx * dx + dy * dy is conservative in the same way: sqrt is monotone and rounds once, so
+// r_in <= sqrt(rr) < r_out needs r_in * r_in * (1 - 2**-50) <= rr <= r_out * r_out * (1 + 2**-50); only then is the root taken.
+// tests/centre_ref.py has neither the cull nor the pre-test: equal sums show that they lose nothing.
+#ifndef XSW_CENTRE_TILE
+#define XSW_CENTRE_TILE 512  // entries of the LDS tile, 48 B each: 24 KiB, two full lines between sweeps
+#endif
+#ifndef XSW_CENTRE_MAX_LINES
+#define XSW_CENTRE_MAX_LINES 64  // a strip is at most this many lines long where the grid allows: the workgroups inside the square do all
+                                 // the pair work, and shorter strips spread it over more of them
+#endif
+#define XSW_CENTRE_MAX_N 31
+static_assert(XSW_CENTRE_TILE >= 512 && XSW_CENTRE_TILE * 48 >= 5 * 256 * 8, "a line must fit twice, and the partial sums of a small lattice meet in the tile");
+static_assert(XSW_CENTRE_MAX_N * XSW_CENTRE_MAX_N <= 4 * 256, "a thread owns at most four candidates");
+
+// The path of a call.  Environment XSW_CENTRE_PATH = direct forces the direct kernel (tests, measurements); read on the host at every call.
+enum { CENTRE_STAGED = 0, CENTRE_DIRECT = 1 };
+static int centre_path(bool &bad_env)
+{
+    bad_env = false;
+    if (const char *v = getenv("XSW_CENTRE_PATH")) {
+        if (!strcmp(v, "direct")) return CENTRE_DIRECT;
+        bad_env = true;
+    }
+    return CENTRE_STAGED;
+}
+
+struct Centre {
+    double lon_g, lat_g, cos_g, sin_g, step_km, r_in, r_out;
+    double rr_lo, rr_hi, bound;  // the staged path's pre-test on rr and its cull square (launch_centre)
+    int n_c;
+};
+
+struct alignas(16) CentreEntry {
+    double x, y, u, v;
+    unsigned long long s24, q16;
+};
+static_assert(sizeof(CentreEntry) == 48, "the tile's entries are 48 B");
+
+template <typename Src, bool DIRECT>
+__global__ __launch_bounds__(256) void k_wind_centre(const Src src, const unsigned char *__restrict__ keep, long long lines, long long samples,
+                                                     const Centre g, const GridTies tp, long long lines_per_block,
+                                                     unsigned long long *__restrict__ sums)
+{
+    constexpr int TILE = DIRECT ? 1 : XSW_CENTRE_TILE;
+    constexpr double D2R = 0.017453292519943295, R_KM = 6371.0088, KX = R_KM * D2R;
+    __shared__ CentreEntry tile[TILE];
+    __shared__ int line_count[3];  // the survivors of line n of the strip are counted in word n % 3
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int nc = min(max(g.n_c, 1), XSW_CENTRE_MAX_N), nc2 = nc * nc, half = (nc - 1) / 2;  // (the entry refuses other sizes: never trusted)
+    // (b)'s ownership: `own` candidates first, first + 256, ...; group `slice` of `slices` takes the entries slice, slice + slices, ...
+    int own, first = tid, slice = 0, slices = 1;
+    if (nc2 < 256) {
+        slices = 256 / nc2;
+        slice = tid / nc2;
+        first = tid - slice * nc2;
+        own = slice < slices ? 1 : 0;
+    } else {
+        own = (nc2 - 1 - tid) / 256 + 1;
+    }
+    double cx[4], cy[4];
+    unsigned long long acc[4][5];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int c = first + 256 * m, i = c / nc, j = c - i * nc;
+        cy[m] = (double)(i - half) * g.step_km;
+        cx[m] = (double)(j - half) * g.step_km;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) acc[m][k] = 0;
+    }
+    const auto sweep = [&](int count) {
+        for (int e = slice; e < count; e += slices) {
+            const CentreEntry p = tile[e];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                if (m >= own) continue;
+                const double dx = p.x - cx[m], dy = p.y - cy[m];
+                const double rr = dx * dx + dy * dy;
+                if (!(rr >= g.rr_lo && rr <= g.rr_hi)) continue;
+                const double r = sqrt(rr);
+                if (!(g.r_in <= r && r < g.r_out)) continue;
+                const bool centre = r == 0.0;
+                const double vr = centre ? 0.0 : (p.u * dx + p.v * dy) / r, vt = centre ? 0.0 : (p.v * dx - p.u * dy) / r;
+                acc[m][0] += 1ull;
+                acc[m][1] += p.s24;
+                acc[m][2] += p.q16;
+                acc[m][3] += fixed_point(vr, 16777216.0);
+                acc[m][4] += fixed_point(vt, 16777216.0);
+            }
+        }
+    };
+
+    const long long col = (long long)blockIdx.x * blockDim.x + tid;
+    const bool live = col < samples;  // (no return: the barriers are the whole workgroup's, and so is every loop bound below)
+    const long long cc = live ? col : samples - 1;
+    const long long l0 = (long long)blockIdx.y * lines_per_block;
+    const long long l1 = l0 + lines_per_block < lines ? l0 + lines_per_block : lines;
+    const int j0 = min(max(tp.sj0[cc], 0), tp.ns - 1), j1 = min(j0 + 1, tp.ns - 1);
+    const double ts = tp.st[cc], ws0 = 1.0 - ts, ws1 = ts;
+    const double half_c = 0.5 * g.cos_g;
+    int tie_cur = -1;
+    TieRows q;
+    int fill = 0, word = 0;  // entries in the tile; the word that counts the line at hand
+    if constexpr (!DIRECT) {
+        if (tid < 3) line_count[tid] = 0;
+        __syncthreads();
+    }
+    for (long long l = l0; l < l1; l += XSW_GRID_LINES) {
+        Px px[XSW_GRID_LINES];
+#pragma unroll
+        for (int k = 0; k < XSW_GRID_LINES; ++k) {
+            px[k] = Px{0.0, 0.0, false};
+            if (live && l + k < l1) {
+                const long long i = (l + k) * samples + col;
+                px[k] = src.fetch(i);
+                if (keep) px[k].ok = px[k].ok && keep[i] != 0;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < XSW_GRID_LINES; ++k) {
+            if (l + k >= l1) break;
+            const int i0 = min(max(tp.li0[l + k], 0), tp.nl - 1);
+            const double tl = tp.lt[l + k];
+            if (i0 != tie_cur) {
+                q = tie_rows(tp.tlon, tp.tlat, tp.tcos, tp.tsin, i0, min(i0 + 1, tp.nl - 1), j0, j1, tp.ns, ws0, ws1);
+                tie_cur = i0;
+            }
+            const TiePoint p = tie_point(q, 1.0 - tl, tl);
+            const double re = px[k].a, im = px[k].b;
+            const double qq = re * re + im * im, sp = sqrt(qq);
+            const double u = -(re * p.ch + im * p.sh), v = -(im * p.ch - re * p.sh);
+            double dl = p.lon - g.lon_g;
+            dl = dl - 360.0 * __builtin_rint(dl / 360.0);
+            const double dy = (p.lat - g.lat_g) * D2R, h = 0.5 * dy;
+            const double m = (g.cos_g - g.sin_g * h) - half_c * (h * h);
+            const double x = (KX * dl) * m, y = R_KM * dy;
+            const bool ok = px[k].ok && !(u != u) && !(v != v) && qq < 65536.0;
+            if constexpr (DIRECT) {
+                if (!ok) continue;
+                const unsigned long long s24 = fixed_point(sp, 16777216.0), q16 = fixed_point(qq, 65536.0);
+                for (int i = 0; i < nc; ++i) {
+                    const double ddy = y - (double)(i - half) * g.step_km;
+                    for (int j = 0; j < nc; ++j) {
+                        const double ddx = x - (double)(j - half) * g.step_km;
+                        const double r = sqrt(ddx * ddx + ddy * ddy);
+                        if (!(g.r_in <= r && r < g.r_out)) continue;  // (a NaN radius fails)
+                        const bool centre = r == 0.0;
+                        const double vr = centre ? 0.0 : (u * ddx + v * ddy) / r, vt = centre ? 0.0 : (v * ddx - u * ddy) / r;
+                        unsigned long long *out = sums + i * nc + j;
+                        atomicAdd(out, 1ull);
+                        atomicAdd(out + nc2, s24);
+                        atomicAdd(out + 2 * nc2, q16);
+                        atomicAdd(out + 3 * nc2, fixed_point(vr, 16777216.0));
+                        atomicAdd(out + 4 * nc2, fixed_point(vt, 16777216.0));
+                    }
+                }
+            } else {
+                // (a): fill <= TILE - 256 here and a line has at most 256 survivors, so every index below is inside the tile
+                const bool survives = ok && fabs(x) < g.bound && fabs(y) < g.bound;
+                const unsigned long long mask = __ballot(survives);
+                int base = 0;
+                if (lane == 0 && mask) base = atomicAdd(&line_count[word], __popcll(mask));
+                base = __shfl(base, 0);
+                if (survives) {
+                    const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+                    tile[fill + base + rank] = CentreEntry{x, y, u, v, fixed_point(sp, 16777216.0), fixed_point(qq, 65536.0)};
+                }
+                __syncthreads();
+                fill += min(max(line_count[word], 0), 256);
+                // the word of the line after the next: read for the last time before this barrier, added to after the next one
+                if (tid == 0) line_count[(word + 2) % 3] = 0;
+                word = (word + 1) % 3;
+                if (fill > TILE - 256) {  // (b); workgroup-uniform
+                    sweep(fill);
+                    __syncthreads();  // the tile has been read
+                    fill = 0;
+                }
+            }
+        }
+    }
+    if constexpr (!DIRECT) {
+        sweep(fill);
+        if (slices > 1) {  // workgroup-uniform: the groups' partial sums meet in the tile, [5][256] words
+            unsigned long long *meet = (unsigned long long *)tile;
+            __syncthreads();  // the tile has been read
+#pragma unroll
+            for (int k = 0; k < 5; ++k) meet[k * 256 + tid] = 0;
+            __syncthreads();
+            if (own && acc[0][0]) {
+#pragma unroll
+                for (int k = 0; k < 5; ++k) atomicAdd(&meet[k * 256 + first], acc[0][k]);
+            }
+            __syncthreads();
+            if (tid < nc2 && meet[tid]) {  // (c)
+#pragma unroll
+                for (int k = 0; k < 5; ++k) atomicAdd(sums + k * nc2 + tid, meet[k * 256 + tid]);
+            }
+        } else {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {  // (c)
+                if (m >= own || !acc[m][0]) continue;
+#pragma unroll
+                for (int k = 0; k < 5; ++k) atomicAdd(sums + k * nc2 + first + 256 * m, acc[m][k]);
+            }
+        }
+    }
+}
+
+template <typename Src>
+static void launch_centre(hipStream_t stream, int path, const Src &src, const void *keep, long long lines, long long samples, const Centre &g,
+                          const GridTies &tp, int64_t *sums)
+{
+    const Strips s = strip_grid(lines, samples);
+    const long long cap = std::max<long long>(XSW_CENTRE_MAX_LINES, (lines + 65534) / 65535);  // grid.y stays within 65535
+    const long long lpb = std::max<long long>(std::min<long long>(s.rows_per_block, cap), XSW_GRID_MIN_LINES);
+    const dim3 grid((unsigned)s.gx, (unsigned)((lines + lpb - 1) / lpb));
+    if (path == CENTRE_DIRECT)
+        hipLaunchKernelGGL((k_wind_centre<Src, true>), grid, dim3(256), 0, stream, src, (const unsigned char *)keep, lines, samples, g, tp, lpb,
+                           (unsigned long long *)sums);
+    else
+        hipLaunchKernelGGL((k_wind_centre<Src, false>), grid, dim3(256), 0, stream, src, (const unsigned char *)keep, lines, samples, g, tp, lpb,
+                           (unsigned long long *)sums);
+}
+
 }  // namespace
 
 extern "C" int xsw_wind_grid(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, int32_t src_kind, const void *src, const uint8_t *keep,
@@ -710,6 +953,65 @@ extern "C" int xsw_wind_polar(xsw_ctx *c, int64_t lines, int64_t samples, int32_
             launch_polar(c->stream, path, s, x[1].dev, lines, samples, g, ss, sc, tp, out);
         }
     }, "wind_polar");
+}
+
+extern "C" int xsw_wind_centre(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, int32_t src_kind, const void *src, const uint8_t *keep,
+                               int32_t n_tie_lines, int32_t n_tie_samples, const double *tie_lon, const double *tie_lat, const double *tie_cos,
+                               const double *tie_sin, const int32_t *line_first, const double *line_t, const int32_t *sample_first,
+                               const double *sample_t, double lon_g, double lat_g, double cos_lat_g, double sin_lat_g, double step_km, int32_t n_c,
+                               double r_in_km, double r_out_km, int64_t *sums)
+{
+    if (!c) return XSW_EINVAL;
+    if (!src) return fail(c, XSW_EINVAL, "wind_centre: no source");
+    if (!sums) return fail(c, XSW_EINVAL, "wind_centre: no sums");
+    if (src_kind != XSW_CELLS_C128 && src_kind != XSW_CELLS_C64 && src_kind != XSW_CELLS_CODES)
+        return fail(c, XSW_EINVAL, "wind_centre: src_kind must be XSW_CELLS_C128, XSW_CELLS_C64 or XSW_CELLS_CODES");
+    if (src_kind == XSW_CELLS_CODES && !c->have_co) return fail(c, XSW_ENOLUT, "wind_centre: co-pol codes given but no co-pol LUT on this context");
+    if (!tie_lon || !tie_lat || !tie_cos || !tie_sin || !line_first || !line_t || !sample_first || !sample_t || n_tie_lines < 1 || n_tie_samples < 1)
+        return fail(c, XSW_EINVAL, "wind_centre: tie points are required: their four grids, both brackets and one point or more per axis");
+    if (lines < 1 || samples < 1) return fail(c, XSW_EINVAL, "wind_centre: the raster must have one line and one sample or more");
+    if (int rc = check_dims(c, "wind_centre", lines, samples)) return rc;
+    if (bad_mem(mem)) return fail(c, XSW_EINVAL, "bad mem kind");
+    if (!std::isfinite(lon_g) || !std::isfinite(lat_g) || !(std::fabs(lat_g) <= 89.0))
+        return fail(c, XSW_EINVAL, "wind_centre: the first guess needs a finite longitude and a latitude within 89 degrees of the equator");
+    if (!std::isfinite(cos_lat_g) || !std::isfinite(sin_lat_g)) return fail(c, XSW_EINVAL, "wind_centre: cos and sin of the first guess's latitude must be finite");
+    if (n_c < 1 || n_c > XSW_CENTRE_MAX_N || n_c % 2 != 1)
+        return fail(c, XSW_EINVAL, "wind_centre: n_c must be odd, from 1 to %d, not %d", XSW_CENTRE_MAX_N, (int)n_c);
+    if (n_c > 1 && (!std::isfinite(step_km) || !(step_km > 0.0))) return fail(c, XSW_EINVAL, "wind_centre: step_km must be finite and positive");
+    if (!std::isfinite(r_in_km) || !std::isfinite(r_out_km) || !(r_in_km >= 0.0) || !(r_in_km < r_out_km))
+        return fail(c, XSW_EINVAL, "wind_centre: the annulus needs finite radii with 0 <= r_in_km < r_out_km");
+    bool bad_env;
+    const int path = centre_path(bad_env);
+    if (bad_env) return fail(c, XSW_EINVAL, "wind_centre: XSW_CENTRE_PATH must be direct, or unset");
+    const size_t npx = (size_t)lines * samples, ties = (size_t)n_tie_lines * n_tie_samples * 8;
+    const size_t elem = src_kind == XSW_CELLS_C128 ? 16 : src_kind == XSW_CELLS_C64 ? 8 : 4;
+    Buf b[11] = {{src, nullptr, npx * elem}, in_buf(keep, npx), {tie_lon, nullptr, ties}, {tie_lat, nullptr, ties}, {tie_cos, nullptr, ties},
+                 {tie_sin, nullptr, ties}, {line_first, nullptr, (size_t)lines * 4}, {line_t, nullptr, (size_t)lines * 8},
+                 {sample_first, nullptr, (size_t)samples * 4}, {sample_t, nullptr, (size_t)samples * 8},
+                 {sums, sums, (size_t)n_c * n_c * 40}};  // copied up, added to, copied down
+    Centre g;
+    g.lon_g = lon_g - 360.0 * std::rint(lon_g / 360.0);
+    g.lat_g = lat_g; g.cos_g = cos_lat_g; g.sin_g = sin_lat_g;
+    g.step_km = n_c > 1 ? step_km : 0.0;  // one candidate: the first guess itself, whatever step_km holds
+    g.r_in = r_in_km; g.r_out = r_out_km; g.n_c = (int)n_c;
+    const double wide = 1.0 + 0x1p-40, up = 1.0 + 0x1p-50, down = 1.0 - 0x1p-50;  // k_wind_centre's comment has the reasons
+    g.rr_lo = (r_in_km * r_in_km) * down;
+    g.rr_hi = (r_out_km * r_out_km) * up;
+    g.bound = ((double)((n_c - 1) / 2) * g.step_km + r_out_km) * wide;
+    return run(c, mem, b, [&](Buf (&x)[11]) {
+        GridTies tp;
+        tp.tlon = (const double *)x[2].dev; tp.tlat = (const double *)x[3].dev; tp.tcos = (const double *)x[4].dev; tp.tsin = (const double *)x[5].dev;
+        tp.li0 = (const int *)x[6].dev; tp.lt = (const double *)x[7].dev; tp.sj0 = (const int *)x[8].dev; tp.st = (const double *)x[9].dev;
+        tp.nl = n_tie_lines; tp.ns = n_tie_samples;
+        int64_t *out = (int64_t *)x[10].dev;
+        if (src_kind == XSW_CELLS_C128) { SrcC128 s; s.p = (const double2 *)x[0].dev; launch_centre(c->stream, path, s, x[1].dev, lines, samples, g, tp, out); }
+        else if (src_kind == XSW_CELLS_C64) { SrcC64 s; s.p = (const float2 *)x[0].dev; launch_centre(c->stream, path, s, x[1].dev, lines, samples, g, tp, out); }
+        else {
+            SrcCodes s;
+            s.p = (const unsigned *)x[0].dev; s.sol = c->T.sol; s.plane = (long long)c->T.n_w * c->T.n_phi;
+            launch_centre(c->stream, path, s, x[1].dev, lines, samples, g, tp, out);
+        }
+    }, "wind_centre");
 }
 
 extern "C" int xsw_wind_cells(xsw_ctx *c, int64_t lines, int64_t samples, int32_t mem, int32_t src_kind, const void *src, const uint8_t *keep,

@@ -165,6 +165,23 @@ class CopolCodes:
         return _polar.codes_polar(self.codes, self.lut_co, tie_points, centre=centre, radius=radius, sectors=sectors, line=line, sample=sample,
                                   keep=keep, into=into)
 
+    def centre_scores(self, tie_points, *, first_guess, step_km, n, annulus, line=None, sample=None, keep=None, into=None):
+        """`xsarsea_amd.wind_centre_scores(self.wind(), tie_points, first_guess=..., step_km=..., n=..., annulus=..., ...)` from the
+        stored codes: the annulus sums of the co-pol wind around every candidate centre of a lattice (`CentreScores`).  The pass
+        reads the 4-byte codes and expands nothing; the result equals that of the complex128 expansion bit for bit.  Arguments
+        and refusals as `wind_centre_scores`."""
+        from .. import centre as _centre
+        return _centre.codes_centre_scores(self.codes, self.lut_co, tie_points, first_guess=first_guess, step_km=step_km, n=n, annulus=annulus,
+                                           line=line, sample=sample, keep=keep, into=into)
+
+    def find_centre(self, tie_points, *, annulus, first_guess=None, steps_km=(8.0, 2.0, 0.5), n=9, criterion="vt", keep=None, line=None, sample=None,
+                    min_coverage=0.9, rotation=None):
+        """`xsarsea_amd.find_centre(self.wind(), tie_points, annulus=..., ...)` from the stored codes: the cyclone's centre, coarse
+        to fine, with nothing expanded (`CentreFix`).  Arguments and refusals as `find_centre`."""
+        from .. import centre as _centre
+        return _centre.codes_find_centre(self.codes, self.lut_co, tie_points, first_guess=first_guess, steps_km=steps_km, n=n, annulus=annulus,
+                                         criterion=criterion, keep=keep, line=line, sample=sample, min_coverage=min_coverage, rotation=rotation)
+
     def dual(self, sigma0_dual, dsig_cr=0.1, model=None, dual_select=True, codes=False, **kwargs):
         """`wind_dual`, the second element of `invert_from_model(inc, sigma0, sigma0_dual, model=(co, model), dsig_cr=...)`, bit
         for bit, from the stored co-pol codes.  model: the cross-pol model; **kwargs go to its `to_lut`.  dual_select=False:
